@@ -2,7 +2,7 @@
 """Solver-update benchmark: DPM-Solver++(2M), 20 steps, [256,4,64,64] fp16, frozen model_fn (BASELINE.json
 configs[1]) on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,10 +16,15 @@ kernel over 32 x 4.2 M elements), so a launch's ramp-up and drain are paid once 
 A *step* is P = 30 (`--trajectories-per-step`) complete 20-stage trajectories of those R requests: 600 fused launches,
 P x R x 256 = 245 760 samples, about 0.125 s -- so that the driver's `--steps 20` is a SUSTAINED 2.5 s measurement (clocks,
 HBM thermals), not an 80 ms burst.  Every input is resident in HBM before the clock starts; the network outputs are
-pre-staged in buffers distinct from x.  A timed region shorter than 2 s is not reported: the step count is
-raised until the region is long enough, and `steps` in the JSON line is the number of steps actually timed
-(`steps_requested` is what --steps asked for).  `sustained` carries the region's length and the throughput of its second
+pre-staged in buffers distinct from x (SURVEY 8d).  Exactly --steps steps are timed (`steps` in the JSON line);
+`ms_per_step` is the wall time of one of them.  `sustained` carries the region's length and the throughput of its second
 half over its first half (a throttling check).
+
+A plain run sets up, warms up, times the steps and prints the headline line; `--dump-outputs DIR` also writes the final
+states of the last timed step as float32 .npy files (request 0 whole, a fixed seeded sample of every request).  Everything
+else -- the per-rank preflight of a single-process run, the parity spot check, the secondary measurements, the other
+BASELINE configurations (`configs`), `cpu_baseline`, `cold_start_ms`, the committed reference figures -- runs with
+`--full` only.  A torch.distributed.run launch always runs the preflight.
 
 Back-to-back fused launches are also the CONSERVATIVE regime: each launch finds the write-back Infinity Cache full of its
 predecessor's dirty stores and pays for them; behind a real network (reads) the cache is clean, absorbs up to 256 MB of the
@@ -67,7 +72,6 @@ STUB = os.environ.get("DPM_BENCH_STUB") == "1"
 
 B, SHAPE, STEPS_SOLVER = 256, (4, 64, 64), 20
 HBM_PEAK_GBS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is what a copy achieves
-MIN_REGION_S = 2.0          # shorter timed regions are not reported (sustained clocks, not a burst)
 _DT = {"fp16": torch.float16, "fp32": torch.float32, "bf16": torch.bfloat16}
 
 
@@ -399,6 +403,22 @@ def lab_secondary(dtype_name, eps_dtype_name, loop_net, requests, timeout=600):
         return dict(error="%s: %s" % (type(e).__name__, e))
 
 
+def dump_outputs(out_dir, sets, resm):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the final state of every request in
+    flight -- as float32 .npy files: request 0 whole ([256,4,64,64], 16.8 MB) and the same fixed, seeded sample of elements
+    of every request ([R, k], k = 65536 at R = 32; at most 44 MB whatever R is).  Returns the file names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    finals = [s_["x"][resm[r]] for r, s_ in enumerate(sets)]
+    n = finals[0].numel()
+    k = min(n, 65536, 11 * 2 ** 20 // len(finals))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))).to(finals[0].device)
+    out = {"x_final_request0": finals[0].float().cpu().numpy(),
+           "x_final_sample": torch.stack([f.reshape(-1)[idx] for f in finals]).float().cpu().numpy()}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in out)
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # preflight: every rank proves its OWN device ordinal before anything is timed (VERDICT round 5, item 4)
 # ---------------------------------------------------------------------------------------------------------------
@@ -502,8 +522,11 @@ def main():
     ap.add_argument("--trajectories-per-step", type=int, default=30,
                     help="a step = this many 20-stage trajectories of the requests in flight (30 x 32 x 256 samples, ~0.125 s): "
                          "the driver's --steps 20 is then a sustained 2.5 s region")
-    ap.add_argument("--min-region-s", type=float, default=MIN_REGION_S,
-                    help="shortest timed region that is reported (profiling runs under rocprofv3 pass a small value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: preflight, parity spot check, secondary measurements, "
+                         "configs, cpu_baseline, cold_start_ms, committed reference figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the final states of the last step as DIR/<name>.npy (float32, < 64 MB)")
     ap.add_argument("--loop-net", default="conv", choices=["gemm", "conv", "none"],
                     help="network of the in_network_loop secondary measurement (conv: MIOpen 3x3 conv stack, falls back to "
                          "gemm: hipBLASLt per-pixel MLP)")
@@ -556,6 +579,7 @@ def main():
             os.dup2(saved_fd, 1)
             os.close(saved_fd)
     assert world == args.gpus, "launch with torch.distributed.run --nproc-per-node %d" % args.gpus
+    assert not (STUB and args.dump_outputs), "a stubbed run computes nothing to dump"
     if STUB:
         dev = torch.device("cpu")
         sync = lambda *a: None
@@ -582,7 +606,7 @@ def main():
 
     # ---- preflight: every rank on its own ordinal, before anything is timed; all ranks report, then a failure stops the run --
     pre = None
-    if True:
+    if args.full or args.preflight or dist is not None:
         mine = preflight(D, L, dev, rank, world, dist, stub=STUB)
         allp = [mine]
         if dist is not None:
@@ -636,40 +660,41 @@ def main():
         sync(dev)
 
     # ---- parity spot check outside the timed region: fused launches == the Python host loop (single launches) ---
-    trajectory()
-    sync(dev)
-    for r in (() if STUB else sorted({0, R - 1})):
-        s_ = sets[r]
-        dchk = D.DPM_Solver(D.model_wrapper(lambda x, t, e=s_["eps"]: e, ns), ns, state_dtype=dtype)
-        want = dchk.sample(s_["x"][0], steps=STEPS_SOLVER, order=2)
-        torch.cuda.synchronize(dev)
-        assert torch.equal(s_["x"][resm[r]], want), "fused multi-request launches and the Python loop disagree (request %d)" % r
+    if args.full and not STUB:
+        trajectory()
+        sync(dev)
+        for r in sorted({0, R - 1}):
+            s_ = sets[r]
+            dchk = D.DPM_Solver(D.model_wrapper(lambda x, t, e=s_["eps"]: e, ns), ns, state_dtype=dtype)
+            want = dchk.sample(s_["x"][0], steps=STEPS_SOLVER, order=2)
+            torch.cuda.synchronize(dev)
+            assert torch.equal(s_["x"][resm[r]], want), "fused multi-request launches and the Python loop disagree (request %d)" % r
 
     for _ in range(args.warmup):
         step()
     steps = args.steps
-    while True:
-        barrier()
-        ev0, ev1, evm = (Event(enable_timing=True) for _ in range(3))
-        t0 = time.perf_counter()
-        ev0.record(stream)                              # HIP events on the launch stream, around the timed region
-        for k in range(steps):
-            if k == steps // 2:
-                evm.record(stream)                      # midpoint: second half vs first half = throttling check
-            step()
-        ev1.record(stream)
-        barrier()
-        wall = time.perf_counter() - t0
-        region_us = ev0.elapsed_time(ev1) * 1e3         # GPU time of the K steps = K * P * 20 fused launches
-        h1_us, h2_us = ev0.elapsed_time(evm) * 1e3, evm.elapsed_time(ev1) * 1e3
-        wall_min = wall
-        if dist is not None:
-            tw = torch.tensor([wall, -wall], dtype=torch.float64, device=dev)
-            dist.all_reduce(tw, op=dist.ReduceOp.MAX)                 # max over ranks (and, negated, the min)
-            wall, wall_min = float(tw[0].item()), -float(tw[1].item())
-        if wall >= args.min_region_s:
-            break
-        steps = int(steps * max(2.0, 1.3 * args.min_region_s / max(wall, 1e-6))) + 1   # too short to report: time more steps
+    assert steps >= 1, "--steps must be at least 1"
+    barrier()
+    ev0, ev1, evm = (Event(enable_timing=True) for _ in range(3))
+    t0 = time.perf_counter()
+    ev0.record(stream)                                  # HIP events on the launch stream, around the timed region
+    for k in range(steps):
+        if k == steps // 2:
+            evm.record(stream)                          # midpoint: second half vs first half = throttling check
+        step()
+    ev1.record(stream)
+    barrier()
+    wall = time.perf_counter() - t0
+    region_us = ev0.elapsed_time(ev1) * 1e3             # GPU time of the K steps = K * P * 20 fused launches
+    h1_us, h2_us = ev0.elapsed_time(evm) * 1e3, evm.elapsed_time(ev1) * 1e3
+    wall_min = wall
+    if dist is not None:
+        tw = torch.tensor([wall, -wall], dtype=torch.float64, device=dev)
+        dist.all_reduce(tw, op=dist.ReduceOp.MAX)                     # max over ranks (and, negated, the min)
+        wall, wall_min = float(tw[0].item()), -float(tw[1].item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, sets, resm)
 
     # ---- roofline of the timed region ---------------------------------------------------------------------------
     n_el = B * int(np.prod(SHAPE))
@@ -710,7 +735,7 @@ def main():
                     host_wall=dict(achieved=round(traj_alg_bytes * R * steps * P / wall / 1e9, 1),
                                    frac=round(traj_alg_bytes * R * steps * P / wall / 1e9 / HBM_PEAK_GBS, 4)))
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         # (1) kernel-only durations of the fused launches (start -> stop events of each launch)
         msb = (C.c_float * (R * n_stages))()
         ko = []
@@ -787,7 +812,7 @@ def main():
 
     # ---- the drop-in Python API on the same workload: DPM_Solver.sample() per request, frozen network ------------
     py_ms = py_req_ms = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         s_ = sets[0]
         dpy = D.DPM_Solver(D.model_wrapper(lambda x, t, e=s_["eps"]: e, ns), ns, state_dtype=dtype)
         for _ in range(5):
@@ -841,7 +866,7 @@ def main():
     # ---- secondaries on the LAB build, in a subprocess: the stage kernel inside a real torch network loop (one request,
     # the drop-in sample() call), the no-arithmetic ceilings, the floor of the lone launch ------------------------------
     lab_configs = None
-    if not args.no_secondary and world == 1:
+    if args.full and not args.no_secondary and world == 1:
         torch.cuda.synchronize(dev)
         lab = lab_secondary(args.dtype, args.eps_dtype, args.loop_net, R)
         if "error" in lab:
@@ -868,7 +893,7 @@ def main():
 
     # ---- the OTHER BASELINE configurations on this run's clock (product library, this process): tools/config_bench.py ----
     configs = None
-    if world == 1 and not args.no_secondary and not args.no_configs and not STUB:
+    if world == 1 and args.full and not args.no_secondary and not args.no_configs and not STUB:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         try:
             import config_bench
@@ -921,26 +946,30 @@ def main():
             "collective_backend": (dist.get_backend() if dist is not None else None),
             "device_ordinals": ([p["ordinal"] for p in pre["ranks"]] if pre is not None else [None if STUB else local_rank]),
             "preflight": pre,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
 
         if STUB:
             line["stub"] = True
             line["value"] = line["roofline"] = line["value_per_gpu"] = line["fastest_rank_value_per_gpu"] = None   # nothing was measured
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(ac)
-        if world == 1 and not args.no_secondary and not STUB:
+        if world == 1 and args.full and not args.no_secondary and not STUB:
             try:
                 line["cold_start_ms"] = cold_start()
             except Exception as e:                           # a secondary never takes the primary line down
                 line["cold_start_ms"] = dict(error="%s: %s" % (type(e).__name__, e))
-        try:     # the unmodified reference on the same kind of GPU through PyTorch-ROCm eager (tools/gpu_reference.py; committed)
-            gr = json.load(open(os.path.join(ROOT, "profiles", "gpu_reference.json")))
-            line["reference_on_mi355x"] = dict(
-                source="profiles/gpu_reference.json (tools/gpu_reference.py through gpurun; committed, not measured in this run)",
-                what=gr["what"], rows=[{k: r[k] for k in ("case", "reference_on_gpu_ms", "engine_ms", "speedup",
-                                                          "rel_err_vs_reference_on_gpu")} for r in gr["rows"]])
-        except Exception:
-            pass
+        if args.full:
+            try:     # the unmodified reference on the same kind of GPU through PyTorch-ROCm eager (tools/gpu_reference.py; committed)
+                gr = json.load(open(os.path.join(ROOT, "profiles", "gpu_reference.json")))
+                line["reference_on_mi355x"] = dict(
+                    source="profiles/gpu_reference.json (tools/gpu_reference.py on an MI355X; committed, not measured in this run)",
+                    what=gr["what"], rows=[{k: r[k] for k in ("case", "reference_on_gpu_ms", "engine_ms", "speedup",
+                                                              "rel_err_vs_reference_on_gpu")} for r in gr["rows"]])
+            except Exception:
+                pass
         if isinstance(line.get("roofline"), dict):
             # The driver's record of this line keeps the SCALAR fields of `roofline` / `cpu_baseline` and the last 2000
             # characters of the line (BENCH_r05.json: nested objects are dropped from `parsed`): the figures a reader needs are

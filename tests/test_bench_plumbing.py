@@ -30,14 +30,14 @@ def test_bench_multi_rank_plumbing_with_a_stubbed_timed_region(world):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "1",
-           "--requests", "2", "--trajectories-per-step", "3", "--min-region-s", "0.002", "--no-secondary", "--no-cpu-baseline"]
+           "--requests", "2", "--trajectories-per-step", "3", "--no-secondary", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                      # ONE JSON line, from rank 0
     line = json.loads(lines[0])
     assert line["stub"] is True and line["value"] is None and line["roofline"] is None
-    assert line["n_gpus"] == world and line["steps"] >= 4 and line["steps_requested"] == 4 and line["warmup"] == 1
+    assert line["n_gpus"] == world and line["steps"] == 4 and line["steps_requested"] == 4 and line["warmup"] == 1
     assert line["scaling"] == "weak" and line["higher_is_better"] is True and line["vs_baseline"] is None
     assert line["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
     cfg = line["config"]
@@ -156,3 +156,32 @@ def test_c_port_cpu_baseline_runs_here():
     out = bench.cpu_baseline_port_c(bench.sd_alphas_cumprod(), budget_s=2.0)
     assert out["kind"] == "port" and out["value"] > 0 and 1 <= out["cores"] <= out["host_cores"]
     assert out["single_thread"]["threads"] == 1 and "dpm_oracle_kernels.c" in out["sample"]
+
+
+def test_dump_outputs_writes_the_final_states_as_a_fixed_float32_sample(tmp_path):
+    """`--dump-outputs DIR`: the final state of every request after the last timed step -- request 0 whole and the same seeded
+    sample of elements of every request, float32, identical from call to call, under 64 MB"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.B * int(np.prod(bench.SHAPE))
+    # every element holds its own position (+ 0.5 x the request): the sample shows which elements it took
+    pos = lambda k: (torch.arange(n, dtype=torch.float32) + 0.5 * k).reshape((bench.B,) + bench.SHAPE)
+    sets = [dict(x=[torch.zeros((bench.B,) + bench.SHAPE), pos(k)]) for k in range(3)]
+    resm = [1, 1, 1]
+    names = bench.dump_outputs(str(tmp_path / "a"), sets, resm)
+    assert names == bench.dump_outputs(str(tmp_path / "b"), sets, resm) == ["x_final_request0.npy", "x_final_sample.npy"]
+    total = 0
+    for name in names:
+        a, b = np.load(str(tmp_path / "a" / name)), np.load(str(tmp_path / "b" / name))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total < 64 * 2 ** 20
+    np.testing.assert_array_equal(np.load(str(tmp_path / "a" / names[0])), pos(0).numpy())
+    sample = np.load(str(tmp_path / "a" / names[1]))
+    assert sample.shape == (3, 65536)
+    idx = sample[0]
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n          # distinct positions, in order
+    for k in range(3):
+        np.testing.assert_array_equal(sample[k], idx + 0.5 * k)            # the same positions in every request

@@ -35,7 +35,7 @@ tests)
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log ;;
 bench)
-  ( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ); echo "bench rc=$?"; tail -3 $O/bench_default.err
+  ( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ); echo "bench rc=$?"; tail -3 $O/bench_default.err
   python - <<PY
 import json
 d = json.load(open("$O/bench_default.json")); r = d["roofline"]

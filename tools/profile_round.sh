@@ -10,8 +10,8 @@ cd "$ROOT"
 export TMPDIR=/tmp
 P=$ROOT/gpurun_out/prof_${TAG}_$DT
 rm -rf "$P"; mkdir -p "$P"
-python bench.py --dtype $DT > "$P/bench.json" 2> "$P/bench.err"
-CMD="python bench.py --dtype $DT --steps 12 --warmup 2 --trajectories-per-step 2 --min-region-s 0.05 --no-cpu-baseline --no-secondary"
+python bench.py --dtype $DT --full > "$P/bench.json" 2> "$P/bench.err"
+CMD="python bench.py --dtype $DT --steps 12 --warmup 2 --trajectories-per-step 2"
 rocprofv3 --kernel-trace --stats --output-format rocpd csv -d "$P/kt" -o kt -- $CMD > "$P/bench_kt.json" 2> "$P/bench_kt.err"
 find "$P/kt" -name "*kernel_stats.csv" -exec cp {} "$P/kernel_stats.csv" \;
 find "$P/kt" -name "*kernel_trace.csv" -delete
