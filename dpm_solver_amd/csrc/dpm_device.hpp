@@ -1,8 +1,8 @@
 // dpm_device.hpp -- gfx950 (MI355X, CDNA4) device code of the DPM-Solver engine: element types, the fused stage
 // kernels (streaming + dynamic thresholding) and their launch plumbing, in five parts included at the end of this
 // file (dpm_access.hpp, dpm_stage_kernel.hpp, dpm_thresh_{common,select,kernel}.hpp, dpm_aux_kernels.hpp, dpm_launch.hpp).  Included by
-// two translation units per (state dtype, eps dtype) pair (dpm_stage_*.hip) so the instantiation matrix compiles in
-// parallel, and by dpm_kernels.hip (C ABI entry points, add_noise, adaptive error norm, calibration).
+// dpm_stage_unit.hip, compiled twice per (state dtype, eps dtype) pair (dpm_internal.hpp: DPM_PAIRS) so the instantiation
+// matrix compiles in parallel, and by dpm_kernels.hip (C ABI entry points, add_noise, adaptive error norm, calibration).
 //
 // One fused, HBM-streaming kernel per solver stage:
 //
@@ -37,8 +37,7 @@
 #include <new>
 
 #include "dpm_hip.h"
-
-int dpm_set_error(int code, const char* fmt, ...);  // dpm_host.cpp
+#include "dpm_internal.hpp"
 
 #ifndef DPM_LAB
 #define DPM_LAB 0   // 1: the lab build (include/dpm_lab.h): process-global tuning knobs, fault injection, experiments
@@ -122,7 +121,7 @@ using dpmk::device_context;
 using dpmk::cluster_fault_word;
 
 // The catch-all kernels of a dtype pair (run-time form / guidance: the one-element-per-lane stage kernel and the general
-// thresholding kernel) are compiled in ONE of the pair's two translation units (dpm_stage_<pair>.hip defines
+// thresholding kernel) are compiled in ONE of the pair's two translation units (unit A of dpm_stage_unit.hip defines
 // DPM_CATCHALL_HOME); the sibling unit launches them through their host-side handles.
 template <typename TS, typename TE>
 const void* dpm_catchall_thresh();

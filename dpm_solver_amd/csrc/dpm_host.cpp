@@ -9,6 +9,7 @@
 //
 // `ref :NNN` = line in the reference's dpm_solver_pytorch.py.
 #include "dpm_hip.h"
+#include "dpm_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -787,11 +788,6 @@ extern "C" int dpm_plan_timesteps(const dpm_plan* p, float* out, int cap, int* n
 // ------------------------------------------------------------------------------------------------
 // native sample loop (buffer choreography shared with the Python shim)
 // ------------------------------------------------------------------------------------------------
-// launch hooks implemented in dpm_kernels.hip
-int dpm_stage_launch_ev(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
-int dpm_timing_begin(int n, void*** starts, void*** stops);
-int dpm_timing_end(int n, void** starts, void** stops, void* stream, float* ms, const unsigned char* recorded);
-
 // buffer rotation of one stage, shared by the single- and multi-request loops: which xbuf the network saw (xe) and
 // which one the stage writes (out), given where the state and the pending intermediate live.  Negative = plan error.
 static int stage_rotation(const dpm_stage& st, int n_stages, int state, int tmp, int* xe, int* out) {
@@ -861,9 +857,6 @@ extern "C" int dpm_plan_run(const dpm_plan* p, const dpm_run_buffers* rb, dpm_mo
                             int* result) {
   return plan_run_impl(p, rb, model, user, stream, result, nullptr, nullptr);
 }
-
-int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void** ev_start,
-                              void** ev_stop, int* fused_first);
 
 extern "C" int dpm_plan_run_multi(const dpm_plan* p, const dpm_run_buffers* rbs, int n_req, void* stream, float* ms,
                                   int* results) {

@@ -1,0 +1,56 @@
+// dpm_internal.hpp -- what the library's translation units share with each other and nothing else: the list of
+// (state dtype, network-output dtype) pairs the stage kernels are built for, and ONE declaration of every function that
+// is defined in one translation unit and called from another.  Included by dpm_device.hpp and by dpm_host.cpp.
+#pragma once
+#include <cstdint>
+
+#include "dpm_hip.h"
+
+// The dtype pairs: name (the build's object files dpm_stage_<name>.o / dpm_stage_<name>_b.o), state type, network-output
+// type, their DPM_DTYPE_* codes.  Row i is compiled by dpm_stage_unit.hip with -DDPM_PAIR=i, so the order is the one of
+// __graft_entry__._PAIRS (the slowest units first).  The types are those of dpm_device.hpp.
+#define DPM_PAIRS(X)                                                         \
+  X(f32_bf16, float, dpmk::bf16_t, DPM_DTYPE_F32, DPM_DTYPE_BF16)            \
+  X(f32_f16, float, __half, DPM_DTYPE_F32, DPM_DTYPE_F16)                    \
+  X(f32_f32, float, float, DPM_DTYPE_F32, DPM_DTYPE_F32)                     \
+  X(bf16_bf16, dpmk::bf16_t, dpmk::bf16_t, DPM_DTYPE_BF16, DPM_DTYPE_BF16)   \
+  X(f16_f16, __half, __half, DPM_DTYPE_F16, DPM_DTYPE_F16)
+
+// The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
+// slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
+// pair's catch-all kernels.
+constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
+constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE);
+
+// ---- dpm_stage_unit.hip, instantiated once per pair and unit
+// one stage of the forms in FORMS; `multi` / n_multi: a thresholded stage of n_multi requests fused into one launch
+template <typename TS, typename TE, unsigned FORMS>
+int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
+                    const dpm_stage* dyn, const int32_t* skip, const dpm_buffers* multi, int n_multi);
+// one stage of n_req requests in one launch of the streaming family; MULTI_NOT_BUILT when it has no fused variant
+template <typename TS, typename TE>
+int dpm_launch_fused(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void* ev_start, void* ev_stop);
+
+// ---- dpm_f64.hip
+int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+int dpm_add_noise_f64(double alpha, double sigma, const void* x, const void* noise, void* out, int64_t n, void* stream);
+int dpm_blend_f64(const void* x, const void* mask, const void* a, const void* b, double alpha, double sigma, void* out,
+                  int64_t n, int64_t mask_period, void* stream);
+
+// ---- dpm_kernels.hip
+int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
+                         const dpm_stage* dyn, const int32_t* skip);
+int dpm_stage_launch_ev(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void** ev_start,
+                              void** ev_stop, int* fused_first);
+int dpm_timing_begin(int n, void*** starts, void*** stops);
+int dpm_timing_end(int n, void** starts, void** stops, void* stream, float* ms, const unsigned char* recorded);
+
+// ---- dpm_host.cpp
+namespace dpmc {
+template <class T>
+struct SchedViewT;
+}
+int dpm_set_error(int code, const char* fmt, ...);
+int dpm_schedule_table_is_f64(const dpm_schedule* s);
+dpmc::SchedViewT<float> dpm_schedule_view(const dpm_schedule* s);

@@ -1,7 +1,7 @@
 // dpm_kernels.hip -- gfx950 (MI355X, CDNA4) device code of the DPM-Solver engine.
 //
 // C ABI entry points of the device side; the stage kernels live in dpm_device.hpp and are instantiated per dtype
-// pair in dpm_stage_*.hip.
+// pair by dpm_stage_unit.hip.
 #include "dpm_device.hpp"
 #include "dpm_coef.hpp"
 
@@ -26,21 +26,94 @@ uint32_t* cluster_fault_word(int dev, bool create) {
 }
 }  // namespace dpmk
 
-// one translation unit per (state, eps) dtype pair
-int dpm_launch_f32_f32(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*);
-int dpm_launch_f32_f16(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*);
-int dpm_launch_f32_bf16(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*);
-int dpm_launch_f16_f16(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*);
-int dpm_launch_bf16_bf16(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*);
-int dpm_launch_f64(const dpm_stage*, const dpm_buffers*, void*, void*, void*);                     // dpm_f64.hip
-int dpm_add_noise_f64(double, double, const void*, const void*, void*, int64_t, void*);
-int dpm_blend_f64(const void*, const void*, const void*, const void*, double, double, void*, int64_t, int64_t, void*);
-int dpm_schedule_table_is_f64(const dpm_schedule* s);                                              // dpm_host.cpp
-int dpm_launch_multi_f32_f32(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
-int dpm_launch_multi_f32_f16(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
-int dpm_launch_multi_f32_bf16(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
-int dpm_launch_multi_f16_f16(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
-int dpm_launch_multi_bf16_bf16(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+namespace {
+// The stage launchers of one dtype pair (dpm_stage_unit.hip, dpm_internal.hpp): unit A's and unit B's single-request
+// launchers and unit A's fused multi-request one.  One row per entry of DPM_PAIRS.
+using UnitFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*,
+                       const dpm_buffers*, int);
+using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+struct PairUnits {
+  int state_dtype, eps_dtype;
+  UnitFn a, b;
+  FusedFn fused;
+};
+#define DPM_PAIR_ROW(name, TS, TE, SD, ED) \
+  {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>},
+constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
+#undef DPM_PAIR_ROW
+
+// the row of a (state, eps) dtype pair; nullptr: no stage kernels for it
+const PairUnits* pair_of(int sd, int ed) {
+  for (const PairUnits& p : kPairs)
+    if (p.state_dtype == sd && p.eps_dtype == ed) return &p;
+  return nullptr;
+}
+
+// the unit that builds a stage's update form: B for FORMS_B, A for every other value (A reports an unknown form)
+UnitFn unit_for(const PairUnits& p, int form) {
+  return form >= 0 && form < 32 && ((FORMS_B >> form) & 1u) ? p.b : p.a;
+}
+
+// one stage of n_req requests in one launch, or MULTI_NOT_BUILT (no error set) when it has no fused variant
+int launch_fused(const PairUnits& p, const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void* ev_start,
+                 void* ev_stop) {
+  if ((st->flags & DPM_F_THRESH) && !(st->flags & DPM_F_BLEND))  // one thresholding launch over all requests' samples
+    return unit_for(p, st->form)(st, bs, stream, ev_start, ev_stop, nullptr, nullptr, bs, n_req);
+  return p.fused(st, bs, n_req, stream, ev_start, ev_stop);
+}
+
+// The argument checks of one request (st and b not null): DPM_OK, or the error of the first check that fails -- set
+// (dpm_set_error) when `report`.  dpm_stage_launch_multi_ev asks without it whether a request may join a fused launch.
+int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool report = true) {
+  auto fail = [report](int code, const char* fmt, auto... args) { return report ? dpm_set_error(code, fmt, args...) : code; };
+  if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
+    return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
+  if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
+  const bool needs_x = st->form != DPM_FORM_DENOISE;
+  const bool needs_h1 = st->form == DPM_FORM_TWO || st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
+  const bool needs_h2 = st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
+  const bool need_xe = (st->flags & DPM_F_TO_X0) || st->model_type == DPM_MODEL_X_START || st->model_type == DPM_MODEL_V;
+  if (!b->e0 || !b->x_out) return fail(DPM_ERR_ARG, "stage_launch: e0 / x_out must not be null");
+  if ((needs_x || need_xe) && !b->x && !b->xe) return fail(DPM_ERR_ARG, "stage_launch: x is null");
+  if (needs_x && !b->x) return fail(DPM_ERR_ARG, "stage_launch: x is null");
+  if (needs_h1 && !b->h1) return fail(DPM_ERR_ARG, "stage_launch: form %d needs h1", st->form);
+  if (needs_h2 && !b->h2) return fail(DPM_ERR_ARG, "stage_launch: form %d needs h2", st->form);
+  if ((st->flags & DPM_F_STORE_M) && !b->m_out) return fail(DPM_ERR_ARG, "stage_launch: STORE_M without m_out");
+  if (st->guidance == DPM_GUIDE_CFG && !b->e1) return fail(DPM_ERR_ARG, "stage_launch: CFG needs e1");
+  if (st->guidance == DPM_GUIDE_CLASSIFIER && !b->g) return fail(DPM_ERR_ARG, "stage_launch: classifier guidance needs g");
+  if (st->flags & DPM_F_BLEND) {
+    if (!b->mask || !b->blend_a || b->mask_period < 1)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_BLEND needs mask, blend_a and mask_period >= 1");
+    if (b->n % b->mask_period != 0)
+      return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of mask_period=%lld", (long long)b->n,
+                  (long long)b->mask_period);
+    if (b->mask_period >= ((int64_t)1 << 31) && b->mask_period != b->n)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: a broadcast mask of 2^31 or more elements");
+  }
+  if (b->eps_stride != 0 && b->eps_stride < b->n / b->batch)
+    return fail(DPM_ERR_ARG, "stage_launch: eps_stride=%lld is smaller than a sample (%lld elements)",
+                (long long)b->eps_stride, (long long)(b->n / b->batch));
+  return DPM_OK;
+}
+
+// the auxiliary launchers' element type: f(float{}), f(__half{}) or f(bf16_t{}) for a DPM_DTYPE_* code; any other code is
+// `what`'s unsupported-dtype error
+template <class F>
+int with_elem_type(int dtype, const char* what, F&& f) {
+  switch (dtype) {
+    case DPM_DTYPE_F32: f(float{}); return DPM_OK;
+    case DPM_DTYPE_F16: f(__half{}); return DPM_OK;
+    case DPM_DTYPE_BF16: f(bf16_t{}); return DPM_OK;
+  }
+  return dpm_set_error(DPM_ERR_UNSUPPORTED, "%s: unsupported dtype %d", what, dtype);
+}
+
+// the status of the kernels just launched: DPM_OK, or the launch error as "<what>: <HIP's text>"
+int launch_status(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DPM_OK : dpm_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
+}
+}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -48,33 +121,8 @@ int dpm_launch_multi_bf16_bf16(const dpm_stage*, const dpm_buffers*, int, void*,
 int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
                          const dpm_stage* dyn, const int32_t* skip) {
   if (!st || !b) return dpm_set_error(DPM_ERR_ARG, "stage_launch: null pointer");
-  if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
-  if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
-  const bool needs_x = st->form != DPM_FORM_DENOISE;
-  const bool needs_h1 = st->form == DPM_FORM_TWO || st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
-  const bool needs_h2 = st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
-  const bool need_xe = (st->flags & DPM_F_TO_X0) || st->model_type == DPM_MODEL_X_START || st->model_type == DPM_MODEL_V;
-  if (!b->e0 || !b->x_out) return dpm_set_error(DPM_ERR_ARG, "stage_launch: e0 / x_out must not be null");
-  if ((needs_x || need_xe) && !b->x && !b->xe) return dpm_set_error(DPM_ERR_ARG, "stage_launch: x is null");
-  if (needs_x && !b->x) return dpm_set_error(DPM_ERR_ARG, "stage_launch: x is null");
-  if (needs_h1 && !b->h1) return dpm_set_error(DPM_ERR_ARG, "stage_launch: form %d needs h1", st->form);
-  if (needs_h2 && !b->h2) return dpm_set_error(DPM_ERR_ARG, "stage_launch: form %d needs h2", st->form);
-  if ((st->flags & DPM_F_STORE_M) && !b->m_out) return dpm_set_error(DPM_ERR_ARG, "stage_launch: STORE_M without m_out");
-  if (st->guidance == DPM_GUIDE_CFG && !b->e1) return dpm_set_error(DPM_ERR_ARG, "stage_launch: CFG needs e1");
-  if (st->guidance == DPM_GUIDE_CLASSIFIER && !b->g) return dpm_set_error(DPM_ERR_ARG, "stage_launch: classifier guidance needs g");
-  if (st->flags & DPM_F_BLEND) {
-    if (!b->mask || !b->blend_a || b->mask_period < 1)
-      return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_BLEND needs mask, blend_a and mask_period >= 1");
-    if (b->n % b->mask_period != 0)
-      return dpm_set_error(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of mask_period=%lld", (long long)b->n,
-                           (long long)b->mask_period);
-    if (b->mask_period >= ((int64_t)1 << 31) && b->mask_period != b->n)
-      return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: a broadcast mask of 2^31 or more elements");
-  }
-  if (b->eps_stride != 0 && b->eps_stride < b->n / b->batch)
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch: eps_stride=%lld is smaller than a sample (%lld elements)",
-                         (long long)b->eps_stride, (long long)(b->n / b->batch));
+  if (const int rc = check_stage_buffers(st, b)) return rc;
+  if (b->n == 0) return DPM_OK;
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -83,6 +131,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
     if (dyn) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: device-resident coefficients with a double state");
     return dpm_launch_f64(st, &bb, stream, ev_start, ev_stop);
   }
+  const PairUnits* p = pair_of(sd, ed);
+  if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused
@@ -91,24 +141,11 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   if (!dyn && !(st->flags & (DPM_F_THRESH | DPM_F_BLEND))) {
     const int big = tuning_for(bb.opts).big_tiles;
     if (big > 0 && (bb.n / EPT + 255) / 256 >= big) {
-      int (*fn)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*) = nullptr;
-      if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F32) fn = dpm_launch_multi_f32_f32;
-      else if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F16) fn = dpm_launch_multi_f32_f16;
-      else if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_BF16) fn = dpm_launch_multi_f32_bf16;
-      else if (sd == DPM_DTYPE_F16 && ed == DPM_DTYPE_F16) fn = dpm_launch_multi_f16_f16;
-      else if (sd == DPM_DTYPE_BF16 && ed == DPM_DTYPE_BF16) fn = dpm_launch_multi_bf16_bf16;
-      if (fn) {
-        const int rc = fn(st, &bb, 1, stream, ev_start, ev_stop);
-        if (rc != MULTI_NOT_BUILT) return rc;
-      }
+      const int rc = launch_fused(*p, st, &bb, 1, stream, ev_start, ev_stop);
+      if (rc != MULTI_NOT_BUILT) return rc;
     }
   }
-  if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F32) return dpm_launch_f32_f32(st, &bb, stream, ev_start, ev_stop, dyn, skip);
-  if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F16) return dpm_launch_f32_f16(st, &bb, stream, ev_start, ev_stop, dyn, skip);
-  if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_BF16) return dpm_launch_f32_bf16(st, &bb, stream, ev_start, ev_stop, dyn, skip);
-  if (sd == DPM_DTYPE_F16 && ed == DPM_DTYPE_F16) return dpm_launch_f16_f16(st, &bb, stream, ev_start, ev_stop, dyn, skip);
-  if (sd == DPM_DTYPE_BF16 && ed == DPM_DTYPE_BF16) return dpm_launch_bf16_bf16(st, &bb, stream, ev_start, ev_stop, dyn, skip);
-  return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
+  return unit_for(*p, st->form)(st, &bb, stream, ev_start, ev_stop, dyn, skip, nullptr, 0);
 }
 
 int dpm_stage_launch_ev(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
@@ -126,38 +163,21 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
                               void** ev_stop, int* fused_first) {
   if (!st || !bs || n_req < 1) return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: bad arguments");
   int done = 0;  // requests already advanced by fused launches
-  bool same = n_req > 1 && tuning_for(bs[0].opts).multi_fuse != 0;
-  for (int r = 1; r < n_req && same; ++r)
-    same = bs[r].n == bs[0].n && bs[r].batch == bs[0].batch && bs[r].state_dtype == bs[0].state_dtype &&
-           bs[r].eps_dtype == bs[0].eps_dtype;
-  if (same && bs[0].n > 0 && bs[0].batch > 0 && bs[0].n % bs[0].batch == 0) {
-    // the argument checks of the single launch, once per request
-    const bool needs_h1 = st->form == DPM_FORM_TWO || st->form == DPM_FORM_MS3;
-    const bool needs_h2 = st->form == DPM_FORM_MS3;
-    for (int r = 0; r < n_req && same; ++r) {
-      const dpm_buffers& b = bs[r];
-      same = b.e0 && b.x_out && (b.x || b.xe) && (!needs_h1 || b.h1) && (!needs_h2 || b.h2) &&
-             (!(st->flags & DPM_F_STORE_M) || b.m_out) && (st->guidance != DPM_GUIDE_CFG || b.e1);
-    }
-    const int sd = bs[0].state_dtype, ed = bs[0].eps_dtype;
-    int (*fn)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*) = nullptr;
-    if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F32) fn = dpm_launch_multi_f32_f32;
-    else if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_F16) fn = dpm_launch_multi_f32_f16;
-    else if (sd == DPM_DTYPE_F32 && ed == DPM_DTYPE_BF16) fn = dpm_launch_multi_f32_bf16;
-    else if (sd == DPM_DTYPE_F16 && ed == DPM_DTYPE_F16) fn = dpm_launch_multi_f16_f16;
-    else if (sd == DPM_DTYPE_BF16 && ed == DPM_DTYPE_BF16) fn = dpm_launch_multi_bf16_bf16;
-    if (same && fn) {
-      int r0 = 0;
-      for (; r0 < n_req; r0 += MULTI_MAX) {
-        const int cnt = std::min(MULTI_MAX, n_req - r0);
-        const int rc = fn(st, bs + r0, cnt, stream, ev_start ? ev_start[r0] : nullptr, ev_stop ? ev_stop[r0] : nullptr);
-        if (rc == MULTI_NOT_BUILT) break;  // no fused variant for this stage, or a buffer of this group is unaligned
-        if (rc) return rc;
-        if (fused_first)
-          for (int r = r0; r < r0 + cnt; ++r) fused_first[r] = r0;
-        done = r0 + cnt;
-      }
-    }
+  // a group fuses when its requests agree in size and dtypes and each one passes the single launch's checks; otherwise
+  // every request is launched on its own (and reports its own error)
+  const PairUnits* p = pair_of(bs[0].state_dtype, bs[0].eps_dtype);
+  bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0;
+  for (int r = 0; r < n_req && fuse; ++r)
+    fuse = bs[r].n == bs[0].n && bs[r].batch == bs[0].batch && bs[r].state_dtype == bs[0].state_dtype &&
+           bs[r].eps_dtype == bs[0].eps_dtype && check_stage_buffers(st, &bs[r], false) == DPM_OK;
+  for (int r0 = 0; fuse && r0 < n_req; r0 += MULTI_MAX) {
+    const int cnt = std::min(MULTI_MAX, n_req - r0);
+    const int rc = launch_fused(*p, st, bs + r0, cnt, stream, ev_start ? ev_start[r0] : nullptr, ev_stop ? ev_stop[r0] : nullptr);
+    if (rc == MULTI_NOT_BUILT) break;  // no fused variant for this stage, or a buffer of this group is unaligned
+    if (rc) return rc;
+    if (fused_first)
+      for (int r = r0; r < r0 + cnt; ++r) fused_first[r] = r0;
+    done = r0 + cnt;
   }
   for (int r = done; r < n_req; ++r) {
     const int rc = dpm_stage_launch_ev(st, &bs[r], stream, ev_start ? ev_start[r] : nullptr, ev_stop ? ev_stop[r] : nullptr);
@@ -259,36 +279,27 @@ extern "C" int dpm_add_noise_launch(const dpm_schedule* s, const float* t_host, 
   const int64_t cap = (int64_t)(di.n_cu > 0 ? di.n_cu : 256) * 16;
   if (blocks > cap) blocks = cap;
   const bool v2 = n % EPT == 0;
-  for (int j = 0; j < nt; ++j) {
-    float a = 0.f, sg = 0.f;
-    dpm_schedule_eval(s, DPM_EVAL_ALPHA, &t_host[j], 1, &a);
-    dpm_schedule_eval(s, DPM_EVAL_STD, &t_host[j], 1, &sg);
-    const int64_t off = (int64_t)j * n;
-#define DPM_AN(T)                                                                                                       \
-  do {                                                                                                                  \
-    const T* xp = (const T*)x;                                                                                          \
-    const T* np_ = (const T*)noise + off;                                                                               \
-    T* op = (T*)out + off;                                                                                              \
-    const size_t al = sizeof(T) * EPT;                                                                                  \
-    if (v2 && aligned(xp, al) && aligned(np_, al) && aligned(op, al)) {                                                 \
-      int64_t bl = (n / EPT + 255) / 256;                                                                               \
-      if (bl > cap) bl = cap;                                                                                           \
-      hipLaunchKernelGGL((add_noise_kernel<T, true>), dim3((unsigned)bl), dim3(256), 0, st, xp, np_, op, n, a, sg);     \
-    } else {                                                                                                            \
-      hipLaunchKernelGGL((add_noise_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, xp, np_, op, n, a, sg); \
-    }                                                                                                                   \
-  } while (0)
-    switch (dtype) {
-      case DPM_DTYPE_F32: DPM_AN(float); break;
-      case DPM_DTYPE_F16: DPM_AN(__half); break;
-      case DPM_DTYPE_BF16: DPM_AN(bf16_t); break;
-      default: return dpm_set_error(DPM_ERR_UNSUPPORTED, "add_noise: unsupported dtype %d", dtype);
+  const int rc = with_elem_type(dtype, "add_noise", [&](auto t) {
+    using T = decltype(t);
+    for (int j = 0; j < nt; ++j) {
+      float a = 0.f, sg = 0.f;
+      dpm_schedule_eval(s, DPM_EVAL_ALPHA, &t_host[j], 1, &a);
+      dpm_schedule_eval(s, DPM_EVAL_STD, &t_host[j], 1, &sg);
+      const int64_t off = (int64_t)j * n;
+      const T* xp = (const T*)x;
+      const T* np_ = (const T*)noise + off;
+      T* op = (T*)out + off;
+      const size_t al = sizeof(T) * EPT;
+      if (v2 && aligned(xp, al) && aligned(np_, al) && aligned(op, al)) {
+        int64_t bl = (n / EPT + 255) / 256;
+        if (bl > cap) bl = cap;
+        hipLaunchKernelGGL((add_noise_kernel<T, true>), dim3((unsigned)bl), dim3(256), 0, st, xp, np_, op, n, a, sg);
+      } else {
+        hipLaunchKernelGGL((add_noise_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, xp, np_, op, n, a, sg);
+      }
     }
-#undef DPM_AN
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "add_noise launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  });
+  return rc ? rc : launch_status("add_noise launch failed");
 }
 
 extern "C" int dpm_blend_launch(const void* x, const void* mask, const void* a, const void* b, float alpha, float sigma,
@@ -306,24 +317,12 @@ extern "C" int dpm_blend_launch(const void* x, const void* mask, const void* a, 
   ext.mask_period = mask_period;
   ext.blend_alpha = alpha;
   ext.blend_sigma = sigma;
-  switch (dtype) {
-    case DPM_DTYPE_F32:
-      hipLaunchKernelGGL(blend_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (const float*)x, (const float*)mask,
-                         (const float*)a, (const float*)b, (float*)out, n, ext);
-      break;
-    case DPM_DTYPE_F16:
-      hipLaunchKernelGGL(blend_kernel<__half>, dim3((unsigned)blocks), dim3(256), 0, st, (const __half*)x,
-                         (const __half*)mask, (const __half*)a, (const __half*)b, (__half*)out, n, ext);
-      break;
-    case DPM_DTYPE_BF16:
-      hipLaunchKernelGGL(blend_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)x,
-                         (const bf16_t*)mask, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n, ext);
-      break;
-    default: return dpm_set_error(DPM_ERR_UNSUPPORTED, "blend: unsupported dtype %d", dtype);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "blend launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  const int rc = with_elem_type(dtype, "blend", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(blend_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x, (const T*)mask, (const T*)a,
+                       (const T*)b, (T*)out, n, ext);
+  });
+  return rc ? rc : launch_status("blend launch failed");
 }
 
 extern "C" int dpm_adaptive_error_launch(const void* x_lower, const void* x_higher, const void* x_prev, float atol,
@@ -334,33 +333,17 @@ extern "C" int dpm_adaptive_error_launch(const void* x_lower, const void* x_high
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipError_t me = hipMemsetAsync(e_out + batch, 0, sizeof(float), st);  // the batch-maximum slot
   if (me != hipSuccess) return dpm_set_error((int)me, "hipMemsetAsync: %s", hipGetErrorString(me));
-  switch (dtype) {
-    case DPM_DTYPE_F32:
-      hipLaunchKernelGGL(adaptive_error_kernel<float>, dim3((unsigned)batch), dim3(1024), 0, st, (const float*)x_lower,
-                         (const float*)x_higher, (const float*)x_prev, atol, rtol, e_out, per_sample);
-      break;
-    case DPM_DTYPE_F16:
-      hipLaunchKernelGGL(adaptive_error_kernel<__half>, dim3((unsigned)batch), dim3(1024), 0, st, (const __half*)x_lower,
-                         (const __half*)x_higher, (const __half*)x_prev, atol, rtol, e_out, per_sample);
-      break;
-    case DPM_DTYPE_BF16:
-      hipLaunchKernelGGL(adaptive_error_kernel<bf16_t>, dim3((unsigned)batch), dim3(1024), 0, st, (const bf16_t*)x_lower,
-                         (const bf16_t*)x_higher, (const bf16_t*)x_prev, atol, rtol, e_out, per_sample);
-      break;
-    default: return dpm_set_error(DPM_ERR_UNSUPPORTED, "adaptive_error: unsupported dtype %d", dtype);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "adaptive_error launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  const int rc = with_elem_type(dtype, "adaptive_error", [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(adaptive_error_kernel<T>, dim3((unsigned)batch), dim3(1024), 0, st, (const T*)x_lower,
+                       (const T*)x_higher, (const T*)x_prev, atol, rtol, e_out, per_sample);
+  });
+  return rc ? rc : launch_status("adaptive_error launch failed");
 }
 
 // ------------------------------------------------------------------------------------------------
 // adaptive solver, controller on the device (include/dpm_hip.h: dpm_adaptive_*; ref :956-1010)
 // ------------------------------------------------------------------------------------------------
-dpmc::SchedView dpm_schedule_view(const dpm_schedule* s);  // dpm_host.cpp
-int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
-                         const dpm_stage* dyn, const int32_t* skip);
-
 namespace {
 struct AdaptiveDev {  // device-resident controller state
   float s, lambda_s, lambda_0, h, t_0, t_err, theta, t;
@@ -663,30 +646,22 @@ extern "C" int dpm_adaptive_begin(dpm_adaptive* a, void* x, void* x_prev, const 
   if (n > 0) {
     const DeviceInfo& di = device_info();
     const int64_t cap = (int64_t)(di.n_cu > 0 ? di.n_cu : 256) * 8;
-#define DPM_COMMIT(T)                                                                                                     \
-  do {                                                                                                                    \
-    const bool v = (n * (int64_t)sizeof(T)) % 16 == 0 && aligned(x, 16) && aligned(x_prev, 16) && aligned(x_lower, 16) && \
-                   aligned(x_higher, 16);                                                                                 \
-    int64_t bl = ((v ? n * (int64_t)sizeof(T) / 16 : n) + 255) / 256;                                                     \
-    if (bl > cap) bl = cap;                                                                                               \
-    if (v)                                                                                                                \
-      hipLaunchKernelGGL((adaptive_commit_kernel<T, true>), dim3((unsigned)bl), dim3(256), 0, st, a->dev, (T*)x,          \
-                         (T*)x_prev, (const T*)x_lower, (const T*)x_higher, n);                                           \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((adaptive_commit_kernel<T, false>), dim3((unsigned)bl), dim3(256), 0, st, a->dev, (T*)x,         \
-                         (T*)x_prev, (const T*)x_lower, (const T*)x_higher, n);                                           \
-  } while (0)
-    switch (dtype) {
-      case DPM_DTYPE_F32: DPM_COMMIT(float); break;
-      case DPM_DTYPE_F16: DPM_COMMIT(__half); break;
-      case DPM_DTYPE_BF16: DPM_COMMIT(bf16_t); break;
-      default: return dpm_set_error(DPM_ERR_UNSUPPORTED, "adaptive_begin: unsupported dtype %d", dtype);
-    }
-#undef DPM_COMMIT
+    const int rc = with_elem_type(dtype, "adaptive_begin", [&](auto t) {
+      using T = decltype(t);
+      const bool v = (n * (int64_t)sizeof(T)) % 16 == 0 && aligned(x, 16) && aligned(x_prev, 16) && aligned(x_lower, 16) &&
+                     aligned(x_higher, 16);
+      int64_t bl = ((v ? n * (int64_t)sizeof(T) / 16 : n) + 255) / 256;
+      if (bl > cap) bl = cap;
+      if (v)
+        hipLaunchKernelGGL((adaptive_commit_kernel<T, true>), dim3((unsigned)bl), dim3(256), 0, st, a->dev, (T*)x,
+                           (T*)x_prev, (const T*)x_lower, (const T*)x_higher, n);
+      else
+        hipLaunchKernelGGL((adaptive_commit_kernel<T, false>), dim3((unsigned)bl), dim3(256), 0, st, a->dev, (T*)x,
+                           (T*)x_prev, (const T*)x_lower, (const T*)x_higher, n);
+    });
+    if (rc) return rc;
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "adaptive_begin: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("adaptive_begin");
 }
 
 extern "C" int dpm_adaptive_stage_launch(dpm_adaptive* a, int which, const dpm_stage* st, const dpm_buffers* b, void* stream) {
@@ -723,29 +698,20 @@ extern "C" int dpm_adaptive_error(dpm_adaptive* a, const void* x_lower, const vo
     a->scratch_batch = batch;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-#define DPM_ERRK(T)                                                                                                     \
-  do {                                                                                                                  \
-    const size_t al = sizeof(T) * EPT;                                                                                  \
-    const bool v = per_sample % EPT == 0 && aligned(x_lower, al) && aligned(x_higher, al) && aligned(x_prev, al);       \
-    if (v)                                                                                                              \
-      hipLaunchKernelGGL((adaptive_error_kernel2<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x_lower, \
-                         (const T*)x_higher, (const T*)x_prev, (float)a->d.atol, (float)a->d.rtol, per_sample, (int)G,   \
-                         a->partial, a->counters, e_dev, &a->dev->done);                                                \
-    else                                                                                                                \
-      hipLaunchKernelGGL((adaptive_error_kernel2<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x_lower, \
-                         (const T*)x_higher, (const T*)x_prev, (float)a->d.atol, (float)a->d.rtol, per_sample, (int)G,   \
-                         a->partial, a->counters, e_dev, &a->dev->done);                                                \
-  } while (0)
-  switch (dtype) {
-    case DPM_DTYPE_F32: DPM_ERRK(float); break;
-    case DPM_DTYPE_F16: DPM_ERRK(__half); break;
-    case DPM_DTYPE_BF16: DPM_ERRK(bf16_t); break;
-    default: return dpm_set_error(DPM_ERR_UNSUPPORTED, "adaptive_error: unsupported dtype %d", dtype);
-  }
-#undef DPM_ERRK
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "adaptive_error: %s", hipGetErrorString(e));
-  return DPM_OK;
+  const int rc = with_elem_type(dtype, "adaptive_error", [&](auto t) {
+    using T = decltype(t);
+    const size_t al = sizeof(T) * EPT;
+    const bool v = per_sample % EPT == 0 && aligned(x_lower, al) && aligned(x_higher, al) && aligned(x_prev, al);
+    if (v)
+      hipLaunchKernelGGL((adaptive_error_kernel2<T, true>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x_lower,
+                         (const T*)x_higher, (const T*)x_prev, (float)a->d.atol, (float)a->d.rtol, per_sample, (int)G,
+                         a->partial, a->counters, e_dev, &a->dev->done);
+    else
+      hipLaunchKernelGGL((adaptive_error_kernel2<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, (const T*)x_lower,
+                         (const T*)x_higher, (const T*)x_prev, (float)a->d.atol, (float)a->d.rtol, per_sample, (int)G,
+                         a->partial, a->counters, e_dev, &a->dev->done);
+  });
+  return rc ? rc : launch_status("adaptive_error");
 }
 
 extern "C" int dpm_adaptive_done_at(const dpm_adaptive* a, int begin_index) {

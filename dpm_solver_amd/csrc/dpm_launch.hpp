@@ -727,19 +727,15 @@ int launch_guide(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& s) 
   return dpm_set_error(DPM_ERR_ARG, "unknown guidance %d", st->guidance);
 }
 
-// The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
-// slowest unit).  FORMS = the update forms this unit instantiates (bit f = form f); a stage of another form returns
-// FORM_ELSEWHERE and the caller (dpm_stage_<pair>.hip) passes it on to the sibling unit.
-constexpr int FORM_ELSEWHERE = -1001;
-constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);  // + the fused multi-request launchers
-constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE);
+// the single-request launchers of the update forms one translation unit instantiates (FORMS, dpm_internal.hpp: bit f =
+// form f); a form outside them is an error here (dpm_kernels.hip hands every stage to the unit of its form)
 template <typename TS, typename TE, unsigned FORMS>
 int launch_form(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& s) {
   switch (st->form) {
-#define DPM_FORM_CASE(F)                                            \
-  case F:                                                           \
+#define DPM_FORM_CASE(F)                                                       \
+  case F:                                                                      \
     if constexpr ((FORMS >> F) & 1u) return launch_guide<TS, TE, F>(st, b, s); \
-    return FORM_ELSEWHERE;
+    break;
     DPM_FORM_CASE(DPM_FORM_LIN1)
     DPM_FORM_CASE(DPM_FORM_TWO)
     DPM_FORM_CASE(DPM_FORM_MS3)

@@ -1,0 +1,46 @@
+// dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
+// translation unit: compiled ten times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1> (__graft_entry__.py).
+//   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
+//   unit B (1): the LIN1, MS3 and DENOISE forms (FORMS_B)
+#if !defined(DPM_PAIR) || !defined(DPM_UNIT)
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1>"
+#endif
+#if DPM_UNIT == 0
+#define DPM_CATCHALL_HOME
+#endif
+#include "dpm_device.hpp"
+
+#include <tuple>
+#include <utility>
+
+#define DPM_PAIR_TYPES(name, TS, TE, SD, ED) std::pair<TS, TE>,
+using Pair = std::tuple_element_t<DPM_PAIR, std::tuple<DPM_PAIRS(DPM_PAIR_TYPES) void>>;
+#undef DPM_PAIR_TYPES
+using State = Pair::first_type;  // the pair's state dtype
+using Eps = Pair::second_type;   // ... and network-output dtype
+
+#if DPM_UNIT == 0
+template const void* dpm_catchall_thresh<State, Eps>();
+template const void* dpm_catchall_scalar<State, Eps, false>();
+template const void* dpm_catchall_scalar<State, Eps, true>();
+#endif
+
+template <typename TS, typename TE, unsigned FORMS>
+int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
+                    const dpm_stage* dyn, const int32_t* skip, const dpm_buffers* multi, int n_multi) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop),
+                    dyn, skip, multi, n_multi};
+  return launch_form<TS, TE, FORMS>(st, b, s);
+}
+template int dpm_launch_unit<State, Eps, DPM_UNIT == 0 ? FORMS_A : FORMS_B>(const dpm_stage*, const dpm_buffers*, void*,
+                                                                             void*, void*, const dpm_stage*, const int32_t*,
+                                                                             const dpm_buffers*, int);
+
+#if DPM_UNIT == 0
+template <typename TS, typename TE>
+int dpm_launch_fused(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void* ev_start, void* ev_stop) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
+  return launch_multi_typed<TS, TE>(st, bs, n_req, s);
+}
+template int dpm_launch_fused<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+#endif

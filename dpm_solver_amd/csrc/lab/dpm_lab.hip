@@ -16,11 +16,6 @@ Tuning g_lab_tuning;
 }
 using dpmk::g_lab_tuning;
 
-// launch hooks of the product sources (dpm_kernels.hip)
-int dpm_stage_launch_ev(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
-int dpm_timing_begin(int n, void*** starts, void*** stops);
-int dpm_timing_end(int n, void** starts, void** stops, void* stream, float* ms, const unsigned char* recorded);
-
 extern "C" int dpm_lab_build(void) { return 1; }
 extern "C" const void* dpm_lab_device_context(int dev) { return &device_context(dev); }
 

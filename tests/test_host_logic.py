@@ -889,3 +889,24 @@ def test_adaptive_host_loop_raises_on_a_nan_estimate_instead_of_spinning():
     dpm.adaptive_on_device = False
     with pytest.raises(FloatingPointError, match="error estimate is NaN"):
         dpm.sample(x, method="adaptive", order=2)
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="hands the library null buffers: CPU hosts only, never a shared GPU")
+def test_stage_launch_multi_checks_every_request_like_a_single_launch():
+    """dpm_stage_launch_multi fuses a group only when every request passes the single launch's argument checks; a request
+    that fails them is launched on its own and reports the single launch's error (it never reaches a kernel)."""
+    fake = iter(range(0x100000, 0x10000000, 0x100000))  # distinct, aligned addresses: nothing here dereferences them
+
+    def request(**null):
+        b = L.Buffers()
+        for f in ("x", "xe", "e0", "h1", "h2", "x_out", "workspace"):
+            setattr(b, f, None if f in null else next(fake))
+        b.n, b.batch, b.state_dtype, b.eps_dtype = 4096, 1, L.DTYPE_F32, L.DTYPE_F32
+        return b
+
+    thr = L.Stage(form=L.FORM_SS3T, flags=L.F_TO_X0 | L.F_THRESH, thr_ratio=0.995, thr_max=1.0, alpha_e=0.5, sigma_e=0.8)
+    lin1 = L.Stage(form=L.FORM_LIN1, flags=L.F_TO_X0, alpha_e=0.5, sigma_e=0.8)
+    for st, null, msg in ((thr, ("h1",), "form %d needs h1" % L.FORM_SS3T), (lin1, ("x",), "x is null")):
+        bs = (L.Buffers * 2)(request(**dict.fromkeys(null)), request(**dict.fromkeys(null)))
+        assert L.lib.dpm_stage_launch_multi(C_.byref(st), bs, 2, None) == L.ERR_ARG
+        assert msg in L.lib.dpm_last_error().decode()
