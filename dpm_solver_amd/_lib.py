@@ -207,6 +207,12 @@ class FloorDesc(C.Structure):
                 ("nt", C.c_int32), ("prio", C.c_int32), ("store", C.c_int32), ("reserved", C.c_int32)]
 
 
+class FloorMultiDesc(C.Structure):
+    """dpm_floor_multi_desc (include/dpm_lab.h)"""
+    _fields_ = [("load_path", C.c_int32), ("nt", C.c_int32), ("pipe", C.c_int32), ("blocks_per_cu", C.c_int32),
+                ("interleave", C.c_int32), ("reserved", C.c_int32)]
+
+
 # what include/dpm_lab.h declares: exported by the LAB build only (bound when the loaded library is one)
 _LAB_SIGNATURES = [
     ("dpm_lab_build", C.c_int, []),
@@ -229,6 +235,8 @@ _LAB_SIGNATURES = [
                                    C.c_void_p, _P(C.c_float)]),
     ("dpm_floor_launch_traced", C.c_int, [_P(FloorDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_void_p, C.c_void_p, C.c_int]),
+    ("dpm_floor_multi_launch", C.c_int, [_P(FloorMultiDesc), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p),
+                                         _P(C.c_void_p), C.c_int, C.c_int64, C.c_void_p, _P(C.c_float)]),
     ("dpm_pagetouch_launch", C.c_int, [_P(C.c_void_p), _P(C.c_int64), C.c_int, C.c_int64, C.c_void_p]),
 ]
 LAB_SYMBOLS = [s[0] for s in _LAB_SIGNATURES]

@@ -128,7 +128,7 @@ __device__ __forceinline__ void load_pack(const bf16_t* __restrict__ p, int64_t 
   unpack8(ld16<NT>(reinterpret_cast<const u32x4*>(p) + group), p, out);
 }
 
-template <bool NT>
+template <bool NT, bool WT = true>  // (WT: see st16; these stores are never written through)
 __device__ __forceinline__ void store_pack(float* __restrict__ p, int64_t group, const float (&in)[EPT]) {
   u32x4 a, b;
 #pragma unroll
@@ -157,20 +157,20 @@ __device__ __forceinline__ uint32_t pack_bf162(float lo, float hi) {
   const b2 v = __builtin_convertvector(f2{lo, hi}, b2);
   return __builtin_bit_cast(uint32_t, v);
 }
-template <bool NT>
+template <bool NT, bool WT = true>
 __device__ __forceinline__ void store_pack(__half* __restrict__ p, int64_t group, const float (&in)[EPT]) {
   u32x4 a;
 #pragma unroll
   for (int j = 0; j < 4; ++j) a[j] = pack_half2(in[2 * j], in[2 * j + 1]);
-  st16<NT>(reinterpret_cast<u32x4*>(p) + group, a);
+  st16<NT, WT>(reinterpret_cast<u32x4*>(p) + group, a);
 }
-template <bool NT>
+template <bool NT, bool WT = true>
 __device__ __forceinline__ void store_pack(bf16_t* __restrict__ p, int64_t group, const float (&in)[EPT]) {
   u32x4 a;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     a[j] = pack_bf162(in[2 * j], in[2 * j + 1]);
-  st16<NT>(reinterpret_cast<u32x4*>(p) + group, a);
+  st16<NT, WT>(reinterpret_cast<u32x4*>(p) + group, a);
 }
 
 // A tile belongs to 256 consecutive lanes.  The streaming kernel may be launched with 256 or 512 threads: every
@@ -235,7 +235,8 @@ __device__ __forceinline__ void load_tile(const T* __restrict__ p, int64_t gi, b
   }
   load_pack<NT>(p, gi, out);
 }
-template <bool NT, typename T>
+// WT = false: a non-temporal (NT) or plain store even in the write-through build (st16)
+template <bool NT, bool WT = true, typename T>
 __device__ __forceinline__ void store_tile(T* __restrict__ p, int64_t gi, bool split, const float (&in)[EPT]) {
   if constexpr (sizeof(T) == 4) {
     if (split) {
@@ -246,12 +247,12 @@ __device__ __forceinline__ void store_tile(T* __restrict__ p, int64_t gi, bool s
         b[j] = __float_as_uint(in[4 + j]);
       }
       u32x4* q = reinterpret_cast<u32x4*>(p) + (2 * gi - (int64_t)tile_lane());
-      st16<NT>(q, a);
-      st16<NT>(q + 256, b);
+      st16<NT, WT>(q, a);
+      st16<NT, WT>(q + 256, b);
       return;
     }
   }
-  store_pack<NT>(p, gi, in);
+  store_pack<NT, WT>(p, gi, in);
 }
 
 }  // namespace

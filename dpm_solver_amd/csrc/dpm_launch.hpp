@@ -606,10 +606,14 @@ int launch_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& str
 // written) -> streaming loads; one super-tile per workgroup -- a grid of all R x tiles workgroups, no grid-stride loop:
 // fp16 7.95 us with the grid capped at 8 workgroups per CU, 7.7 / 7.5 at 16 / 32 per CU, 6.93 uncapped (0.757 of the
 // HBM peak; fp32 15.4 -> 13.9, fp32 state + fp16 output 13.3 -> 12.6); two tiles per workgroup for 4-byte states.
+// Store policy of 2-byte states (profiles/r07_fused_floor.md, rocprofv3 rows, 32 x [256,4,64,64] fp16 back to back): the
+// new state written through and the model value by a non-temporal store (nt mask bit 3) -- the no-arithmetic floor of
+// the five streams 211.5 -> 189.9 us, both stores written through or both nt 211.5 / 212.7; LDS-DMA reads, two tiles of
+// loads in flight and resident grids were no faster.  4-byte states keep both stores written through (not measured).
 template <typename TS, typename TE>
 struct MultiShape {
   static constexpr int U = (sizeof(TS) == 4) ? 2 : 1;
-  static constexpr int NT = 1;
+  static constexpr int NT = (sizeof(TS) == 2) ? 1 | 8 : 1;
   static constexpr int THREADS = 256;  // per workgroup (256 / 512: stage_kernel_multi)
 };
 
@@ -653,10 +657,11 @@ int launch_multi_spec(const dpm_stage* st, const dpm_buffers* bs, int n_req, con
 #ifdef DPM_TUNING_VARIANTS  // tools/tune.py multi: every (tiles per iteration, nt mask) of the 2M kernel
   if constexpr (FORM == DPM_FORM_TWO && GUIDE == DPM_GUIDE_NONE && SPEC == SPEC_NOISE_X0) {
     if (tn.unroll > 0 && tn.nontemporal >= 0) {
-      switch (tn.unroll * 8 + (tn.nontemporal & 7)) {
+      switch (tn.unroll * 8 + (tn.nontemporal & 7) + ((tn.nontemporal & 8) ? 64 : 0)) {  // nt mask 9: MultiShape's
         case 8 + 0: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 1, 0>, 1); break;
         case 8 + 1: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 1, 1>, 1); break;
         case 8 + 5: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 1, 5>, 1); break;
+        case 64 + 8 + 1: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 1, 9>, 1); break;
         case 16 + 0: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 2, 0>, 2); break;
         case 16 + 1: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 2, 1>, 2); break;
         case 16 + 5: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 2, 5>, 2); break;

@@ -446,7 +446,8 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
     if (gi < ngroups) {
       store_tile<(NT & 2) != 0>(xo, gi, split, ox);
       if (EXT && xo2) store_tile<(NT & 2) != 0>(xo2, gi, split, ox);
-      if (store_m) store_tile<(NT & 4) != 0>(mo, gi, split, om);
+      // NT bit 3: the model value leaves by a non-temporal store, not written through (the fused launch, MultiShape)
+      if (store_m) store_tile<(NT & 12) != 0, (NT & 8) == 0>(mo, gi, split, om);
     }
   }
 }

@@ -213,7 +213,7 @@ extern "C" int dpm_tuning_set(int knob, int value) {
         return dpm_set_error(DPM_ERR_ARG, "unroll must be 0 (default), 1, 2, 4 or 8 (4 and 8: tuning builds only)");
       g_lab_tuning.unroll = value;
       return DPM_OK;
-    case DPM_TUNE_NONTEMPORAL: g_lab_tuning.nontemporal = value < 0 ? -1 : (value & 7); return DPM_OK;
+    case DPM_TUNE_NONTEMPORAL: g_lab_tuning.nontemporal = value < 0 ? -1 : (value & 15); return DPM_OK;
     case DPM_TUNE_BLOCKS_PER_CU:
       if (value < 1 || value > 64) return dpm_set_error(DPM_ERR_ARG, "blocks_per_cu must be in 1..64");
       g_lab_tuning.blocks_per_cu = value;
@@ -438,6 +438,221 @@ extern "C" int dpm_floor_launch_traced(const dpm_floor_desc* f, const void* a, c
   if (!t || slot < 0 || slot >= t->cap) return dpm_set_error(DPM_ERR_ARG, "floor_launch_traced: slot %d outside the trace", slot);
   const int rc = floor_launch_ev(f, a, b, c, d, e, nbytes, stream, t->starts[slot], t->stops[slot]);
   if (!rc) t->used[(size_t)slot] = 1;
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The floor of the FUSED 2M launch (include/dpm_lab.h: dpm_floor_multi_launch): the same five streams per request, through a
+// pointer table over up to DPM_MULTI_MAX requests, in the fused kernel's tiles (256 lanes x 16 B = 4 KiB per stream) and
+// request-major tile order, every XCD owning one contiguous eighth of the tile space (workgroup b runs on XCD b % 8, as
+// stage_kernel_multi's xcd_span mapping assumes).  256-thread workgroups throughout (the fused kernel's shape).
+// ------------------------------------------------------------------------------------------------
+namespace {
+struct FloorMultiTab {
+  const u32x4* a[DPM_MULTI_MAX];
+  const u32x4* b[DPM_MULTI_MAX];
+  const u32x4* c[DPM_MULTI_MAX];
+  u32x4* d[DPM_MULTI_MAX];
+  u32x4* e[DPM_MULTI_MAX];
+};
+template <bool NT>
+__device__ __forceinline__ void fm_store(u32x4* p, u32x4 v) {
+  if (NT)
+    __builtin_nontemporal_store(v, p);
+  else
+    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
+}
+// ds_read_b128 the compiler does not see: it would otherwise order the read behind every LDS-DMA still in flight (vmcnt(0)),
+// the next tile's included, and the two-tile pipeline would collapse to one tile in flight.  The wait is in the string.
+__device__ __forceinline__ u32x4 fm_ds_read(const u32x4* lds) {
+  u32x4 v;
+  const uint32_t a = (uint32_t)(uintptr_t)lds;
+  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
+  return v;
+}
+// vmcnt immediates the two-tile DMA pipeline waits with: the current tile's 3 LDS-DMA loads are older than the previous
+// tile's 2 stores (if any) and the next tile's 3 loads (if any)
+template <int N>
+__device__ __forceinline__ void fm_vmcnt() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// PATH 0: registers, 1: LDS-DMA into this wavefront's own rows.  PIPE 1: load, wait, store, next tile; PIPE 2: the next tile's
+// loads are issued before the current tile's stores.  STM bit 0 / 1: nt store of d / e (else write-through, the product's).
+// A 256-lane workgroup g takes `chunk` tiles of its XCD's eighth: j = g >> 3, tiles j * chunk .. (contiguous) or j, j + gpx, ..
+// (interleaved: at any time the XCD's workgroups stream neighbouring tiles).
+template <int PATH, bool NTL, int STM, int PIPE>
+__global__ __launch_bounds__(256) void floor_multi_kernel(const FloorMultiTab tab, uint32_t tpr, uint32_t total, uint32_t span,
+                                                          uint32_t chunk, uint32_t gpx, uint32_t ilv) {
+  extern __shared__ __align__(16) unsigned char fm_lds[];
+  const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+  const uint32_t lo = xcd * span, hi = min(lo + span, total);
+  const uint32_t lane256 = threadIdx.x, lane = threadIdx.x & 63u;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  u32x4* rows = reinterpret_cast<u32x4*>(fm_lds) + (size_t)wave * 3 * PIPE * 64;
+  // the i-th tile of this workgroup, or `total` when there is none
+  auto tile = [&](uint32_t i) -> uint32_t {
+    if (i >= chunk) return total;
+    const uint32_t v = lo + (ilv ? j + i * gpx : j * chunk + i);
+    return v < hi ? v : total;
+  };
+  auto at = [&](uint32_t v, uint32_t& r, uint32_t& off) {
+    r = v / tpr;
+    off = (v - r * tpr) * 256u + lane256;
+  };
+  if constexpr (PATH == 0) {
+    uint32_t v = tile(0);
+    if (v >= total) return;
+    uint32_t r, off;
+    at(v, r, off);
+    u32x4 va = ld16<NTL>(tab.a[r] + off), vb = ld16<NTL>(tab.b[r] + off), vc = ld16<NTL>(tab.c[r] + off);
+    for (uint32_t i = 0;; ++i) {
+      const uint32_t vn = tile(i + 1);
+      uint32_t rn = 0, offn = 0;
+      u32x4 na = {}, nb = {}, nc = {};
+      if (PIPE == 2 && vn < total) {
+        at(vn, rn, offn);
+        na = ld16<NTL>(tab.a[rn] + offn);
+        nb = ld16<NTL>(tab.b[rn] + offn);
+        nc = ld16<NTL>(tab.c[rn] + offn);
+      }
+      fm_store<(STM & 1) != 0>(tab.d[r] + off, va ^ vb);
+      fm_store<(STM & 2) != 0>(tab.e[r] + off, vb ^ vc);
+      if (vn >= total) break;
+      if (PIPE == 2) {
+        r = rn;
+        off = offn;
+        va = na;
+        vb = nb;
+        vc = nc;
+      } else {
+        at(vn, r, off);
+        va = ld16<NTL>(tab.a[r] + off);
+        vb = ld16<NTL>(tab.b[r] + off);
+        vc = ld16<NTL>(tab.c[r] + off);
+      }
+    }
+  } else {
+    uint32_t v = tile(0);
+    if (v >= total) return;
+    uint32_t r, off;
+    at(v, r, off);
+    glds16<NTL>(tab.a[r] + off, rows);
+    glds16<NTL>(tab.b[r] + off, rows + 64);
+    glds16<NTL>(tab.c[r] + off, rows + 128);
+    for (uint32_t i = 0;; ++i) {
+      u32x4* cur = rows + (PIPE == 2 ? (i & 1u) * 192 : 0);
+      const uint32_t vn = tile(i + 1);
+      uint32_t rn = 0, offn = 0;
+      if (PIPE == 2 && vn < total) {
+        u32x4* nxt = rows + ((i + 1) & 1u) * 192;
+        at(vn, rn, offn);
+        glds16<NTL>(tab.a[rn] + offn, nxt);
+        glds16<NTL>(tab.b[rn] + offn, nxt + 64);
+        glds16<NTL>(tab.c[rn] + offn, nxt + 128);
+      }
+      if (PIPE == 1) {
+        fm_vmcnt<0>();
+      } else {  // wave-uniform: (previous tile's stores pending, next tile's loads pending)
+        const bool prev = i > 0, next = vn < total;
+        if (prev && next) fm_vmcnt<5>();
+        else if (next) fm_vmcnt<3>();
+        else if (prev) fm_vmcnt<2>();
+        else fm_vmcnt<0>();
+      }
+      const u32x4 va = fm_ds_read(cur + lane), vb = fm_ds_read(cur + 64 + lane), vc = fm_ds_read(cur + 128 + lane);
+      fm_store<(STM & 1) != 0>(tab.d[r] + off, va ^ vb);
+      fm_store<(STM & 2) != 0>(tab.e[r] + off, vb ^ vc);
+      if (vn >= total) break;
+      if (PIPE == 2) {
+        r = rn;
+        off = offn;
+      } else {  // the rows are free: their ds_reads completed before the stores that consumed them were issued
+        at(vn, r, off);
+        glds16<NTL>(tab.a[r] + off, rows);
+        glds16<NTL>(tab.b[r] + off, rows + 64);
+        glds16<NTL>(tab.c[r] + off, rows + 128);
+      }
+    }
+  }
+}
+
+template <int PATH, bool NTL, int STM>
+void floor_multi_pipe(int pipe, dim3 grid, const LaunchCtx& c, const FloorMultiTab& t, uint32_t tpr, uint32_t total, uint32_t span,
+                      uint32_t chunk, uint32_t gpx, uint32_t ilv) {
+  const size_t lds = PATH == 1 ? (size_t)4 * 3 * pipe * 1024 : 0;
+  if (pipe == 2) launch(floor_multi_kernel<PATH, NTL, STM, 2>, grid, dim3(256), lds, c, t, tpr, total, span, chunk, gpx, ilv);
+  else launch(floor_multi_kernel<PATH, NTL, STM, 1>, grid, dim3(256), lds, c, t, tpr, total, span, chunk, gpx, ilv);
+}
+template <int PATH, bool NTL>
+void floor_multi_st(int stm, int pipe, dim3 grid, const LaunchCtx& c, const FloorMultiTab& t, uint32_t tpr, uint32_t total,
+                    uint32_t span, uint32_t chunk, uint32_t gpx, uint32_t ilv) {
+  switch (stm) {
+    case 1: floor_multi_pipe<PATH, NTL, 1>(pipe, grid, c, t, tpr, total, span, chunk, gpx, ilv); break;
+    case 2: floor_multi_pipe<PATH, NTL, 2>(pipe, grid, c, t, tpr, total, span, chunk, gpx, ilv); break;
+    case 3: floor_multi_pipe<PATH, NTL, 3>(pipe, grid, c, t, tpr, total, span, chunk, gpx, ilv); break;
+    default: floor_multi_pipe<PATH, NTL, 0>(pipe, grid, c, t, tpr, total, span, chunk, gpx, ilv); break;
+  }
+}
+}  // namespace
+
+extern "C" int dpm_floor_multi_launch(const dpm_floor_multi_desc* f, const void* const* a, const void* const* b,
+                                      const void* const* c, void* const* d, void* const* e, int n_req, int64_t nbytes,
+                                      void* stream, float* ms) {
+  if (!f || !a || !b || !c || !d || !e || n_req < 1 || n_req > DPM_MULTI_MAX || nbytes < 4096 || nbytes % 4096)
+    return dpm_set_error(DPM_ERR_ARG, "floor_multi: bad arguments (1..%d requests, nbytes a multiple of 4096)", DPM_MULTI_MAX);
+  if (f->load_path < 0 || f->load_path > 1 || f->pipe < 1 || f->pipe > 2 || f->blocks_per_cu < 0 || f->blocks_per_cu > 64 ||
+      f->interleave < 0 || f->interleave > 1 || f->nt < 0 || f->nt > 7)
+    return dpm_set_error(DPM_ERR_ARG, "floor_multi: load_path 0..1, pipe 1..2, blocks_per_cu 0..64, interleave 0..1, nt 0..7");
+  const int64_t tpr64 = nbytes / 4096, total64 = tpr64 * n_req;
+  if (total64 > (int64_t)0x7fffffff) return dpm_set_error(DPM_ERR_ARG, "floor_multi: too many tiles");
+  FloorMultiTab tab;
+  std::memset(&tab, 0, sizeof tab);
+  for (int r = 0; r < n_req; ++r) {
+    for (const void* p : {a[r], b[r], c[r], (const void*)d[r], (const void*)e[r]})
+      if (!p || !aligned(p, 16)) return dpm_set_error(DPM_ERR_ALIGN, "floor_multi: buffers of request %d: null or not 16-byte aligned", r);
+    tab.a[r] = static_cast<const u32x4*>(a[r]);
+    tab.b[r] = static_cast<const u32x4*>(b[r]);
+    tab.c[r] = static_cast<const u32x4*>(c[r]);
+    tab.d[r] = static_cast<u32x4*>(d[r]);
+    tab.e[r] = static_cast<u32x4*>(e[r]);
+  }
+  const uint32_t total = (uint32_t)total64, span = (uint32_t)((total64 + 7) / 8);
+  uint32_t chunk, gpx;
+  if (f->blocks_per_cu == 0) {  // one-shot workgroups: `pipe` tiles each, a grid of all of them
+    chunk = (uint32_t)f->pipe;
+    gpx = (span + chunk - 1) / chunk;
+  } else {                      // resident grid: blocks_per_cu x CUs workgroups share the tiles
+    const DeviceInfo& di = device_info();
+    const int64_t n_cu = di.n_cu > 0 ? di.n_cu : 256;
+    gpx = (uint32_t)std::max<int64_t>(1, n_cu * f->blocks_per_cu / 8);
+    if (gpx > span) gpx = span;
+    chunk = (span + gpx - 1) / gpx;
+  }
+  void **starts = nullptr, **stops = nullptr;
+  if (ms) {
+    int rc = dpm_timing_begin(1, &starts, &stops);
+    if (rc) return rc;
+  }
+  const LaunchCtx ctx{static_cast<hipStream_t>(stream), ms ? static_cast<hipEvent_t>(starts[0]) : nullptr,
+                      ms ? static_cast<hipEvent_t>(stops[0]) : nullptr};
+  const dim3 grid(8u * gpx);
+  const int stm = (f->nt >> 1) & 3;
+  const uint32_t tpr = (uint32_t)tpr64, ilv = (uint32_t)f->interleave;
+  if (f->load_path == 1) {
+    if (f->nt & 1) floor_multi_st<1, true>(stm, f->pipe, grid, ctx, tab, tpr, total, span, chunk, gpx, ilv);
+    else floor_multi_st<1, false>(stm, f->pipe, grid, ctx, tab, tpr, total, span, chunk, gpx, ilv);
+  } else {
+    if (f->nt & 1) floor_multi_st<0, true>(stm, f->pipe, grid, ctx, tab, tpr, total, span, chunk, gpx, ilv);
+    else floor_multi_st<0, false>(stm, f->pipe, grid, ctx, tab, tpr, total, span, chunk, gpx, ilv);
+  }
+  int rc = DPM_OK;
+  hipError_t he = hipGetLastError();
+  if (he != hipSuccess) rc = dpm_set_error((int)he, "floor_multi launch failed: %s", hipGetErrorString(he));
+  if (ms) {
+    int rc2 = dpm_timing_end(1, starts, stops, stream, rc ? nullptr : ms, nullptr);
+    if (!rc) rc = rc2;
+  }
   return rc;
 }
 

@@ -96,6 +96,22 @@ DPM_API int dpm_floor_launch(const dpm_floor_desc* f, const void* a, const void*
 DPM_API int dpm_floor_launch_traced(const dpm_floor_desc* f, const void* a, const void* b, const void* c, void* d, void* e,
                             int64_t nbytes, void* stream, dpm_trace* t, int slot);
 
+/* The FLOOR of the fused multi-request 2M launch (stage_kernel_multi's shape): for each of n_req requests (<= DPM_MULTI_MAX)
+   three read and two write streams of nbytes each (a multiple of 4096), d[r] = a[r] ^ b[r], e[r] = b[r] ^ c[r], in 4 KiB tiles
+   per stream (256 lanes x 16 B), request-major, every XCD one contiguous eighth of the tiles; 256-thread workgroups.
+     load_path      0: global_load_dwordx4 into registers, 1: LDS-DMA into the wavefront's own rows
+     nt             bit 0: nt loads; bit 1 / 2: nt store of d / e (else write-through sc0 sc1, the product's store)
+     pipe           tiles of loads in flight per wavefront: 1 (load, wait, store) or 2 (next tile's loads before the stores)
+     blocks_per_cu  0: one-shot workgroups of `pipe` tiles each (the product's shape at pipe 1); else a resident grid of
+                    blocks_per_cu x CUs workgroups sharing the tiles
+     interleave     resident grid: 0 = each workgroup a contiguous run of its XCD's tiles, 1 = strided by the XCD's workgroups
+   ms (optional) = kernel time by events. */
+typedef struct dpm_floor_multi_desc {
+  int32_t load_path, nt, pipe, blocks_per_cu, interleave, reserved;
+} dpm_floor_multi_desc;
+DPM_API int dpm_floor_multi_launch(const dpm_floor_multi_desc* f, const void* const* a, const void* const* b, const void* const* c,
+                           void* const* d, void* const* e, int n_req, int64_t nbytes, void* stream, float* ms);
+
 /* ---- side-stream helpers measured against the lone launch's ramp-up (neither is used by any loop of the library) ----
    dpm_prefetch_launch: read `n_buf` device buffers (bytes[i] each, 16-byte aligned) and discard the data (policy 0:
    default loads, 1: streaming loads): rejected in round 3 (profiles/r03_in_loop.md).
