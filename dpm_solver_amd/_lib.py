@@ -74,7 +74,7 @@ class StageF64(C.Structure):
 class LaunchOpts(C.Structure):
     """dpm_launch_opts: what a caller may choose per call (zero = defaults)"""
     _fields_ = [("cluster_in_graph", C.c_int32), ("no_fuse", C.c_int32), ("thr_spin_limit", C.c_int32),
-                ("reserved", C.c_int32 * 5)]
+                ("per_request_stages", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class Buffers(C.Structure):
@@ -268,8 +268,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 201:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 201 -- stale library, rebuild"
+if lib.dpm_version() < 202:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 202 -- stale library, rebuild"
                       % lib.dpm_version())
 
 

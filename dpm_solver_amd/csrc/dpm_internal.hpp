@@ -18,7 +18,7 @@
 
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
-// pair's catch-all kernels.
+// pair's catch-all kernels, unit B the heterogeneous fused launcher.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE);
 
@@ -30,6 +30,9 @@ int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, voi
 // one stage of n_req requests in one launch of the streaming family; MULTI_NOT_BUILT when it has no fused variant
 template <typename TS, typename TE>
 int dpm_launch_fused(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void* ev_start, void* ev_stop);
+// (unit B) one heterogeneous fused launch: request r advanced by st[r]; the requests are grouped by the caller
+template <typename TS, typename TE>
+int dpm_launch_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

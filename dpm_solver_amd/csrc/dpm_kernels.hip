@@ -28,17 +28,20 @@ uint32_t* cluster_fault_word(int dev, bool create) {
 
 namespace {
 // The stage launchers of one dtype pair (dpm_stage_unit.hip, dpm_internal.hpp): unit A's and unit B's single-request
-// launchers and unit A's fused multi-request one.  One row per entry of DPM_PAIRS.
+// launchers, unit A's fused multi-request one and unit B's heterogeneous one.  One row per entry of DPM_PAIRS.
 using UnitFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*,
                        const dpm_buffers*, int);
 using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
   FusedFn fused;
+  HetFn het;  // unit B's heterogeneous fused launcher (per-request stage records)
 };
-#define DPM_PAIR_ROW(name, TS, TE, SD, ED) \
-  {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>},
+#define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
+  {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
+   dpm_launch_het<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -187,7 +190,66 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
   return DPM_OK;
 }
 
+namespace {
+// May request r join a heterogeneous fused launch (stage_kernel_het)?  The stage- and buffer-level conditions of
+// launch_multi_typed, per request: a streaming stage of a fused form, no thresholding / blend / classifier guidance, the
+// evaluation state is the state, dense 16-byte-aligned buffers, a duplicate store only under classifier-free guidance.
+bool het_fusable(const dpm_stage& st, const dpm_buffers& b) {
+  const PairUnits* p = pair_of(b.state_dtype, b.eps_dtype);
+  if (!p || b.n <= 0 || b.n % EPT != 0) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND)) return false;
+  if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3) return false;
+  if (b.eps_stride && b.eps_stride != b.n / b.batch) return false;
+  if (!b.x || (b.xe && b.xe != b.x)) return false;
+  const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
+  if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
+  return aligned(b.x, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) && aligned(b.m_out, as) &&
+         aligned(b.e0, ae) && aligned(b.e1, ae);
+}
+// ... together with request 0 of its group: the fields that are template arguments or kernel-wide scalars
+bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b) {
+  return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && b.n == b0.n && b.batch == b0.batch &&
+         s.model_type == s0.model_type && s.guidance == s0.guidance && (s.flags & DPM_F_TO_X0) == (s0.flags & DPM_F_TO_X0);
+}
+
+// dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
+// HET_MAX (first come, first grouped), launch the rest one by one
+int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
+  for (int r = 0; r < n_req; ++r)
+    if (const int rc = check_stage_buffers(&st[r], &bs[r])) return rc;
+  const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
+  std::vector<char> done((size_t)n_req, 0);
+  dpm_stage gs[HET_MAX];
+  dpm_buffers gb[HET_MAX];
+  int gi[HET_MAX];
+  for (int r0 = 0; r0 < n_req; ++r0) {
+    if (done[r0]) continue;
+    int cnt = 0;
+    if (fuse && het_fusable(st[r0], bs[r0])) {
+      for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
+        if (!done[r] && het_fusable(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+          gs[cnt] = st[r];
+          gb[cnt] = bs[r];
+          gi[cnt++] = r;
+        }
+    }
+    if (cnt > 1) {
+      const int rc = pair_of(bs[r0].state_dtype, bs[r0].eps_dtype)->het(gs, gb, cnt, stream);
+      if (rc) return rc;
+      for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
+    } else {
+      if (const int rc = dpm_stage_launch_ev(&st[r0], &bs[r0], stream, nullptr, nullptr)) return rc;
+      done[r0] = 1;
+    }
+  }
+  return DPM_OK;
+}
+}  // namespace
+
 extern "C" int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
+  if (st && bs && n_req >= 1 && bs[0].opts && bs[0].opts->per_request_stages == 1)
+    return stage_launch_multi_het(st, bs, n_req, stream);
   return dpm_stage_launch_multi_ev(st, bs, n_req, stream, nullptr, nullptr, nullptr);
 }
 

@@ -716,6 +716,64 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
 #undef DPM_MULTI
 }
 
+// ---- heterogeneous fused launch (stage_kernel_het): request r advanced by st[r].  The caller (dpm_kernels.hip) has
+// grouped the requests: every one passes het_fusable, and they agree on dtypes, n, batch, model type, guidance kind and
+// DPM_F_TO_X0.  Here: the prologue (compile-time only when every request's alpha passes the division guard), the
+// smallest form set that covers the group, the launch shape of the lockstep kernel (MultiShape, XCD-contiguous remap).
+template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC>
+void launch_het_spec(HetArgs& a, const Tuning& tn, const LaunchCtx& c) {
+  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT;
+  const int64_t ntiles = ((a.n / EPT) + 255) / 256;
+  const int64_t spr = (ntiles + U - 1) / U;
+  const int64_t groups = spr * a.nreq;  // 256-lane groups of work: one super-tile each, no grid-stride loop
+  const int bt = tn.block_threads > 0 ? tn.block_threads : MultiShape<TS, TE>::THREADS;
+  const int64_t per = bt / 256;
+  const bool remap = tn.multi_xcd_remap < 0 ? sizeof(TS) == 2 : tn.multi_xcd_remap != 0;
+  a.spr = (uint32_t)spr;
+  a.xcd_span = remap ? (uint32_t)((groups + 7) / 8) : 0u;
+  const int64_t blocks = a.xcd_span ? 8 * (((int64_t)a.xcd_span + per - 1) / per) : (groups + per - 1) / per;
+  launch(stage_kernel_het<TS, TE, FORMS, GUIDE, SPEC, U, NT>, dim3((unsigned)blocks), dim3((unsigned)bt), 0, c, a);
+}
+
+template <typename TS, typename TE>
+int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
+  if (n_req < 1 || n_req > HET_MAX)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one fused launch", n_req);
+  const Tuning tn = tuning_for(bs[0].opts);
+  HetArgs a;
+  std::memset(&a, 0, sizeof a);
+  bool ms3 = false;
+  bool noise = st[0].model_type == DPM_MODEL_NOISE && (st[0].flags & DPM_F_TO_X0) && !tn.force_generic;
+  for (int r = 0; r < n_req; ++r) {
+    const dpm_buffers& b = bs[r];
+    a.x[r] = b.x ? b.x : b.xe;
+    a.e0[r] = b.e0;
+    a.e1[r] = b.e1;
+    a.h1[r] = b.h1;
+    a.h2[r] = b.h2;
+    a.xo[r] = b.x_out;
+    a.mo[r] = b.m_out;
+    a.xo2[r] = b.x_out2;
+    a.p[r] = make_params(&st[r]);
+    ms3 = ms3 || st[r].form == DPM_FORM_MS3;
+    noise = noise && div_invariant_ok(st[r].alpha_e);
+  }
+  a.n = bs[0].n;
+  a.nreq = (uint32_t)n_req;
+  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
+#define DPM_HET(FS_)                                                                                            \
+  (noise ? (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, tn, c)                         \
+                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, tn, c))                       \
+         : (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_GENERIC>(a, tn, c)                          \
+                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_GENERIC>(a, tn, c)))
+  if (ms3) DPM_HET(HET_FORMS_3);
+  else DPM_HET(HET_FORMS_2);
+#undef DPM_HET
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dpm_set_error((int)e, "fused stage kernel launch failed: %s", hipGetErrorString(e));
+  return DPM_OK;
+}
+
 template <typename TS, typename TE, int FORM, int GUIDE>
 int launch_xe(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& s) {
   return (b->xe != nullptr && b->xe != b->x) ? launch_typed<TS, TE, FORM, GUIDE, true>(st, b, s)

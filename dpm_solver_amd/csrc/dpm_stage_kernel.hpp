@@ -1,5 +1,6 @@
 // dpm_stage_kernel.hpp -- the streaming stage kernels: per-stage scalars (KParams), prologues, update forms, the KExt
-// extensions, stage_kernel / stage_kernel_multi / stage_kernel_scalar (part of dpm_device.hpp; include that)
+// extensions, stage_kernel / stage_kernel_multi / stage_kernel_het / stage_kernel_scalar (part of dpm_device.hpp; include
+// that)
 #pragma once
 
 namespace {
@@ -567,6 +568,81 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_multi(const Mu
         nullptr, static_cast<const TS*>(tab.h1[r]), static_cast<const TS*>(tab.h2[r]), static_cast<TS*>(tab.xo[r]),
         static_cast<TS*>(tab.mo[r]), ngroups, t0, p, ext);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// heterogeneous fused stage (continuous batching): the launch shape and tile body of stage_kernel_multi, but every request
+// carries its own stage record -- form, flags and coefficients -- so requests at different positions of different plans
+// share one launch.  The records travel in the kernel-argument block next to the pointer table (no per-launch copy, no
+// allocation, captured by value in a graph).  Group-uniform (template arguments, checked by the host): dtype pair, n,
+// model type, guidance kind, DPM_F_TO_X0, prologue SPEC.  FORMS = bit set of the update forms the kernel dispatches
+// (workgroup-uniform switch over the record's form): {LIN1, TWO} for second-order multistep groups, {LIN1, TWO, MS3} for
+// the rest -- a 2M group does not pay MS3's registers.
+// The records are whole KParams, made by the host (make_params, as for every other launch) and read IN PLACE: a compact
+// record expanded into a local KParams on the device -- reciprocals and division guard derived there, or not -- leaves the
+// tail of that copy addressable in the generic kernels (the splat loads of div_uniform), and the backend parks it in LDS
+// (6 KiB per workgroup).  80-byte records and a 16-entry pointer table fit HIP's 4 KiB of kernel arguments at 16
+// requests per launch (32 would need 4.5 KiB).
+// ------------------------------------------------------------------------------------------------
+constexpr int HET_MAX = 16;
+struct HetArgs {
+  const void* x[HET_MAX];
+  const void* e0[HET_MAX];
+  const void* e1[HET_MAX];
+  const void* h1[HET_MAX];
+  const void* h2[HET_MAX];
+  void* xo[HET_MAX];
+  void* mo[HET_MAX];
+  void* xo2[HET_MAX];  // classifier-free guidance: the second half of the [2B, ...] network input (or null)
+  KParams p[HET_MAX];
+  int64_t n;
+  uint32_t nreq, spr;  // spr = super-tiles (U tiles) per request
+  uint32_t xcd_span;   // != 0: XCD-contiguous remap (see stage_kernel_multi)
+};
+static_assert(sizeof(HetArgs) <= 4096, "the heterogeneous launch's argument block must fit HIP's 4 KiB");
+constexpr unsigned HET_FORMS_2 = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_TWO);
+constexpr unsigned HET_FORMS_3 = HET_FORMS_2 | (1u << DPM_FORM_MS3);
+
+// One super-tile per 256-lane group, the grid covers them all (MultiShape, XCD-contiguous remap as stage_kernel_multi).
+// The argument is read through the kernarg segment pointer: every access with the wave-uniform request index r is then a
+// scalar load from the argument block itself (indexed through the by-value parameter, it becomes a private copy).
+template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het(const HetArgs args) {
+  (void)args;
+  const HetArgs& a = *(const HetArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int64_t ngroups = a.n / EPT;
+  const uint32_t total = a.nreq * a.spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (a.xcd_span && in_xcd >= a.xcd_span) return;
+  const uint32_t v = a.xcd_span ? (b & 7u) * a.xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = v / a.spr;
+  const int64_t t0 = (int64_t)(v - r * a.spr) * U;
+  const KParams& p = a.p[r];
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = a.xo2[r];
+  const TS* x = static_cast<const TS*>(a.x[r]);
+  const TE* e0 = static_cast<const TE*>(a.e0[r]);
+  const TE* e1 = static_cast<const TE*>(a.e1[r]);
+  const TS* h1 = static_cast<const TS*>(a.h1[r]);
+  const TS* h2 = static_cast<const TS*>(a.h2[r]);
+  TS* xo = static_cast<TS*>(a.xo[r]);
+  TS* mo = static_cast<TS*>(a.mo[r]);
+#define DPM_HET_TILES(F_) \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP>(x, nullptr, e0, e1, nullptr, h1, h2, xo, mo, ngroups, t0, p, ext)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_HET_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_HET_TILES(DPM_FORM_TWO); break;
+    case DPM_FORM_MS3:
+      if constexpr ((FORMS >> DPM_FORM_MS3) & 1u) DPM_HET_TILES(DPM_FORM_MS3);
+      break;
+    default: break;  // (the host groups only forms of FORMS)
+  }
+#undef DPM_HET_TILES
 }
 
 // same arithmetic, one element per lane: used when a pointer is not 16/32-byte aligned (views with offsets), for ragged

@@ -1,7 +1,7 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
 // translation unit: compiled ten times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
-//   unit B (1): the LIN1, MS3 and DENOISE forms (FORMS_B)
+//   unit B (1): the LIN1, MS3 and DENOISE forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het)
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1>"
 #endif
@@ -43,4 +43,13 @@ int dpm_launch_fused(const dpm_stage* st, const dpm_buffers* bs, int n_req, void
   return launch_multi_typed<TS, TE>(st, bs, n_req, s);
 }
 template int dpm_launch_fused<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+#endif
+
+#if DPM_UNIT == 1
+template <typename TS, typename TE>
+int dpm_launch_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_het_typed<TS, TE>(st, bs, n_req, s);
+}
+template int dpm_launch_het<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
 #endif

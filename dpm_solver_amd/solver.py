@@ -19,6 +19,7 @@ The class and its reference-named methods live here; what they run on is split b
   updates.py      the machinery under the public per-update methods
   adaptive.py     the adaptive solver: device-side controller, host loop, the predicate that chooses
   capture.py      hipGraph capture (`GraphedSample`) and auto_capture
+  pool.py         `RequestPool`: continuous batching, one fused launch per tick for requests at any stage
 
 `ref :NNN` = line in the reference's dpm_solver_pytorch.py.
 """
@@ -37,6 +38,7 @@ from . import adaptive as _adaptive
 from . import capture as _capture
 from . import loops as _loops
 from . import plan_cache as _plan_cache
+from . import pool as _pool
 from . import updates as _updates
 from .capture import GraphedSample
 from .correctors import MaskBlend  # noqa: F401  (part of this module's namespace since round 2)
@@ -569,6 +571,48 @@ class DPM_Solver:
     _run_plan_group = _loops.run_plan_group
     _auto_captured = _capture.auto_captured
 
+    def _sample_plan(self, x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type):
+        """The plan of a multistep / singlestep / singlestep_fixed `sample()` call, with the reference's argument checks and
+        errors (shared by sample() and the request pool)."""
+        if method == 'multistep':
+            assert steps >= order                       # (the reference's first check, ref :1172)
+        elif method == 'singlestep' and order not in (1, 2, 3):
+            raise ValueError("'order' must be '1' or '2' or '3'.")    # ref :533, before the grid is built
+        elif method == 'singlestep_fixed':
+            steps // order                              # ref :1218: K = steps // order (ZeroDivisionError for order 0)
+        if skip_type not in L.SKIP:
+            raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
+        plan_solver_type = solver_type
+        if solver_type not in L.SOLVER:
+            # the reference checks solver_type inside its second-order updates and the singlestep third-order one (ref
+            # :611, :697, :815), i.e. only when such an update is reached: a run made of first-order (and multistep
+            # third-order) updates accepts any value.  Plan with the default to see which updates the run contains.
+            plan_solver_type = "dpmsolver"
+        if method == 'multistep':
+            # the order is validated where the reference validates it -- when an update of that order is reached
+            # (ref :948-954): order=4 with steps <= 6 and lower_order_final never reaches one and runs (the planner
+            # raises the reference's ValueError otherwise)
+            assert steps >= order
+            if order > 3 and plan_solver_type is not solver_type:
+                # ... and the warm-up of such a run passes through a second-order update first (ref :1185-1193)
+                raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        elif method == 'singlestep_fixed' and order not in (1, 2, 3):
+            # ref :1218-1232: K = steps // order updates of that order -- none at all when K <= 0 (the run is a no-op),
+            # else the dispatcher's error at the first one (ref :927-930); order 0 is Python's ZeroDivisionError
+            K = steps // order
+            if K > 0:
+                raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
+            order, steps = 3, 1                    # a plan without update stages (K = 1 // 3 = 0)
+        elif order not in (1, 2, 3):
+            raise ValueError("'order' must be '1' or '2' or '3'.")
+        plan = self._get_plan(precision=self._precision(self._sdtype(x)), method=method, order=order, steps=steps,
+                              skip_type=skip_type, solver_type=plan_solver_type,
+                              lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
+                              t_T=float(t_T), t_0=float(t_0))
+        if plan_solver_type is not solver_type and any(st.form in (L.FORM_TWO, L.FORM_SS3T) for st in plan.stages):
+            raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+        return plan
+
     def sample(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform',
                method='multistep', lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver',
                atol=0.0078, rtol=0.05, return_intermediate=False):
@@ -598,43 +642,8 @@ class DPM_Solver:
                 if denoise_to_zero:
                     x = self.denoise_to_zero_fn(x, self._tt(t_0, device, shape1=True))
             elif method in ['multistep', 'singlestep', 'singlestep_fixed']:
-                if method == 'multistep':
-                    assert steps >= order                       # (the reference's first check, ref :1172)
-                elif method == 'singlestep' and order not in (1, 2, 3):
-                    raise ValueError("'order' must be '1' or '2' or '3'.")    # ref :533, before the grid is built
-                elif method == 'singlestep_fixed':
-                    steps // order                              # ref :1218: K = steps // order (ZeroDivisionError for order 0)
-                if skip_type not in L.SKIP:
-                    raise ValueError("Unsupported skip_type {}, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'".format(skip_type))
-                plan_solver_type = solver_type
-                if solver_type not in L.SOLVER:
-                    # the reference checks solver_type inside its second-order updates and the singlestep third-order one (ref
-                    # :611, :697, :815), i.e. only when such an update is reached: a run made of first-order (and multistep
-                    # third-order) updates accepts any value.  Plan with the default to see which updates the run contains.
-                    plan_solver_type = "dpmsolver"
-                if method == 'multistep':
-                    # the order is validated where the reference validates it -- when an update of that order is reached
-                    # (ref :948-954): order=4 with steps <= 6 and lower_order_final never reaches one and runs (the planner
-                    # raises the reference's ValueError otherwise)
-                    assert steps >= order
-                    if order > 3 and plan_solver_type is not solver_type:
-                        # ... and the warm-up of such a run passes through a second-order update first (ref :1185-1193)
-                        raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
-                elif method == 'singlestep_fixed' and order not in (1, 2, 3):
-                    # ref :1218-1232: K = steps // order updates of that order -- none at all when K <= 0 (the run is a no-op),
-                    # else the dispatcher's error at the first one (ref :927-930); order 0 is Python's ZeroDivisionError
-                    K = steps // order
-                    if K > 0:
-                        raise ValueError("Solver order must be 1 or 2 or 3, got {}".format(order))
-                    order, steps = 3, 1                    # a plan without update stages (K = 1 // 3 = 0)
-                elif order not in (1, 2, 3):
-                    raise ValueError("'order' must be '1' or '2' or '3'.")
-                plan = self._get_plan(precision=self._precision(self._sdtype(x)), method=method, order=order, steps=steps,
-                                      skip_type=skip_type, solver_type=plan_solver_type,
-                                      lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
-                                      t_T=float(t_T), t_0=float(t_0))
-                if plan_solver_type is not solver_type and any(st.form in (L.FORM_TWO, L.FORM_SS3T) for st in plan.stages):
-                    raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
+                plan = self._sample_plan(x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero,
+                                         solver_type)
                 x = self._run_plan(plan, x, method, cxt, return_intermediate, intermediates)
             else:
                 raise ValueError("Got wrong method {}".format(method))
@@ -669,6 +678,13 @@ class DPM_Solver:
         finally:
             self._group = None
 
+
+    def request_pool(self):
+        """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
+        own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
+        then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
+        bit-identical to `sample()`; see dpm_solver_amd/pool.py."""
+        return _pool.RequestPool(self)
 
     def capture(self, x, warmup=2, **sample_kwargs):
         """hipGraph-capture `sample(x, **sample_kwargs)` for a fixed shape (extension).

@@ -51,11 +51,13 @@ extern "C" {
    process-global mutable state: per-device contexts only (the chain of clustered launches, the diagnostics word).
    201 (round 6) dpm_add_noise_launch_f64 (double times on double tensors); -fvisibility=hidden + DPM_API: the dynamic symbol
    table is this header's functions and nothing else.
+   202 dpm_launch_opts.per_request_stages (was reserved[0]): dpm_stage_launch_multi with one stage record per request --
+   requests at different positions of different plans in one fused launch (continuous batching).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 201
+#define DPM_HIP_VERSION 202
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -161,7 +163,9 @@ typedef struct dpm_launch_opts {
                                identical; what a single request's stage costs next to the fused launch)               */
   int32_t thr_spin_limit;   /* > 0: polls (a microsecond or two each) before a wait on a cluster peer gives up and the
                                workgroup finishes its sample alone; 0 = the default, 4096                             */
-  int32_t reserved[5];      /* zero                                                                                   */
+  int32_t per_request_stages; /* 1: dpm_stage_launch_multi reads `st` as an array of n_req stage records, request r is
+                               advanced by st[r] (version 202; see there)                                             */
+  int32_t reserved[4];      /* zero                                                                                   */
 } dpm_launch_opts;
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
@@ -313,7 +317,16 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    find a DIFFERENT workspace in every request; classifier-free guidance keeps its duplicate store (x_out2).  Stages
    neither family covers (mask blend, classifier guidance, strided or
    unaligned buffers, the singlestep mid-stages, thresholding with a shared workspace) are launched request by
-   request; results are identical either way. */
+   request; results are identical either way.
+   Per-request stages (version 202): with bs[0].opts->per_request_stages == 1, `st` points at n_req stage records and
+   request r is advanced by st[r] -- requests that arrived at different times, at different positions of plans with
+   different step counts or orders (continuous batching).  Every request is checked as dpm_stage_launch checks it (same
+   error texts; nothing is launched when one fails).  Requests whose stage is first-order, 2M-style second-order (TWO) or
+   multistep third-order (MS3), without thresholding, mask blend or classifier guidance, whose evaluation state is the
+   state and whose buffers are dense and 16-byte aligned, are fused -- 16 per launch: the records travel in the kernel's
+   arguments, within HIP's 4 KiB -- with every other
+   request that agrees with them on dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the rest are launched
+   one by one.  Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
