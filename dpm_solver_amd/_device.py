@@ -110,6 +110,8 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
     # brought to that order (no-ops from the second stage on, the states this function hands out are in it).  The mask
     # blend's operands are indexed with a flat period in the default order: such launches stay there.
     mf = _mf_of(e0) if (e0.shape == ref_t.shape and not (ext is not None and ext.get("blend") is not None)) else None
+    if st.flags & L.F_NOISE:
+        mf = None    # the noise contract indexes the default [B, C, H, W] order: SDE stages run on contiguous tensors
     x, xe, h1, h2 = _conv(x, sd, mf), _conv(xe, sd, mf), _conv(h1, sd, mf), _conv(h2, sd, mf)
     ed = e0.dtype
     if ed not in _DT or (sd != torch.float32 and ed != sd) or ed is torch.float64:

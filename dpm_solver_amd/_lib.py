@@ -23,6 +23,7 @@ LAB_LIB_PATH = os.path.join(os.path.dirname(_HERE), "tools", "_variants", "lab",
 DPM_OK = 0
 ERR_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_NOMEM, ERR_CALLBACK, ERR_FAULT = -1, -2, -3, -4, -5, -6
 ALGO = {"dpmsolver": 0, "dpmsolver++": 1}
+ALGO_SDE_DPMSOLVERPP = 2      # dpm_plan_create only (DPM_Solver.sample_sde)
 SOLVER = {"dpmsolver": 0, "taylor": 1}
 METHOD = {"multistep": 0, "singlestep": 1, "singlestep_fixed": 2}
 SKIP = {"time_uniform": 0, "logSNR": 1, "time_quadratic": 2}
@@ -32,6 +33,7 @@ DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_F64 = 0, 1, 2, 3
 EVAL_LOG_ALPHA, EVAL_ALPHA, EVAL_STD, EVAL_LAMBDA, EVAL_INV_LAMBDA = 0, 1, 2, 3, 4
 FORM_LIN1, FORM_TWO, FORM_MS3, FORM_SS3T, FORM_DENOISE = 0, 1, 2, 3, 4
 F_TO_X0, F_STORE_M, F_BASE_HIST, F_THRESH, F_USER_X0, F_BLEND = 1, 2, 4, 8, 16, 32
+F_NOISE = 64
 SRC_STATE, SRC_TMP = 0, 1
 # knobs of the LAB build (include/dpm_lab.h: dpm_tuning_set / dpm_tuning_get; the product library has none)
 TUNE_UNROLL, TUNE_NONTEMPORAL, TUNE_BLOCKS_PER_CU, TUNE_ASSUME_RESIDENT = 0, 1, 2, 3
@@ -74,7 +76,8 @@ class StageF64(C.Structure):
 class LaunchOpts(C.Structure):
     """dpm_launch_opts: what a caller may choose per call (zero = defaults)"""
     _fields_ = [("cluster_in_graph", C.c_int32), ("no_fuse", C.c_int32), ("thr_spin_limit", C.c_int32),
-                ("per_request_stages", C.c_int32), ("reserved", C.c_int32 * 4)]
+                ("per_request_stages", C.c_int32), ("noise_seed_lo", C.c_uint32), ("noise_seed_hi", C.c_uint32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class Buffers(C.Structure):

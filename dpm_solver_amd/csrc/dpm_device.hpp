@@ -127,6 +127,8 @@ template <typename TS, typename TE>
 const void* dpm_catchall_thresh();
 template <typename TS, typename TE, bool DYN>
 const void* dpm_catchall_scalar();
+template <typename TS, typename TE>
+const void* dpm_catchall_scalar_noise();  // the SDE stages' one-element-per-lane kernel (DPM_F_NOISE)
 
 #include "dpm_access.hpp"
 #include "dpm_stage_kernel.hpp"

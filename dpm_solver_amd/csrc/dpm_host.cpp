@@ -719,11 +719,38 @@ void split_stage64(const dpmc::Stage64& q, dpm_stage* st, dpm_stage_f64* d64) {
   d64->thr_ratio = q.thr_ratio; d64->thr_max = q.thr_max; d64->blend_alpha = q.blend_alpha; d64->blend_sigma = q.blend_sigma;
   d64->time_f64 = q.time_f64;
 }
+// SDE-DPM-Solver++ (DPM_ALGO_SDE_DPMSOLVERPP; diffusers' sde-dpmsolver++): the multistep DPM-Solver++ plan -- same stages,
+// forms, times, buffer roles and history slots -- with the scalars of every LIN1 / TWO stage replaced by the stochastic
+// update's, evaluated in double at the plan's times and rounded once, and DPM_F_NOISE set.  In FORM_TWO's convention
+// (D = k0 (mn - h1); out = (cx x - c0 mn) - c1 D), h = lambda_t - lambda_s, r0 = h_0 / h:
+//   cx = (sigma_t / sigma_s) e^-h,  c0 = alpha_t expm1(-2h),  k0 = 1 / r0,
+//   c1 = 0.5 alpha_t expm1(-2h) (solver_type 'dpmsolver' = diffusers' midpoint) | -alpha_t (1 + expm1(-2h) / 2h) ('taylor' = heun),
+//   c2 = sigma_t sqrt(-expm1(-2h)): the scale of the in-kernel Gaussian term.  DENOISE stays as it is (no noise).
+void sde_scalars(const dpm_schedule* s, int solver_type, const std::vector<float>& grid, std::vector<dpm_stage>& stages) {
+  const dpmc::SchedView64 v = s->view64();
+  for (dpm_stage& st : stages) {
+    if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO) continue;
+    const int i = st.index;  // multistep: stage i advances grid[i] -> grid[i + 1]
+    const double ts = grid[i], tt = grid[i + 1];
+    const double lam_s = v.lambda(ts), lam_t = v.lambda(tt);
+    const double sig_s = v.std_(ts), sig_t = v.std_(tt), a_t = v.alpha(tt);
+    const double h = lam_t - lam_s, em = expm1(-2. * h);
+    st.cx = (float)(sig_t / sig_s * exp(-h));
+    st.c0 = (float)(a_t * em);
+    st.c2 = (float)(sig_t * sqrt(-em));
+    if (st.form == DPM_FORM_TWO) {
+      const double h_0 = lam_s - v.lambda((double)grid[i - 1]);
+      st.k[0] = (float)(1. / (h_0 / h));
+      st.c1 = (float)(solver_type == DPM_SOLVER_DPMSOLVER ? 0.5 * (a_t * em) : -(a_t * (1. + em / (2. * h))));
+    }
+    st.flags |= DPM_F_NOISE;
+  }
+}
 }  // namespace
 
 extern "C" int dpm_plan_create(const dpm_schedule* s, const dpm_plan_desc* d, dpm_plan** out) {
   if (!s || !d || !out) return dpm_set_error(DPM_ERR_ARG, "null pointer");
-  if (check_enum(d->algorithm_type, 0, 1, "algorithm_type") || check_enum(d->model_type, 0, 3, "model_type") ||
+  if (check_enum(d->algorithm_type, 0, 2, "algorithm_type") || check_enum(d->model_type, 0, 3, "model_type") ||
       check_enum(d->guidance, 0, 2, "guidance_type"))
     return DPM_ERR_ARG;
   if (d->method < 0 || d->method > 2) return dpm_set_error(DPM_ERR_ARG, "Got wrong method %d", d->method);
@@ -735,11 +762,26 @@ extern "C" int dpm_plan_create(const dpm_schedule* s, const dpm_plan_desc* d, dp
     return dpm_set_error(DPM_ERR_ARG, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array");
   if (d->steps < 1) return dpm_set_error(DPM_ERR_ARG, "steps must be >= 1, got %d", d->steps);
   if (d->precision != 0 && d->precision != 1) return dpm_set_error(DPM_ERR_ARG, "precision must be 0 (fp32) or 1 (double)");
+  const bool sde = d->algorithm_type == DPM_ALGO_SDE_DPMSOLVERPP;
+  dpm_plan_desc ode = *d;  // an SDE plan is the DPM-Solver++ multistep plan with other scalars (sde_scalars)
+  if (sde) {
+    if (d->method != DPM_METHOD_MULTISTEP)
+      return dpm_set_error(DPM_ERR_UNSUPPORTED, "sde-dpmsolver++: multistep only (method %d)", d->method);
+    if (d->order < 1 || d->order > 2)
+      return dpm_set_error(DPM_ERR_ARG, "sde-dpmsolver++: 'order' must be 1 or 2 (no third-order SDE update), got %d", d->order);
+    if (d->thresholding)
+      return dpm_set_error(DPM_ERR_UNSUPPORTED, "sde-dpmsolver++ with dynamic thresholding: the thresholding kernel has no noise epilogue");
+    if (d->precision)
+      return dpm_set_error(DPM_ERR_UNSUPPORTED, "sde-dpmsolver++: double-precision plans (no double noise kernel)");
+    ode.algorithm_type = DPM_ALGO_DPMSOLVERPP;
+    d = &ode;
+  }
   dpm_plan* p = new (std::nothrow) dpm_plan;
   if (!p) return dpm_set_error(DPM_ERR_NOMEM, "out of memory");
   int rc;
   if (d->precision == 0) {
     rc = plan_build(s, d, p->stages, p->grid, p->slots);
+    if (!rc && sde) sde_scalars(s, d->solver_type, p->grid, p->stages);
     p->grid64.assign(p->grid.begin(), p->grid.end());
   } else {
     const dpmc::SchedView64 v = s->view64();
@@ -893,7 +935,7 @@ extern "C" int dpm_plan_run_multi(const dpm_plan* p, const dpm_run_buffers* rbs,
       b.m_out = st.m_slot >= 0 ? rb.hist[st.m_slot] : nullptr;
       b.workspace = rb.workspace;
       b.thr_hint = rb.thr_hint;
-      b.opts = rbs[0].opts;
+      b.opts = (st.flags & DPM_F_NOISE) ? rb.opts : rbs[0].opts;  // SDE stages: every request its own seed
       b.coef64 = p->stages64.empty() ? nullptr : &p->stages64[(size_t)st.index];
       b.n = rb.n;
       b.batch = rb.batch;

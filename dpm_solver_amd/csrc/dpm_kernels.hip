@@ -93,6 +93,14 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool report =
     if (b->mask_period >= ((int64_t)1 << 31) && b->mask_period != b->n)
       return fail(DPM_ERR_UNSUPPORTED, "stage_launch: a broadcast mask of 2^31 or more elements");
   }
+  if (st->flags & DPM_F_NOISE) {  // the SDE epilogue exists in the streaming family's LIN1 / TWO kernels only
+    if (st->form != DPM_FORM_LIN1 && st->form != DPM_FORM_TWO)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE is valid on LIN1 / TWO stages only (form %d)", st->form);
+    if (st->flags & DPM_F_THRESH)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with DPM_F_THRESH (the thresholding kernel has no noise epilogue)");
+    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with a double state (no double noise kernel)");
+  }
   if (b->eps_stride != 0 && b->eps_stride < b->n / b->batch)
     return fail(DPM_ERR_ARG, "stage_launch: eps_stride=%lld is smaller than a sample (%lld elements)",
                 (long long)b->eps_stride, (long long)(b->n / b->batch));
@@ -126,6 +134,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   if (!st || !b) return dpm_set_error(DPM_ERR_ARG, "stage_launch: null pointer");
   if (const int rc = check_stage_buffers(st, b)) return rc;
   if (b->n == 0) return DPM_OK;
+  if (dyn && (st->flags & DPM_F_NOISE))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with device-resident coefficients");
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -140,8 +150,9 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused
   // family does not build (thresholding, mask blend, classifier guidance, SS3T / DENOISE, unaligned or strided operands)
-  // come back MULTI_NOT_BUILT and take the single-request path below.
-  if (!dyn && !(st->flags & (DPM_F_THRESH | DPM_F_BLEND))) {
+  // come back MULTI_NOT_BUILT and take the single-request path below.  SDE stages (DPM_F_NOISE) never take it: the fused
+  // kernel has no noise epilogue.
+  if (!dyn && !(st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))) {
     const int big = tuning_for(bb.opts).big_tiles;
     if (big > 0 && (bb.n / EPT + 255) / 256 >= big) {
       const int rc = launch_fused(*p, st, &bb, 1, stream, ev_start, ev_stop);
@@ -169,7 +180,8 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
   // a group fuses when its requests agree in size and dtypes and each one passes the single launch's checks; otherwise
   // every request is launched on its own (and reports its own error)
   const PairUnits* p = pair_of(bs[0].state_dtype, bs[0].eps_dtype);
-  bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0;
+  // SDE stages are launched request by request, each with the seed of its own bs[r].opts
+  bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0 && !(st->flags & DPM_F_NOISE);
   for (int r = 0; r < n_req && fuse; ++r)
     fuse = bs[r].n == bs[0].n && bs[r].batch == bs[0].batch && bs[r].state_dtype == bs[0].state_dtype &&
            bs[r].eps_dtype == bs[0].eps_dtype && check_stage_buffers(st, &bs[r], false) == DPM_OK;
@@ -197,7 +209,7 @@ namespace {
 bool het_fusable(const dpm_stage& st, const dpm_buffers& b) {
   const PairUnits* p = pair_of(b.state_dtype, b.eps_dtype);
   if (!p || b.n <= 0 || b.n % EPT != 0) return false;
-  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND)) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE)) return false;
   if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
   if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3) return false;
   if (b.eps_stride && b.eps_stride != b.n / b.batch) return false;

@@ -594,9 +594,63 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   return DPM_OK;
 }
 
+// ---- an SDE stage (DPM_F_NOISE; checked by the caller: LIN1 / TWO, no thresholding, no device-resident coefficients):
+// stage_kernel_noise where the streaming family's vector conditions hold, stage_kernel_scalar_noise otherwise.  The seed
+// comes from the call's dpm_launch_opts, the Philox counter is the stage index, the scale the stage's c2.
+template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
+int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
+  KNoise nz;
+  nz.key0 = b->opts ? b->opts->noise_seed_lo : 0u;
+  nz.key1 = b->opts ? b->opts->noise_seed_hi : 0u;
+  nz.ctr = (uint32_t)st->index;
+  nz.scale = st->c2;
+  const KParams& p = op.p;
+  const KExt& ext = op.ext;
+  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
+  constexpr bool BUILT = (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO) && GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
+  bool vec = BUILT && b->n % EPT == 0 && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.xo, as) && aligned(op.mo, as) &&
+             aligned(op.e0, ae) && aligned(op.e1, ae);
+  if (op.use_ext)
+    vec = vec && aligned(ext.xo2, as) && aligned(ext.mask, as) && aligned(ext.ba, as) && aligned(ext.bb, as) &&
+          ext.mask_period % EPT == 0 && (!ext.eps_stride || (ext.per_sample % EPT == 0 && ext.eps_stride % EPT == 0));
+  if (!vec) {
+    int64_t blocks = (b->n + 255) / 256;
+    const int64_t cap = (int64_t)op.n_cu * 16;
+    if (blocks > cap) blocks = cap;
+    using ScalarNoise = decltype(&stage_kernel_scalar_noise<TS, TE>);
+    launch(reinterpret_cast<ScalarNoise>(const_cast<void*>(dpm_catchall_scalar_noise<TS, TE>())), dim3((unsigned)blocks), dim3(256),
+           0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, nz);
+  } else if constexpr (BUILT) {
+    const Tuning tn = tuning_for(b->opts);
+    const bool x0 = !tn.force_generic && st->model_type == DPM_MODEL_NOISE && (st->flags & DPM_F_TO_X0) && div_invariant_ok(st->alpha_e);
+    // the launch shape of stage_kernel with one tile per iteration (launch_stream: shape_for(1))
+    const int64_t ntiles = ((b->n / EPT) + 255) / 256;
+    const int bt = tn.block_threads > 0 ? tn.block_threads : (ntiles >= 4 * (int64_t)op.n_cu ? STAGE_MAX_THREADS : 256);
+    const int64_t per = bt / 256;
+    int64_t blocks = (ntiles + per - 1) / per;
+    const int64_t cap = std::max<int64_t>(1, (int64_t)op.n_cu * tn.blocks_per_cu / per);
+    if (blocks > cap) blocks = cap;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks)), block((unsigned)bt);
+#define DPM_NOISE_LAUNCH(SPEC_, EXT_) \
+  launch(stage_kernel_noise<TS, TE, FORM, GUIDE, SPEC_, EXT_>, grid, block, 0, stream, op.x, op.e0, op.e1, op.h1, op.xo, op.mo, b->n, p, ext, nz)
+    if (op.use_ext) {
+      if (x0) DPM_NOISE_LAUNCH(SPEC_NOISE_X0, true);
+      else DPM_NOISE_LAUNCH(SPEC_GENERIC, true);
+    } else {
+      if (x0) DPM_NOISE_LAUNCH(SPEC_NOISE_X0, false);
+      else DPM_NOISE_LAUNCH(SPEC_GENERIC, false);
+    }
+#undef DPM_NOISE_LAUNCH
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return dpm_set_error((int)e, "noise stage kernel launch failed: %s", hipGetErrorString(e));
+  return DPM_OK;
+}
+
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
 int launch_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream) {
   const Operands<TS, TE> op(st, b);
+  if (st->flags & DPM_F_NOISE) return launch_noise<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
   return (st->flags & DPM_F_THRESH) ? launch_thresh<TS, TE, FORM, GUIDE, XE>(st, b, stream, op)
                                     : launch_stream<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
 }
@@ -819,5 +873,9 @@ const void* dpm_catchall_thresh() {
 template <typename TS, typename TE, bool DYN>
 const void* dpm_catchall_scalar() {
   return reinterpret_cast<const void*>(&stage_kernel_scalar<TS, TE, DYN>);
+}
+template <typename TS, typename TE>
+const void* dpm_catchall_scalar_noise() {
+  return reinterpret_cast<const void*>(&stage_kernel_scalar_noise<TS, TE>);
 }
 #endif

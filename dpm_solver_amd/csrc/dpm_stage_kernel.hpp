@@ -289,6 +289,68 @@ __device__ __forceinline__ float blend_ref(float v, float m, float a, float b, b
 }
 
 // ------------------------------------------------------------------------------------------------
+// in-kernel Gaussian noise of the SDE stages (DPM_F_NOISE; include/dpm_hip.h, "noise contract"): out += scale * z, with z
+// of element i a function of (seed, stage index, i) only -- i = index in the flat [B, C, H, W] state.  Philox4x32-10
+// (Random123; rocRAND's and torch's generator) keyed by the seed, counter (i >> 2 lo, i >> 2 hi, stage index, 0): one call
+// gives the four z of elements 4g .. 4g+3 by Box-Muller, element i taking output pair p = (i & 3) >> 1, cos for even i and
+// sin for odd i.  A separate kernel argument (KParams' 80 bytes size the heterogeneous launch's records).
+// ------------------------------------------------------------------------------------------------
+struct KNoise {
+  uint32_t key0, key1;  // the seed, low and high word
+  uint32_t ctr;         // dpm_stage.index
+  float scale;          // dpm_stage.c2: sigma_t * sqrt(-expm1(-2h))
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+// 32 random bits -> u = (2 (r >> 9) + 1) 2^-24: the 23 high bits, centred -- exact in fp32, inside (0, 1)
+__device__ __forceinline__ float philox_unit(uint32_t r) {
+  return (float)(r >> 9) * 0x1p-23f + 0x1p-24f;
+}
+// one Box-Muller pair: radius from u_r, angle 2 pi u_a (v_cos_f32 / v_sin_f32 take their argument in revolutions)
+__device__ __forceinline__ float bm_radius(uint32_t r) { return sqrtf(-2.f * logf(philox_unit(r))); }
+__device__ __forceinline__ float bm_cos(uint32_t a) { return __builtin_amdgcn_cosf(philox_unit(a)); }
+__device__ __forceinline__ float bm_sin(uint32_t a) { return __builtin_amdgcn_sinf(philox_unit(a)); }
+__device__ __forceinline__ void philox_block(const KNoise& nz, uint64_t g, uint32_t (&c)[4]) {
+  c[0] = (uint32_t)g;
+  c[1] = (uint32_t)(g >> 32);
+  c[2] = nz.ctr;
+  c[3] = 0u;
+  philox4x32_10(c, nz.key0, nz.key1);
+}
+// z of the four elements 4g .. 4g+3
+__device__ __forceinline__ void noise4(const KNoise& nz, uint64_t g, float* z) {
+  uint32_t c[4];
+  philox_block(nz, g, c);
+  const float r0 = bm_radius(c[0]), r1 = bm_radius(c[2]);
+  z[0] = r0 * bm_cos(c[1]);
+  z[1] = r0 * bm_sin(c[1]);
+  z[2] = r1 * bm_cos(c[3]);
+  z[3] = r1 * bm_sin(c[3]);
+}
+// z of element i alone (the same operations on the same bits as noise4)
+__device__ __forceinline__ float noise1(const KNoise& nz, uint64_t i) {
+  uint32_t c[4];
+  philox_block(nz, i >> 2, c);
+  const bool p1 = (i & 2u) != 0;
+  const float r = bm_radius(p1 ? c[2] : c[0]);
+  const uint32_t a = p1 ? c[3] : c[1];
+  return r * ((i & 1u) ? bm_sin(a) : bm_cos(a));
+}
+
+// ------------------------------------------------------------------------------------------------
 // the streaming stage kernel
 // ------------------------------------------------------------------------------------------------
 // model values of the U tiles of one workgroup iteration for prologue mode PM (the loaded registers arrive by reference:
@@ -321,13 +383,17 @@ __device__ __forceinline__ void tile_models(const float (&vx)[U][EPT], const flo
 // through global_load_dwordx4 into registers: the lone-launch variant of the north-star kernels (2-byte state and network
 // output, unguided noise-prediction network, dpmsolver++: x, eps and -- second order -- the cached model value).  Same
 // elements per lane, same arithmetic, same bits; `dma_rows` = the workgroup's dynamic LDS (3 KiB per wavefront).
-template <typename TS, typename TE, int FORM, int GUIDE, bool XE, int SPEC, int U, int NT, bool EXT, bool DMA = false>
+// NOISE = the SDE epilogue (stage_kernel_noise): out += nz.scale * z before the store rounding (and before a mask blend, the
+// corrector that runs after the update).  The element index of ox[j]: split layout -> 4-element runs at tile*2048 + 4*lane and
+// tile*2048 + 1024 + 4*lane, else the 8 consecutive elements of group gi -- two Philox blocks per lane either way.
+template <typename TS, typename TE, int FORM, int GUIDE, bool XE, int SPEC, int U, int NT, bool EXT, bool DMA = false,
+          bool NOISE = false>
 __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* __restrict__ xe,
                                             const TE* __restrict__ e0, const TE* __restrict__ e1,
                                             const TE* __restrict__ g, const TS* __restrict__ h1,
                                             const TS* __restrict__ h2, TS* __restrict__ xo, TS* __restrict__ mo,
                                             const int64_t ngroups, const int64_t t0, const KParams& p, const KExt& ext,
-                                            u32x4* dma_rows = nullptr) {
+                                            u32x4* dma_rows = nullptr, const KNoise* nz = nullptr) {
   using FT = FormTraits<FORM>;
   static_assert(!DMA || (sizeof(TS) == 2 && sizeof(TE) == 2 && !EXT && !XE && GUIDE == DPM_GUIDE_NONE && SPEC == SPEC_NOISE_X0 &&
                          U == 1 && (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO)),
@@ -438,6 +504,15 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
       ox[q] = o.x;
       ox[q + 1] = o.y;
     }
+    if constexpr (NOISE) {
+      const uint64_t ga = split ? (uint64_t)(t0 + u) * 512u + tile_lane() : 2u * (uint64_t)gi;
+      const uint64_t gb = split ? ga + 256u : ga + 1u;
+      float z[EPT];
+      noise4(*nz, ga, z);
+      noise4(*nz, gb, z + 4);
+#pragma unroll
+      for (int j = 0; j < EPT; ++j) ox[j] = ox[j] + nz->scale * z[j];
+    }
     if (EXT && mask) {
 #pragma unroll
       for (int j = 0; j < EPT; ++j)
@@ -520,6 +595,25 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_dma(const TS* 
   for (int64_t t0 = (int64_t)blockIdx.x * per + sub; t0 < ntiles; t0 += (int64_t)gridDim.x * per)
     stage_tiles<TS, TE, FORM, DPM_GUIDE_NONE, false, SPEC_NOISE_X0, 1, NT, false, true>(x, nullptr, e0, nullptr, nullptr, h1, nullptr,
                                                                                       xo, mo, ngroups, t0, p, ext, rows);
+}
+
+// SDE stage (DPM_F_NOISE, forms LIN1 / TWO): stage_kernel's tiling with the noise epilogue -- one tile per 256-lane group and
+// iteration, the nt mask of the inputs-from-HBM situation, no ragged tail (n % 8 != 0 takes stage_kernel_scalar_noise), the
+// evaluation state is the state, unguided or classifier-free.  Its own family, so that the ODE kernels stay as they are.
+template <typename TS, typename TE, int FORM, int GUIDE, int SPEC, bool EXT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_noise(const TS* __restrict__ x, const TE* __restrict__ e0,
+                                                                        const TE* __restrict__ e1, const TS* __restrict__ h1,
+                                                                        TS* __restrict__ xo, TS* __restrict__ mo, int64_t n,
+                                                                        const KParams p, KExt ext, const KNoise nz) {
+  static_assert((FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO) && GUIDE != DPM_GUIDE_CLASSIFIER, "noise: LIN1 / TWO, no classifier");
+  constexpr int NT = sizeof(TS) == 2 ? 1 : (sizeof(TE) == 4 ? 5 : 1);
+  const int64_t ngroups = n / EPT;
+  const int64_t ntiles = (ngroups + 255) / 256;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  for (int64_t t0 = (int64_t)blockIdx.x * per + sub; t0 < ntiles; t0 += (int64_t)gridDim.x * per)
+    stage_tiles<TS, TE, FORM, GUIDE, false, SPEC, 1, NT, EXT, false, true>(x, nullptr, e0, e1, nullptr, h1, nullptr, xo, mo, ngroups,
+                                                                          t0, p, ext, nullptr, &nz);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -649,19 +743,12 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het(const HetA
 // extended launches and for (form, xe) combinations the streaming family does not instantiate.  ONE kernel per dtype
 // pair: form and guidance are read from the stage record (wave-uniform branches), xe always points at the state the
 // network saw (= x when there is no separate one).
-template <typename TS, typename TE, bool DYN = false>
-__global__ __launch_bounds__(256) void stage_kernel_scalar(const TS* __restrict__ x, const TS* __restrict__ xe,
-                                                           const TE* __restrict__ e0, const TE* __restrict__ e1,
-                                                           const TE* __restrict__ g, const TS* __restrict__ h1,
-                                                           const TS* __restrict__ h2, TS* __restrict__ xo,
-                                                           TS* __restrict__ mo, int64_t n, const KParams p_arg, KExt ext,
-                                                           const dpm_stage* dyn, const int32_t* skip) {
-  if constexpr (DYN) {
-    if (*skip) return;
-  }
-  KParams p_dyn;  // (a copy of the argument, even a const one, would leave part of it in memory -> LDS)
-  if constexpr (DYN) p_dyn = params_from_dyn(p_arg, dyn);
-  const KParams& p = DYN ? p_dyn : p_arg;
+// NOISE: the SDE epilogue (stage_kernel_scalar_noise), out += nz.scale * z of the element's flat index
+template <typename TS, typename TE, bool NOISE>
+__device__ __forceinline__ void scalar_elements(const TS* __restrict__ x, const TS* __restrict__ xe, const TE* __restrict__ e0,
+                                                const TE* __restrict__ e1, const TE* __restrict__ g, const TS* __restrict__ h1,
+                                                const TS* __restrict__ h2, TS* __restrict__ xo, TS* __restrict__ mo, int64_t n,
+                                                const KParams& p, const KExt& ext, const KNoise& nz) {
   const bool need_xe = (p.flags & DPM_F_TO_X0) || p.model_type == DPM_MODEL_X_START || p.model_type == DPM_MODEL_V;
   const bool store_m = p.flags & DPM_F_STORE_M;
   const bool nx = form_needs_x<FORM_RT>(p), nh1 = form_needs_h1<FORM_RT>(p), nh2 = form_needs_h2<FORM_RT>(p);
@@ -678,6 +765,7 @@ __global__ __launch_bounds__(256) void stage_kernel_scalar(const TS* __restrict_
     const float xev = need_xe ? to_f32(xe[i]) : 0.f;
     const float mn = prologue<GUIDE_RT, PM_RT, float, TE>(xev, to_f32(e0[ie]), cfg ? to_f32(e1[ie]) : 0.f, clsg ? to_f32(g[i]) : 0.f, p);
     float o = combine_any<FORM_RT, float, TE>(xv, mn, nh1 ? to_f32(h1[i]) : 0.f, nh2 ? to_f32(h2[i]) : 0.f, p, hm);
+    if constexpr (NOISE) o = o + nz.scale * noise1(nz, (uint64_t)i);
     if (mask) {
       o = to_f32(from_f32<TS>(o));  // the reference blends the stored state
       o = blend_ref(o, to_f32(mask[i % ext.mask_period]), to_f32(ba[i]), bb ? to_f32(bb[i]) : 0.f, bb != nullptr, ext);
@@ -687,6 +775,34 @@ __global__ __launch_bounds__(256) void stage_kernel_scalar(const TS* __restrict_
     if (xo2) xo2[i] = ov;
     if (store_m) mo[i] = from_f32<TS>(mn);
   }
+}
+
+template <typename TS, typename TE, bool DYN = false>
+__global__ __launch_bounds__(256) void stage_kernel_scalar(const TS* __restrict__ x, const TS* __restrict__ xe,
+                                                           const TE* __restrict__ e0, const TE* __restrict__ e1,
+                                                           const TE* __restrict__ g, const TS* __restrict__ h1,
+                                                           const TS* __restrict__ h2, TS* __restrict__ xo,
+                                                           TS* __restrict__ mo, int64_t n, const KParams p_arg, KExt ext,
+                                                           const dpm_stage* dyn, const int32_t* skip) {
+  if constexpr (DYN) {
+    if (*skip) return;
+  }
+  KParams p_dyn;  // (a copy of the argument, even a const one, would leave part of it in memory -> LDS)
+  if constexpr (DYN) p_dyn = params_from_dyn(p_arg, dyn);
+  const KParams& p = DYN ? p_dyn : p_arg;
+  scalar_elements<TS, TE, false>(x, xe, e0, e1, g, h1, h2, xo, mo, n, p, ext, KNoise{});
+}
+
+// the SDE stages the vector family does not take (unaligned or ragged buffers, classifier guidance, a separate evaluation
+// state): one element per lane, the same z (noise1 == noise4 element by element)
+template <typename TS, typename TE>
+__global__ __launch_bounds__(256) void stage_kernel_scalar_noise(const TS* __restrict__ x, const TS* __restrict__ xe,
+                                                                 const TE* __restrict__ e0, const TE* __restrict__ e1,
+                                                                 const TE* __restrict__ g, const TS* __restrict__ h1,
+                                                                 const TS* __restrict__ h2, TS* __restrict__ xo,
+                                                                 TS* __restrict__ mo, int64_t n, const KParams p, KExt ext,
+                                                                 const KNoise nz) {
+  scalar_elements<TS, TE, true>(x, xe, e0, e1, g, h1, h2, xo, mo, n, p, ext, nz);
 }
 
 }  // namespace

@@ -23,6 +23,7 @@ using Eps = Pair::second_type;   // ... and network-output dtype
 template const void* dpm_catchall_thresh<State, Eps>();
 template const void* dpm_catchall_scalar<State, Eps, false>();
 template const void* dpm_catchall_scalar<State, Eps, true>();
+template const void* dpm_catchall_scalar_noise<State, Eps>();
 #endif
 
 template <typename TS, typename TE, unsigned FORMS>

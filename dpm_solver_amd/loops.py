@@ -116,6 +116,8 @@ def run_plan_fast(self, plan, x, sd, cfg):
     # the network's layout is the run's (see DV._mf_of): an NHWC network gets NHWC states and its outputs are bound as
     # they are; x_T is brought there once and the result goes back to x_T's layout, like ATen would return it
     mf = DV._mf_of(first[0]) if first[0].shape == x.shape else None
+    if plan.sde:
+        mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit))
     fr = None if capturing else self._fast.get(key)      # a captured graph bakes its buffers in: give it its own
     if fr is None:
@@ -129,6 +131,11 @@ def run_plan_fast(self, plan, x, sd, cfg):
     out = DV._empty(x.shape, sd, device, mf)
     bufs, refs, roles = fr.bufs, fr.refs, plan.roles
     bufs[fr.last].x_out = out.data_ptr()
+    if plan.sde:
+        # the seed is patched per call, never cached in the launch records
+        o = self._opts_ptr()
+        for b in bufs:
+            b.opts = o
     xbuf, xfull = fr.xbuf, fr.xfull
     launch = DV._stage_launch_raw
     for i, b in enumerate(bufs):

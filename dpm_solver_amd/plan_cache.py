@@ -29,6 +29,7 @@ class _Plan:
         self.slots = L.lib.dpm_plan_num_slots(self.handle)
         self.stages = []
         self.stages64 = None                 # double-precision plans: the dpm_stage_f64 twin of every stage
+        self.sde = desc.algorithm_type == L.ALGO_SDE_DPMSOLVERPP   # stages carry DPM_F_NOISE (DPM_Solver.sample_sde)
         for i in range(n):
             st = L.Stage()
             L.check(L.lib.dpm_plan_stage(self.handle, i, C.byref(st)))
@@ -159,7 +160,7 @@ def get_plan(self, precision=0, **kw):
     plan = self._plans.get(key)
     if plan is None:
         d = L.PlanDesc()
-        d.algorithm_type = self._algo
+        d.algorithm_type = L.ALGO_SDE_DPMSOLVERPP if kw.get("sde") else self._algo
         d.method = L.METHOD[kw["method"]]
         d.order = int(kw["order"])
         d.steps = int(kw["steps"])

@@ -39,6 +39,7 @@ from . import capture as _capture
 from . import loops as _loops
 from . import plan_cache as _plan_cache
 from . import pool as _pool
+from . import sde as _sde
 from . import updates as _updates
 from .capture import GraphedSample
 from .correctors import MaskBlend  # noqa: F401  (part of this module's namespace since round 2)
@@ -72,6 +73,8 @@ class DPM_Solver:
     # to know its network is a pure function of (x, t) on fixed tensors, as for torch.cuda.graph.  Calls with Python callbacks
     # (correcting_xt_fn, a callable correcting_x0_fn), return_intermediate or a host-side adaptive loop are never captured.
     auto_capture = 0
+    _noise_seed = None                       # sample_sde: the seed of the call in progress (dpm_launch_opts.noise_seed_*)
+    _sde_opts = None
 
     def __init__(self, model_fn, noise_schedule, algorithm_type="dpmsolver++", correcting_x0_fn=None,
                  correcting_xt_fn=None, thresholding_max_val=1., dynamic_thresholding_ratio=0.995,
@@ -135,6 +138,15 @@ class DPM_Solver:
     def _opts_ptr(self):
         """ctypes pointer to this solver's dpm_launch_opts, or None when everything is at its default"""
         key = (bool(self.cluster_in_graph), int(self.thr_spin_limit))
+        if self._noise_seed is not None:
+            seed = int(self._noise_seed)
+            hit = self._sde_opts
+            if hit is None or hit[0] != (key, seed):
+                o = L.LaunchOpts()
+                o.cluster_in_graph, o.thr_spin_limit = int(key[0]), key[1]
+                o.noise_seed_lo, o.noise_seed_hi = seed & 0xffffffff, seed >> 32
+                hit = self._sde_opts = ((key, seed), o, C.pointer(o))
+            return hit[2]
         if key == (False, 0):
             return None
         hit = getattr(self, "_opts_cache", None)
@@ -571,7 +583,8 @@ class DPM_Solver:
     _run_plan_group = _loops.run_plan_group
     _auto_captured = _capture.auto_captured
 
-    def _sample_plan(self, x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type):
+    def _sample_plan(self, x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type,
+                     sde=False):
         """The plan of a multistep / singlestep / singlestep_fixed `sample()` call, with the reference's argument checks and
         errors (shared by sample() and the request pool)."""
         if method == 'multistep':
@@ -608,7 +621,7 @@ class DPM_Solver:
         plan = self._get_plan(precision=self._precision(self._sdtype(x)), method=method, order=order, steps=steps,
                               skip_type=skip_type, solver_type=plan_solver_type,
                               lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
-                              t_T=float(t_T), t_0=float(t_0))
+                              t_T=float(t_T), t_0=float(t_0), **({"sde": True} if sde else {}))
         if plan_solver_type is not solver_type and any(st.form in (L.FORM_TWO, L.FORM_SS3T) for st in plan.stages):
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         return plan
@@ -651,6 +664,8 @@ class DPM_Solver:
             return x, intermediates
         else:
             return x
+
+    sample_sde = _sde.sample_sde
 
     def sample_requests(self, xs, **sample_kwargs):
         """(extension) `sample()` for several independent requests that are in flight together -- a server's batch of

@@ -53,11 +53,13 @@ extern "C" {
    table is this header's functions and nothing else.
    202 dpm_launch_opts.per_request_stages (was reserved[0]): dpm_stage_launch_multi with one stage record per request --
    requests at different positions of different plans in one fused launch (continuous batching).
+   203 DPM_ALGO_SDE_DPMSOLVERPP, DPM_F_NOISE and dpm_launch_opts.noise_seed_lo / _hi (were reserved[0..1]): SDE-DPM-Solver++
+   with its Gaussian term generated inside the stage kernel (see "noise contract" below; no struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 202
+#define DPM_HIP_VERSION 203
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -74,7 +76,10 @@ enum {
 };
 
 /* ---- enumerations (values are ABI) ----------------------------------------------------- */
-enum { DPM_ALGO_DPMSOLVER = 0, DPM_ALGO_DPMSOLVERPP = 1 };        /* algorithm_type, ref :342,:406 */
+enum { DPM_ALGO_DPMSOLVER = 0, DPM_ALGO_DPMSOLVERPP = 1,          /* algorithm_type, ref :342,:406 */
+       DPM_ALGO_SDE_DPMSOLVERPP = 2 /* version 203: the stochastic multistep DPM-Solver++ ("DPM++ 2M SDE", diffusers'
+                                       sde-dpmsolver++).  dpm_plan_create only (method multistep, order 1 or 2, fp32
+                                       scalars, no thresholding); the per-update coefficient builders reject it */ };
 enum { DPM_SOLVER_DPMSOLVER = 0, DPM_SOLVER_TAYLOR = 1 };         /* solver_type,    ref :611      */
 enum { DPM_METHOD_MULTISTEP = 0, DPM_METHOD_SINGLESTEP = 1, DPM_METHOD_SINGLESTEP_FIXED = 2 }; /* ref :1171,:1214 */
 enum { DPM_SKIP_TIME_UNIFORM = 0, DPM_SKIP_LOGSNR = 1, DPM_SKIP_TIME_QUADRATIC = 2 };          /* ref :468-478    */
@@ -105,6 +110,18 @@ enum {
 #define DPM_F_BLEND 32u     /* epilogue: x_out <- x_out*mask + (1-mask)*(blend_alpha*blend_a + blend_sigma*blend_b),
                                the mask blend DiffEdit / inpainting callers run as correcting_xt_fn after every
                                update (scripts/diffedit_inpaint.ipynb cell 6; hook: ref :1180,:1188,:1203,:1229)     */
+#define DPM_F_NOISE 64u     /* version 203, forms LIN1 / TWO only: out += c2 * z before the store rounding (and before a
+                               DPM_F_BLEND epilogue), z the standard normal of the noise contract below with counter
+                               dpm_stage.index and the seed of dpm_launch_opts.noise_seed_lo / _hi.  With thresholding,
+                               another form, a double state or device-resident coefficients: DPM_ERR_ARG.
+   Noise contract.  z of element i -- i = index in the flat, contiguous [B, C, H, W] order of the state -- depends on (seed,
+   stage index, i) only: not on the launch shape, tile mapping, dtype pair, kernel or the batch around it.
+     key = (seed lo, seed hi), counter = ((i >> 2) lo, (i >> 2) hi, stage index, 0); r[0..3] = Philox4x32-10(key, counter)
+     (Random123; zero key and counter give 6627e8d5 e169c58d bc57ac4c 9b00dbd8);
+     u(r) = ((r >> 9) + 0.5) * 2^-23: the 23 high bits, centred -- exact in fp32 and inside (0, 1) (24 bits + 0.5 would need
+     25 significant bits);  element i takes the pair p = (i & 3) >> 1:
+     z = sqrt(-2 ln u(r[2p])) * (i even ? cos : sin)(2 pi u(r[2p + 1]))
+     in fp32 (logf, sqrtf, the hardware sine / cosine of u in revolutions), the same device function on every route. */
 
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
@@ -165,7 +182,11 @@ typedef struct dpm_launch_opts {
                                workgroup finishes its sample alone; 0 = the default, 4096                             */
   int32_t per_request_stages; /* 1: dpm_stage_launch_multi reads `st` as an array of n_req stage records, request r is
                                advanced by st[r] (version 202; see there)                                             */
-  int32_t reserved[4];      /* zero                                                                                   */
+  uint32_t noise_seed_lo;   /* version 203: the 64-bit seed of DPM_F_NOISE stages (Philox key), low and high word (were */
+  uint32_t noise_seed_hi;   /* reserved[0..1]).  dpm_stage_launch_multi launches noise stages request by request, each  */
+                            /* with its own bs[r].opts seed; dpm_plan_run_multi hands request r its rbs[r].opts there;  */
+                            /* dpm_graph_create bakes the seed of rb->opts into the graph                              */
+  int32_t reserved[2];      /* zero                                                                                   */
 } dpm_launch_opts;
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
