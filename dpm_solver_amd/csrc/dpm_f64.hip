@@ -358,9 +358,7 @@ int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void
     if (blocks > 0x7fffffff) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: double state of %lld elements", (long long)b->n);
     launch(stage_kernel_f64, dim3((unsigned)blocks), dim3(256), 0, ctx, q, p, b->n);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("stage kernel launch failed");
 }
 
 int dpm_add_noise_f64(double alpha, double sigma, const void* x, const void* noise, void* out, int64_t n, void* stream) {
@@ -370,9 +368,7 @@ int dpm_add_noise_f64(double alpha, double sigma, const void* x, const void* noi
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL(add_noise_kernel_f64, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const double*>(x), static_cast<const double*>(noise), static_cast<double*>(out), n, alpha, sigma);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "add_noise launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("add_noise launch failed");
 }
 
 int dpm_blend_f64(const void* x, const void* mask, const void* a, const void* b, double alpha, double sigma, void* out, int64_t n,
@@ -384,7 +380,5 @@ int dpm_blend_f64(const void* x, const void* mask, const void* a, const void* b,
   hipLaunchKernelGGL(blend_kernel_f64, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const double*>(x), static_cast<const double*>(mask), static_cast<const double*>(a),
                      static_cast<const double*>(b), static_cast<double*>(out), n, period, alpha, sigma);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "blend launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("blend launch failed");
 }

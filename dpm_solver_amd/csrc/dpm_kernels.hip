@@ -118,12 +118,6 @@ int with_elem_type(int dtype, const char* what, F&& f) {
   }
   return dpm_set_error(DPM_ERR_UNSUPPORTED, "%s: unsupported dtype %d", what, dtype);
 }
-
-// the status of the kernels just launched: DPM_OK, or the launch error as "<what>: <HIP's text>"
-int launch_status(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? DPM_OK : dpm_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
-}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -203,23 +197,8 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
 }
 
 namespace {
-// May request r join a heterogeneous fused launch (stage_kernel_het)?  The stage- and buffer-level conditions of
-// launch_multi_typed, per request: a streaming stage of a fused form, no thresholding / blend / classifier guidance, the
-// evaluation state is the state, dense 16-byte-aligned buffers, a duplicate store only under classifier-free guidance.
-bool het_fusable(const dpm_stage& st, const dpm_buffers& b) {
-  const PairUnits* p = pair_of(b.state_dtype, b.eps_dtype);
-  if (!p || b.n <= 0 || b.n % EPT != 0) return false;
-  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE)) return false;
-  if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
-  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3) return false;
-  if (b.eps_stride && b.eps_stride != b.n / b.batch) return false;
-  if (!b.x || (b.xe && b.xe != b.x)) return false;
-  const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
-  if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
-  return aligned(b.x, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) && aligned(b.m_out, as) &&
-         aligned(b.e0, ae) && aligned(b.e1, ae);
-}
-// ... together with request 0 of its group: the fields that are template arguments or kernel-wide scalars
+// May a request that passes fusable_request (dpm_launch.hpp) join the heterogeneous fused launch (stage_kernel_het) of
+// request 0 of a group?  They must agree on the fields that are template arguments or kernel-wide scalars.
 bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b) {
   return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && b.n == b0.n && b.batch == b0.batch &&
          s.model_type == s0.model_type && s.guidance == s0.guidance && (s.flags & DPM_F_TO_X0) == (s0.flags & DPM_F_TO_X0);
@@ -238,9 +217,9 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
   for (int r0 = 0; r0 < n_req; ++r0) {
     if (done[r0]) continue;
     int cnt = 0;
-    if (fuse && het_fusable(st[r0], bs[r0])) {
+    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
       for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
-        if (!done[r] && het_fusable(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
           gs[cnt] = st[r];
           gb[cnt] = bs[r];
           gi[cnt++] = r;
@@ -704,9 +683,7 @@ extern "C" int dpm_adaptive_reset(dpm_adaptive* a, void* stream) {
   hipLaunchKernelGGL(adaptive_reset_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), a->dev, a->s0,
                      a->lambda_s0, a->lambda_0, (float)a->d.h_init, (float)a->d.t_end, (float)a->d.t_err, (float)a->d.theta,
                      a->d.order, a->status);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "adaptive_reset: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("adaptive_reset");
 }
 
 extern "C" int dpm_adaptive_begin(dpm_adaptive* a, void* x, void* x_prev, const void* x_lower, const void* x_higher, int64_t n,

@@ -68,6 +68,16 @@ inline KParams make_params(const dpm_stage* st) {
   return p;
 }
 
+// may this stage run a compile-time data-prediction prologue (SPEC_NOISE_X0, thresholding HOT 1)?  Only the data-prediction
+// form of a noise network (dpmsolver++: eps -> x0 by the invariant alpha) has one: x_start / v / score networks and an
+// alpha the division guard rejects take the general prologue.  The eps form (algorithm_type "dpmsolver") had one too until
+// round 5: with inputs from HBM the run-time prologue measures equal or faster on every eps-form launch (2M at cfg2 size
+// fp16 / fp32, the unconditional and the CFG singlestep-3 sampler at [64,3,256,256]; profiles/r05_kernel_budget.md).
+// Callers that honour Tuning::force_generic test it themselves.
+inline bool x0_prologue_ok(const dpm_stage& st) {
+  return st.model_type == DPM_MODEL_NOISE && (st.flags & DPM_F_TO_X0) && div_invariant_ok(st.alpha_e);
+}
+
 // cluster shape of the thresholding kernel: k workgroups per sample, `chunk` elements each.  Depends only on the
 // batch, the sample size and the CU count, so dpm_threshold_workspace_bytes() and the launch agree.
 struct ThrPlan {
@@ -141,9 +151,48 @@ void launch(K kern, dim3 grid, dim3 block, size_t lds, const LaunchCtx& c, Args.
     hipLaunchKernelGGL(kern, grid, block, lds, c.stream, args...);
 }
 
+// the status of the kernels just launched: DPM_OK, or the launch error as "<what>: <HIP's text>"
+inline int launch_status(const char* what) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? DPM_OK : dpm_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
+}
+
 // what a fused multi-request launcher returns -- without setting an error text -- when this stage (form, guidance,
 // prologue, buffers) has no fused variant: the caller then launches the requests one by one
 constexpr int MULTI_NOT_BUILT = -1000;
+
+// ---- the requests of a fused launch (stage_kernel_multi, stage_kernel_het, the multi-request stage_thresh_kernel)
+// a request the pointer tables can serve: the update starts from the state itself (x set, no separate evaluation state)
+// and the network output is dense (no channel slice)
+inline bool plain_request(const dpm_buffers& b) {
+  return b.x && (!b.xe || b.xe == b.x) && (!b.eps_stride || b.eps_stride == b.n / b.batch);
+}
+
+// May this request join a fused streaming launch?  A streaming stage of a fused form (no thresholding / blend / noise,
+// no classifier guidance), a plain request of whole 8-element groups, every buffer 16-byte aligned, a duplicate store
+// only under classifier-free guidance.  The element sizes come from the dtype codes: only 4- and 2-byte pairs fuse.
+inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE)) return false;
+  if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3) return false;
+  if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b)) return false;
+  const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
+  if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
+  return aligned(b.x, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) && aligned(b.m_out, as) &&
+         aligned(b.e0, ae) && aligned(b.e1, ae);
+}
+
+// request r's entry in a fused pointer table (MultiTab, HetArgs, ThrTab); the caller sets the rest (xo2, ws)
+template <typename Tab>
+void fill_request(Tab& t, int r, const dpm_buffers& b) {
+  t.x[r] = b.x;
+  t.e0[r] = b.e0;
+  t.e1[r] = b.e1;
+  t.h1[r] = b.h1;
+  t.h2[r] = b.h2;
+  t.xo[r] = b.x_out;
+  t.mo[r] = b.m_out;
+}
 
 // the operands of one single-request launch, typed: what both kernel families (streaming, thresholding) start from
 template <typename TS, typename TE>
@@ -182,6 +231,39 @@ struct Operands {
     use_ext = ext.xo2 || ext.mask || ext.eps_stride;
   }
 };
+
+// the KExt half of the vector kernels' 16-byte test: the extended vector kernel has no ragged tail and indexes whole
+// 8-element groups
+template <typename TS, typename TE>
+bool ext_vec_ok(const Operands<TS, TE>& op, const dpm_buffers* b) {
+  const size_t as = sizeof(TS) * EPT;
+  const KExt& ext = op.ext;
+  return !op.use_ext ||
+         (aligned(ext.xo2, as) && aligned(ext.mask, as) && aligned(ext.ba, as) && aligned(ext.bb, as) && b->n % EPT == 0 &&
+          ext.mask_period % EPT == 0 && (!ext.eps_stride || (ext.per_sample % EPT == 0 && ext.eps_stride % EPT == 0)));
+}
+
+// grid of the one-element-per-lane catch-all kernels (256 threads per workgroup, grid-stride loop)
+inline dim3 scalar_grid(int64_t n, int n_cu) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)n_cu * 16)); }
+
+struct Shape {
+  dim3 grid, block;
+};
+// launch shape of the streaming family's vector kernels (stage_kernel, stage_kernel_noise) at u tiles per iteration: one
+// 256-lane group per u tiles, capped per CU; two groups per workgroup (stage_kernel) when that still leaves two workgroups
+// per CU: what larger workgroups save is dispatches ([256,4,64,64]: 2048 -> 1024), and a small launch needs every CU more
+// than it needs that.  (One step below -- 512 tiles, SD's [64,4,64,64] -- 512 threads measure neutral inside the loop:
+// CFG + duplicate store 6.87-6.98 us against 7.00-7.02, the plain fp16 kernel 4.81-4.86 against 4.66-4.84;
+// profiles/r04_block_threads.md.)
+inline Shape stream_grid(int64_t n, int u, int n_cu, const Tuning& tn) {
+  const int64_t iters = ((n / EPT + 255) / 256 + u - 1) / u;
+  int bt = 256;
+  if (tn.block_threads > 0) bt = tn.block_threads;
+  else if (iters >= 4 * (int64_t)n_cu) bt = STAGE_MAX_THREADS;
+  const int64_t per = bt / 256;
+  const int64_t blocks = std::min((iters + per - 1) / per, std::max<int64_t>(1, (int64_t)n_cu * tn.blocks_per_cu / per));
+  return Shape{dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3((unsigned)bt)};
+}
 
 // ---- a thresholded stage (stage_thresh_kernel): cluster shape, select parameters, kernel flavour, the launch
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
@@ -226,7 +308,7 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   tp.chunk = (int32_t)pl.chunk;
   tp.k = (int32_t)pl.k;
   tp.batch = (int32_t)batch;
-  tp.fastdiv = st->model_type == DPM_MODEL_NOISE && (st->flags & DPM_F_TO_X0) && div_invariant_ok(st->alpha_e);
+  tp.fastdiv = x0_prologue_ok(*st);
   const size_t a4s = sizeof(TS) * 4, a4e = sizeof(TE) * 4;
   tp.vec = per_sample % 4 == 0 && ext.eps_stride % 4 == 0 && ext.mask_period % 4 == 0 && aligned(x, a4s) &&
            aligned(xe, a4s) && aligned(h1, a4s) && aligned(h2, a4s) && aligned(xo, a4s) && aligned(mo, a4s) &&
@@ -242,7 +324,7 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     tp.bpr = (int32_t)b->batch;
     for (int r = 0; r < stream.n_multi; ++r) {
       const dpm_buffers& q = stream.multi[r];
-      if (!q.x || (q.xe && q.xe != q.x) || q.x_out2 || (q.eps_stride && q.eps_stride != per_sample)) return MULTI_NOT_BUILT;
+      if (!plain_request(q) || q.x_out2) return MULTI_NOT_BUILT;
       if (pl.k > 1) {
         if (!q.workspace) return MULTI_NOT_BUILT;
         for (int r2 = 0; r2 < r; ++r2)
@@ -250,13 +332,7 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
       }
       tp.vec = tp.vec && aligned(q.x, a4s) && aligned(q.h1, a4s) && aligned(q.h2, a4s) && aligned(q.x_out, a4s) &&
                aligned(q.m_out, a4s) && aligned(q.e0, a4e) && aligned(q.e1, a4e);
-      tab_multi.x[r] = q.x;
-      tab_multi.e0[r] = q.e0;
-      tab_multi.e1[r] = q.e1;
-      tab_multi.h1[r] = q.h1;
-      tab_multi.h2[r] = q.h2;
-      tab_multi.xo[r] = q.x_out;
-      tab_multi.mo[r] = q.m_out;
+      fill_request(tab_multi, r, q);
       tab_multi.ws[r] = static_cast<uint32_t*>(q.workspace);
     }
   }
@@ -417,16 +493,12 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
       launch(kern, dim3((unsigned)grid), dim3(THR_THREADS), lds_bytes, stream, x, xe, e0, e1, g, h1, h2, xo, mo, p, tp, ext, tab);
       if (ch.ev && hipEventRecord(ch.ev, stream.stream) == hipSuccess) ch.recorded = true;
       t_dump(grid);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return dpm_set_error((int)e, "stage kernel launch failed: %s", hipGetErrorString(e));
-      return DPM_OK;
+      return launch_status("stage kernel launch failed");
     }
   }
   launch(kern, dim3((unsigned)grid), dim3(THR_THREADS), lds_bytes, stream, x, xe, e0, e1, g, h1, h2, xo, mo, p, tp, ext, tab);
   t_dump(grid);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("stage kernel launch failed");
 }
 
 // ---- a stage of the streaming family (stage_kernel / the one-element-per-lane catch-all): variant and launch shape
@@ -440,12 +512,8 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   const int n_cu = op.n_cu;
   const bool use_ext = op.use_ext;
   const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
-  bool vec = aligned(x, as) && aligned(xe, as) && aligned(h1, as) && aligned(h2, as) && aligned(xo, as) &&
-             aligned(mo, as) && aligned(e0, ae) && aligned(e1, ae) && aligned(g, ae);
-  if (use_ext)  // the extended vector kernel has no ragged tail and indexes whole 8-element groups
-    vec = vec && aligned(ext.xo2, as) && aligned(ext.mask, as) && aligned(ext.ba, as) && aligned(ext.bb, as) &&
-          b->n % EPT == 0 && ext.mask_period % EPT == 0 &&
-          (!ext.eps_stride || (ext.per_sample % EPT == 0 && ext.eps_stride % EPT == 0));
+  const bool vec = aligned(x, as) && aligned(xe, as) && aligned(h1, as) && aligned(h2, as) && aligned(xo, as) &&
+                   aligned(mo, as) && aligned(e0, ae) && aligned(e1, ae) && aligned(g, ae) && ext_vec_ok(op, b);
   // what the streaming family instantiates (binary size, build time and first-call cost: one kernel per combination and
   // dtype pair).  Round 5 measured what a compile-time prologue is worth against the run-time one (SPEC_GENERIC: the mode is
   // chosen once per workgroup iteration, the same straight-line code) -- 0-7 % per launch, profiles/r05_kernel_budget.md --
@@ -476,50 +544,25 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
                               (FORM == DPM_FORM_SS3T && XE));  // the launches of the adaptive solver's device-side controller
   const bool dyn_vec = stream.dyn && DYN_BUILT && !use_ext;
   if (!vec || !COMBO_BUILT || (stream.dyn && !dyn_vec) || (use_ext && !EXT_BUILT)) {
-    int64_t blocks = (b->n + 255) / 256;
-    const int64_t cap = (int64_t)n_cu * 16;
-    if (blocks > cap) blocks = cap;
     using ScalarKernel = decltype(&stage_kernel_scalar<TS, TE, false>);  // the DYN = true variant has the same signature
     const void* k = stream.dyn ? dpm_catchall_scalar<TS, TE, true>() : dpm_catchall_scalar<TS, TE, false>();
-    launch(reinterpret_cast<ScalarKernel>(const_cast<void*>(k)), dim3((unsigned)blocks), dim3(256), 0, stream, x, xe ? xe : x,
-           e0, e1, g, h1, h2, xo, mo, b->n, p, ext, stream.dyn, stream.skip);
+    launch(reinterpret_cast<ScalarKernel>(const_cast<void*>(k)), scalar_grid(b->n, n_cu), dim3(256), 0, stream, x,
+           xe ? xe : x, e0, e1, g, h1, h2, xo, mo, b->n, p, ext, stream.dyn, stream.skip);
   } else if constexpr (COMBO_BUILT) {
     const Tuning tn = tuning_for(b->opts);
-    // the compile-time prologue exists for the data-prediction form of a noise network (dpmsolver++: eps -> x0 by the
-    // invariant alpha) only.  The eps form (algorithm_type "dpmsolver") had one too until round 5: with inputs from HBM the
-    // run-time prologue measures equal or faster on every eps-form launch (2M at cfg2 size fp16 / fp32, the unconditional
-    // and the CFG singlestep-3 sampler at [64,3,256,256]; profiles/r05_kernel_budget.md), so it takes SPEC_GENERIC now
-    const bool noise = SPEC_BUILT && !stream.dyn && !tn.force_generic && st->model_type == DPM_MODEL_NOISE &&
-                       (st->flags & DPM_F_TO_X0) && div_invariant_ok(st->alpha_e);
+    const bool noise = SPEC_BUILT && !stream.dyn && !tn.force_generic && x0_prologue_ok(*st);
     const int spec = noise ? SPEC_NOISE_X0 : SPEC_GENERIC;
-    const int64_t ntiles = ((b->n / EPT) + 255) / 256;
-    const bool big = ntiles >= 4 * (int64_t)n_cu;  // two tiles per iteration only when there is work for it
-    // launch shape: one 256-lane group per U tiles, capped per CU; two groups per workgroup (stage_kernel) when that still
-    // leaves two workgroups per CU: what larger workgroups save is dispatches ([256,4,64,64]: 2048 -> 1024), and a small
-    // launch needs every CU more than it needs that.  (One step below -- 512 tiles, SD's [64,4,64,64] -- 512 threads measure
-    // neutral inside the loop: CFG + duplicate store 6.87-6.98 us against 7.00-7.02, the plain fp16 kernel 4.81-4.86 against
-    // 4.66-4.84; profiles/r04_block_threads.md.)
-    auto shape_for = [&](int u) {
-      const int64_t iters = (ntiles + u - 1) / u;
-      int bt = 256;
-      if (tn.block_threads > 0) bt = tn.block_threads;
-      else if (iters >= 4 * (int64_t)n_cu) bt = STAGE_MAX_THREADS;
-      const int64_t per = bt / 256;
-      int64_t blocks = (iters + per - 1) / per;
-      const int64_t cap = std::max<int64_t>(1, (int64_t)n_cu * tn.blocks_per_cu / per);
-      if (blocks > cap) blocks = cap;
-      return std::make_pair(dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3((unsigned)bt));
-    };
-#define DPM_LAUNCH(SPEC_, U_, NT_, EXT_)                                                                                 \
-  do {                                                                                                                   \
-    const auto sh_ = shape_for(U_);                                                                                      \
-    launch(stage_kernel<TS, TE, FORM, GUIDE, XE, SPEC_, U_, NT_, EXT_>, sh_.first, sh_.second, 0, stream, x, xe, e0, e1, \
-           g, h1, h2, xo, mo, b->n, p, ext, stream.dyn, stream.skip);                                                    \
+    const bool big = (b->n / EPT + 255) / 256 >= 4 * (int64_t)n_cu;  // two tiles per iteration only when there is work for it
+#define DPM_LAUNCH(SPEC_, U_, NT_, EXT_)                                                                               \
+  do {                                                                                                                 \
+    const Shape sh_ = stream_grid(b->n, U_, n_cu, tn);                                                                 \
+    launch(stage_kernel<TS, TE, FORM, GUIDE, XE, SPEC_, U_, NT_, EXT_>, sh_.grid, sh_.block, 0, stream, x, xe, e0, e1, \
+           g, h1, h2, xo, mo, b->n, p, ext, stream.dyn, stream.skip);                                                  \
   } while (0)
     if (dyn_vec) {
       if constexpr (DYN_BUILT) {
-        const auto sh = shape_for(1);
-        launch(stage_kernel<TS, TE, FORM, GUIDE, XE, SPEC_GENERIC, 1, DefNT<TS>::value, false, true>, sh.first, sh.second, 0,
+        const Shape sh = stream_grid(b->n, 1, n_cu, tn);
+        launch(stage_kernel<TS, TE, FORM, GUIDE, XE, SPEC_GENERIC, 1, DefNT<TS>::value, false, true>, sh.grid, sh.block, 0,
                stream, x, xe, e0, e1, g, h1, h2, xo, mo, b->n, p, ext, stream.dyn, stream.skip);
       }
     } else if (use_ext) {
@@ -575,8 +618,8 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
           if constexpr (sizeof(TS) == 2 && sizeof(TE) == 2) dma = (tn.lds_dma < 0 ? DPM_LDS_DMA_DEFAULT : tn.lds_dma) != 0 && b->n % EPT == 0;
           if (dma) {
             if constexpr (sizeof(TS) == 2 && sizeof(TE) == 2) {
-              const auto sh = shape_for(1);
-              launch(stage_kernel_dma<TS, TE, FORM, CNT>, sh.first, sh.second, (size_t)(sh.second.x / 64) * 3072, stream, x, e0, h1, xo, mo,
+              const Shape sh = stream_grid(b->n, 1, n_cu, tn);
+              launch(stage_kernel_dma<TS, TE, FORM, CNT>, sh.grid, sh.block, (size_t)(sh.block.x / 64) * 3072, stream, x, e0, h1, xo, mo,
                      b->n, p);
             }
           }
@@ -589,9 +632,7 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     }
 #undef DPM_LAUNCH
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("stage kernel launch failed");
 }
 
 // ---- an SDE stage (DPM_F_NOISE; checked by the caller: LIN1 / TWO, no thresholding, no device-resident coefficients):
@@ -608,31 +649,19 @@ int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& str
   const KExt& ext = op.ext;
   const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
   constexpr bool BUILT = (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO) && GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
-  bool vec = BUILT && b->n % EPT == 0 && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.xo, as) && aligned(op.mo, as) &&
-             aligned(op.e0, ae) && aligned(op.e1, ae);
-  if (op.use_ext)
-    vec = vec && aligned(ext.xo2, as) && aligned(ext.mask, as) && aligned(ext.ba, as) && aligned(ext.bb, as) &&
-          ext.mask_period % EPT == 0 && (!ext.eps_stride || (ext.per_sample % EPT == 0 && ext.eps_stride % EPT == 0));
+  const bool vec = BUILT && b->n % EPT == 0 && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.xo, as) &&
+                   aligned(op.mo, as) && aligned(op.e0, ae) && aligned(op.e1, ae) && ext_vec_ok(op, b);
   if (!vec) {
-    int64_t blocks = (b->n + 255) / 256;
-    const int64_t cap = (int64_t)op.n_cu * 16;
-    if (blocks > cap) blocks = cap;
     using ScalarNoise = decltype(&stage_kernel_scalar_noise<TS, TE>);
-    launch(reinterpret_cast<ScalarNoise>(const_cast<void*>(dpm_catchall_scalar_noise<TS, TE>())), dim3((unsigned)blocks), dim3(256),
-           0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, nz);
+    launch(reinterpret_cast<ScalarNoise>(const_cast<void*>(dpm_catchall_scalar_noise<TS, TE>())), scalar_grid(b->n, op.n_cu),
+           dim3(256), 0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, nz);
   } else if constexpr (BUILT) {
     const Tuning tn = tuning_for(b->opts);
-    const bool x0 = !tn.force_generic && st->model_type == DPM_MODEL_NOISE && (st->flags & DPM_F_TO_X0) && div_invariant_ok(st->alpha_e);
-    // the launch shape of stage_kernel with one tile per iteration (launch_stream: shape_for(1))
-    const int64_t ntiles = ((b->n / EPT) + 255) / 256;
-    const int bt = tn.block_threads > 0 ? tn.block_threads : (ntiles >= 4 * (int64_t)op.n_cu ? STAGE_MAX_THREADS : 256);
-    const int64_t per = bt / 256;
-    int64_t blocks = (ntiles + per - 1) / per;
-    const int64_t cap = std::max<int64_t>(1, (int64_t)op.n_cu * tn.blocks_per_cu / per);
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)(blocks < 1 ? 1 : blocks)), block((unsigned)bt);
-#define DPM_NOISE_LAUNCH(SPEC_, EXT_) \
-  launch(stage_kernel_noise<TS, TE, FORM, GUIDE, SPEC_, EXT_>, grid, block, 0, stream, op.x, op.e0, op.e1, op.h1, op.xo, op.mo, b->n, p, ext, nz)
+    const bool x0 = !tn.force_generic && x0_prologue_ok(*st);
+    const Shape sh = stream_grid(b->n, 1, op.n_cu, tn);  // stage_kernel's, one tile per iteration
+#define DPM_NOISE_LAUNCH(SPEC_, EXT_)                                                                                   \
+  launch(stage_kernel_noise<TS, TE, FORM, GUIDE, SPEC_, EXT_>, sh.grid, sh.block, 0, stream, op.x, op.e0, op.e1, op.h1, \
+         op.xo, op.mo, b->n, p, ext, nz)
     if (op.use_ext) {
       if (x0) DPM_NOISE_LAUNCH(SPEC_NOISE_X0, true);
       else DPM_NOISE_LAUNCH(SPEC_GENERIC, true);
@@ -642,9 +671,7 @@ int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& str
     }
 #undef DPM_NOISE_LAUNCH
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "noise stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("noise stage kernel launch failed");
 }
 
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
@@ -671,41 +698,47 @@ struct MultiShape {
   static constexpr int THREADS = 256;  // per workgroup (256 / 512: stage_kernel_multi)
 };
 
+struct FusedShape {
+  dim3 grid, block;
+  uint32_t spr;       // super-tiles (u tiles of one request) per request
+  uint32_t xcd_span;  // != 0: super-tiles per XCD of the XCD-contiguous remap (stage_kernel_multi)
+};
+// the fused kernels' launch shape for n_req requests of n elements at u tiles per super-tile: one super-tile per 256-lane
+// group, XCD-contiguous super-tiles for 2-byte states (Tuning::multi_xcd_remap).  `capped`: the kernel loops over its
+// super-tiles (stage_kernel_multi), so the multi_blocks_per_cu tuning hook may cap the grid; stage_kernel_het has no such
+// loop and always gets the whole grid.
+template <typename TS, typename TE>
+FusedShape fused_grid(int64_t n, int n_req, int u, const Tuning& tn, bool capped) {
+  const int64_t spr = ((n / EPT + 255) / 256 + u - 1) / u;
+  const int64_t groups = spr * n_req;  // 256-lane groups of work: one super-tile each
+  const int bt = tn.block_threads > 0 ? tn.block_threads : MultiShape<TS, TE>::THREADS;
+  const int64_t per = bt / 256;
+  const bool remap = tn.multi_xcd_remap < 0 ? sizeof(TS) == 2 : tn.multi_xcd_remap != 0;
+  const uint32_t span = remap ? (uint32_t)((groups + 7) / 8) : 0u;
+  int64_t blocks = span ? 8 * (((int64_t)span + per - 1) / per) : (groups + per - 1) / per;
+  if (capped && tn.multi_blocks_per_cu > 0) {
+    const DeviceInfo& di = device_info();
+    blocks = std::min(blocks, (int64_t)(di.n_cu > 0 ? di.n_cu : 256) * tn.multi_blocks_per_cu);
+  }
+  return FusedShape{dim3((unsigned)blocks), dim3((unsigned)bt), (uint32_t)spr, span};
+}
+
 // ---- fused multi-request launch of the streaming family (stage_kernel_multi); thresholded stages fuse inside
 // launch_typed (LaunchCtx::multi)
 template <typename TS, typename TE, int FORM, int GUIDE, int SPEC>
 int launch_multi_spec(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
-  const DeviceInfo& di = device_info();
-  const int n_cu = di.n_cu > 0 ? di.n_cu : 256;
   const Tuning tn = tuning_for(bs[0].opts);
   MultiTab tab;
   std::memset(&tab, 0, sizeof tab);
   for (int r = 0; r < n_req; ++r) {
-    tab.x[r] = bs[r].x ? bs[r].x : bs[r].xe;
-    tab.e0[r] = bs[r].e0;
-    tab.e1[r] = bs[r].e1;
-    tab.h1[r] = bs[r].h1;
-    tab.h2[r] = bs[r].h2;
-    tab.xo[r] = bs[r].x_out;
-    tab.mo[r] = bs[r].m_out;
+    fill_request(tab, r, bs[r]);
     tab.xo2[r] = bs[r].x_out2;
   }
   const KParams p = make_params(st);
   const int64_t n = bs[0].n;
-  const int64_t ntiles = ((n / EPT) + 255) / 256;
   auto go = [&](auto kern, int u) {
-    const int64_t spr = (ntiles + u - 1) / u;
-    const int64_t groups = spr * n_req;                     // 256-lane groups of work: one super-tile each
-    const int bt = tn.block_threads > 0 ? tn.block_threads : MultiShape<TS, TE>::THREADS;
-    const int64_t per = bt / 256;
-    const bool remap = tn.multi_xcd_remap < 0 ? sizeof(TS) == 2 : tn.multi_xcd_remap != 0;
-    const uint32_t span = remap ? (uint32_t)((groups + 7) / 8) : 0u;   // super-tiles per XCD
-    int64_t blocks = span ? 8 * (((int64_t)span + per - 1) / per) : (groups + per - 1) / per;
-    if (tn.multi_blocks_per_cu > 0) {  // tuning hook: cap the grid, workgroups loop over the super-tiles
-      const int64_t cap = (int64_t)n_cu * tn.multi_blocks_per_cu;
-      if (blocks > cap) blocks = cap;
-    }
-    launch(kern, dim3((unsigned)blocks), dim3((unsigned)bt), 0, c, tab, n, (uint32_t)n_req, (uint32_t)spr, p, span);
+    const FusedShape sh = fused_grid<TS, TE>(n, n_req, u, tn, true);
+    launch(kern, sh.grid, sh.block, 0, c, tab, n, (uint32_t)n_req, sh.spr, p, sh.xcd_span);
   };
   constexpr int DU = MultiShape<TS, TE>::U, DN = MultiShape<TS, TE>::NT;
 #ifdef DPM_TUNING_VARIANTS  // tools/tune.py multi: every (tiles per iteration, nt mask) of the 2M kernel
@@ -721,42 +754,22 @@ int launch_multi_spec(const dpm_stage* st, const dpm_buffers* bs, int n_req, con
         case 16 + 5: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, 2, 5>, 2); break;
         default: go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, DU, DN>, DU); break;
       }
-      hipError_t e2 = hipGetLastError();
-      if (e2 != hipSuccess) return dpm_set_error((int)e2, "fused stage kernel launch failed: %s", hipGetErrorString(e2));
-      return DPM_OK;
+      return launch_status("fused stage kernel launch failed");
     }
   }
 #endif
   go(stage_kernel_multi<TS, TE, FORM, GUIDE, SPEC, DU, DN>, DU);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "fused stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("fused stage kernel launch failed");
 }
 
-// every request of the group: same stage, n, batch, dtypes (checked by the caller); here: is there a fused variant, and
-// do all buffers allow 16-byte accesses?
+// every request of the group: same stage, n, batch, dtypes (checked by the caller); here: does every request pass
+// fusable_request, and which prologue runs
 template <typename TS, typename TE>
 int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
-  if (st->flags & (DPM_F_THRESH | DPM_F_BLEND)) return MULTI_NOT_BUILT;
-  if (st->guidance == DPM_GUIDE_CLASSIFIER) return MULTI_NOT_BUILT;
-  if (st->form != DPM_FORM_LIN1 && st->form != DPM_FORM_TWO && st->form != DPM_FORM_MS3) return MULTI_NOT_BUILT;
-  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
-  if (bs[0].n % EPT != 0) return MULTI_NOT_BUILT;
-  for (int r = 0; r < n_req; ++r) {
-    const dpm_buffers& b = bs[r];
-    if (b.eps_stride && b.eps_stride != b.n / b.batch) return MULTI_NOT_BUILT;
-    if (b.x_out2 && (st->guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return MULTI_NOT_BUILT;
-    if (b.xe && b.x && b.xe != b.x) return MULTI_NOT_BUILT;
-    if (!(aligned(b.x, as) && aligned(b.xe, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) &&
-          aligned(b.m_out, as) && aligned(b.e0, ae) && aligned(b.e1, ae)))
-      return MULTI_NOT_BUILT;
-  }
-  const bool x0 = (st->flags & DPM_F_TO_X0) != 0;
+  for (int r = 0; r < n_req; ++r)
+    if (!fusable_request(*st, bs[r])) return MULTI_NOT_BUILT;
   const bool cfg = st->guidance == DPM_GUIDE_CFG;
-  // x_start / v / score networks (and an alpha the division-by-invariant guard rejects) take the general prologue
-  // ... and so does the eps form of a noise network (launch_stream: no compile-time prologue of its own since round 5)
-  const bool generic = st->model_type != DPM_MODEL_NOISE || !x0 || !div_invariant_ok(st->alpha_e) ||
-                       tuning_for(bs[0].opts).force_generic != 0;
+  const bool generic = !x0_prologue_ok(*st) || tuning_for(bs[0].opts).force_generic != 0;
 #define DPM_MULTI(FORM_)                                                                                        \
   (generic ? (cfg ? launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_GENERIC>(st, bs, n_req, c)             \
                   : launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_GENERIC>(st, bs, n_req, c))           \
@@ -771,22 +784,13 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
 }
 
 // ---- heterogeneous fused launch (stage_kernel_het): request r advanced by st[r].  The caller (dpm_kernels.hip) has
-// grouped the requests: every one passes het_fusable, and they agree on dtypes, n, batch, model type, guidance kind and
-// DPM_F_TO_X0.  Here: the prologue (compile-time only when every request's alpha passes the division guard), the
-// smallest form set that covers the group, the launch shape of the lockstep kernel (MultiShape, XCD-contiguous remap).
+// grouped the requests: every one passes fusable_request, and they agree on dtypes, n, batch, model type, guidance kind
+// and DPM_F_TO_X0.  Here: the prologue (compile-time only when every request may run it), the smallest form set that
+// covers the group, the launch shape of the lockstep kernel (MultiShape, XCD-contiguous remap).
 template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC>
-void launch_het_spec(HetArgs& a, const Tuning& tn, const LaunchCtx& c) {
-  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT;
-  const int64_t ntiles = ((a.n / EPT) + 255) / 256;
-  const int64_t spr = (ntiles + U - 1) / U;
-  const int64_t groups = spr * a.nreq;  // 256-lane groups of work: one super-tile each, no grid-stride loop
-  const int bt = tn.block_threads > 0 ? tn.block_threads : MultiShape<TS, TE>::THREADS;
-  const int64_t per = bt / 256;
-  const bool remap = tn.multi_xcd_remap < 0 ? sizeof(TS) == 2 : tn.multi_xcd_remap != 0;
-  a.spr = (uint32_t)spr;
-  a.xcd_span = remap ? (uint32_t)((groups + 7) / 8) : 0u;
-  const int64_t blocks = a.xcd_span ? 8 * (((int64_t)a.xcd_span + per - 1) / per) : (groups + per - 1) / per;
-  launch(stage_kernel_het<TS, TE, FORMS, GUIDE, SPEC, U, NT>, dim3((unsigned)blocks), dim3((unsigned)bt), 0, c, a);
+void launch_het_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
+  launch(stage_kernel_het<TS, TE, FORMS, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c,
+         a);
 }
 
 template <typename TS, typename TE>
@@ -797,35 +801,29 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
   HetArgs a;
   std::memset(&a, 0, sizeof a);
   bool ms3 = false;
-  bool noise = st[0].model_type == DPM_MODEL_NOISE && (st[0].flags & DPM_F_TO_X0) && !tn.force_generic;
+  bool noise = !tn.force_generic;
   for (int r = 0; r < n_req; ++r) {
-    const dpm_buffers& b = bs[r];
-    a.x[r] = b.x ? b.x : b.xe;
-    a.e0[r] = b.e0;
-    a.e1[r] = b.e1;
-    a.h1[r] = b.h1;
-    a.h2[r] = b.h2;
-    a.xo[r] = b.x_out;
-    a.mo[r] = b.m_out;
-    a.xo2[r] = b.x_out2;
+    fill_request(a, r, bs[r]);
+    a.xo2[r] = bs[r].x_out2;
     a.p[r] = make_params(&st[r]);
     ms3 = ms3 || st[r].form == DPM_FORM_MS3;
-    noise = noise && div_invariant_ok(st[r].alpha_e);
+    noise = noise && x0_prologue_ok(st[r]);
   }
+  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, MultiShape<TS, TE>::U, tn, false);
   a.n = bs[0].n;
   a.nreq = (uint32_t)n_req;
+  a.spr = sh.spr;
+  a.xcd_span = sh.xcd_span;
   const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
 #define DPM_HET(FS_)                                                                                            \
-  (noise ? (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, tn, c)                         \
-                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, tn, c))                       \
-         : (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_GENERIC>(a, tn, c)                          \
-                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_GENERIC>(a, tn, c)))
+  (noise ? (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, sh, c)                         \
+                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, sh, c))                       \
+         : (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_GENERIC>(a, sh, c)                          \
+                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_GENERIC>(a, sh, c)))
   if (ms3) DPM_HET(HET_FORMS_3);
   else DPM_HET(HET_FORMS_2);
 #undef DPM_HET
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return dpm_set_error((int)e, "fused stage kernel launch failed: %s", hipGetErrorString(e));
-  return DPM_OK;
+  return launch_status("fused stage kernel launch failed");
 }
 
 template <typename TS, typename TE, int FORM, int GUIDE>

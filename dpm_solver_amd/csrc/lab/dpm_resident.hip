@@ -132,8 +132,8 @@ extern "C" int dpm_resident_create(const dpm_stage* stages, const dpm_buffers* b
     const dpm_stage& st = stages[s];
     const dpm_buffers& b = bufs[s];
     const bool ok = (st.form == DPM_FORM_TWO || st.form == DPM_FORM_LIN1) && st.guidance == DPM_GUIDE_NONE &&
-                    st.model_type == DPM_MODEL_NOISE && (st.flags & DPM_F_TO_X0) && !(st.flags & (DPM_F_THRESH | DPM_F_BLEND)) &&
-                    (!b.xe || b.xe == b.x) && b.state_dtype == b.eps_dtype && b.n % (EPT * 256) == 0 && div_invariant_ok(st.alpha_e) &&
+                    x0_prologue_ok(st) && !(st.flags & (DPM_F_THRESH | DPM_F_BLEND)) && (!b.xe || b.xe == b.x) &&
+                    b.state_dtype == b.eps_dtype && b.n % (EPT * 256) == 0 &&
                     (b.state_dtype == DPM_DTYPE_F16 || b.state_dtype == DPM_DTYPE_F32);
     if (!ok) {
       delete r;  // (no device allocation yet)
