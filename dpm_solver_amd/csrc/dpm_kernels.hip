@@ -144,8 +144,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused
   // family does not build (thresholding, mask blend, classifier guidance, SS3T / DENOISE, unaligned or strided operands)
-  // come back MULTI_NOT_BUILT and take the single-request path below.  SDE stages (DPM_F_NOISE) never take it: the fused
-  // kernel has no noise epilogue.
+  // come back MULTI_NOT_BUILT and take the single-request path below.  SDE stages (DPM_F_NOISE) do not take it: a lone SDE
+  // stage keeps stage_kernel_noise (the fused noise kernels serve dpm_stage_launch_multi).
   if (!dyn && !(st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))) {
     const int big = tuning_for(bb.opts).big_tiles;
     if (big > 0 && (bb.n / EPT + 255) / 256 >= big) {
@@ -174,8 +174,8 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
   // a group fuses when its requests agree in size and dtypes and each one passes the single launch's checks; otherwise
   // every request is launched on its own (and reports its own error)
   const PairUnits* p = pair_of(bs[0].state_dtype, bs[0].eps_dtype);
-  // SDE stages are launched request by request, each with the seed of its own bs[r].opts
-  bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0 && !(st->flags & DPM_F_NOISE);
+  // (SDE stages fuse like the others: stage_kernel_multi_noise, each request with the seed of its own bs[r].opts)
+  bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0;
   for (int r = 0; r < n_req && fuse; ++r)
     fuse = bs[r].n == bs[0].n && bs[r].batch == bs[0].batch && bs[r].state_dtype == bs[0].state_dtype &&
            bs[r].eps_dtype == bs[0].eps_dtype && check_stage_buffers(st, &bs[r], false) == DPM_OK;
@@ -201,7 +201,8 @@ namespace {
 // request 0 of a group?  They must agree on the fields that are template arguments or kernel-wide scalars.
 bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b) {
   return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && b.n == b0.n && b.batch == b0.batch &&
-         s.model_type == s0.model_type && s.guidance == s0.guidance && (s.flags & DPM_F_TO_X0) == (s0.flags & DPM_F_TO_X0);
+         s.model_type == s0.model_type && s.guidance == s0.guidance &&
+         (s.flags & (DPM_F_TO_X0 | DPM_F_NOISE)) == (s0.flags & (DPM_F_TO_X0 | DPM_F_NOISE));  // SDE stages apart from ODE ones
 }
 
 // dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to

@@ -168,18 +168,32 @@ inline bool plain_request(const dpm_buffers& b) {
   return b.x && (!b.xe || b.xe == b.x) && (!b.eps_stride || b.eps_stride == b.n / b.batch);
 }
 
-// May this request join a fused streaming launch?  A streaming stage of a fused form (no thresholding / blend / noise,
-// no classifier guidance), a plain request of whole 8-element groups, every buffer 16-byte aligned, a duplicate store
-// only under classifier-free guidance.  The element sizes come from the dtype codes: only 4- and 2-byte pairs fuse.
+// May this request join a fused streaming launch?  A streaming stage of a fused form (no thresholding / blend, no
+// classifier guidance, no device-resident coefficients: the fused launchers take none), a plain request of whole 8-element
+// groups, every buffer 16-byte aligned, a duplicate store only under classifier-free guidance.  The element sizes come from
+// the dtype codes: only 4- and 2-byte pairs fuse.  SDE stages (DPM_F_NOISE) fuse too, with kernels of their own
+// (stage_kernel_multi_noise, stage_kernel_het_noise: LIN1 / TWO); the callers keep them apart from the ODE stages.
 inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
-  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE)) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND)) return false;
   if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
-  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3) return false;
+  const bool ms3_ok = !(st.flags & DPM_F_NOISE);
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && !(ms3_ok && st.form == DPM_FORM_MS3)) return false;
   if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b)) return false;
   const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
   if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
   return aligned(b.x, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) && aligned(b.m_out, as) &&
          aligned(b.e0, ae) && aligned(b.e1, ae);
+}
+
+// the generator's parameters of one request's SDE stage: the seed from the request's own dpm_launch_opts (none: seed 0),
+// the Philox counter word = the stage index, the scale = the stage's c2
+inline KNoise noise_of(const dpm_stage& st, const dpm_buffers& b) {
+  KNoise nz;
+  nz.key0 = b.opts ? b.opts->noise_seed_lo : 0u;
+  nz.key1 = b.opts ? b.opts->noise_seed_hi : 0u;
+  nz.ctr = (uint32_t)st.index;
+  nz.scale = st.c2;
+  return nz;
 }
 
 // request r's entry in a fused pointer table (MultiTab, HetArgs, ThrTab); the caller sets the rest (xo2, ws)
@@ -640,11 +654,7 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
 // comes from the call's dpm_launch_opts, the Philox counter is the stage index, the scale the stage's c2.
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
 int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
-  KNoise nz;
-  nz.key0 = b->opts ? b->opts->noise_seed_lo : 0u;
-  nz.key1 = b->opts ? b->opts->noise_seed_hi : 0u;
-  nz.ctr = (uint32_t)st->index;
-  nz.scale = st->c2;
+  const KNoise nz = noise_of(*st, *b);
   const KParams& p = op.p;
   const KExt& ext = op.ext;
   const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
@@ -762,6 +772,29 @@ int launch_multi_spec(const dpm_stage* st, const dpm_buffers* bs, int n_req, con
   return launch_status("fused stage kernel launch failed");
 }
 
+// ---- the same for an SDE stage (stage_kernel_multi_noise): MultiShape's tiles and cache policy, the whole grid (the
+// kernel has no loop over super-tiles), every request's Philox key from its own bs[r].opts
+template <typename TS, typename TE, int FORM, int GUIDE, int SPEC>
+int launch_multi_noise_spec(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
+  const Tuning tn = tuning_for(bs[0].opts);
+  MultiTab tab;
+  MultiKeys keys;
+  std::memset(&tab, 0, sizeof tab);
+  std::memset(&keys, 0, sizeof keys);
+  for (int r = 0; r < n_req; ++r) {
+    fill_request(tab, r, bs[r]);
+    tab.xo2[r] = bs[r].x_out2;
+    const KNoise nz = noise_of(*st, bs[r]);
+    keys.k0[r] = nz.key0;
+    keys.k1[r] = nz.key1;
+  }
+  constexpr int U = MultiShape<TS, TE>::U;
+  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  launch(stage_kernel_multi_noise<TS, TE, FORM, GUIDE, SPEC, U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, tab, keys,
+         bs[0].n, (uint32_t)n_req, sh.spr, make_params(st), sh.xcd_span, (uint32_t)st->index, st->c2);
+  return launch_status("fused noise stage kernel launch failed");
+}
+
 // every request of the group: same stage, n, batch, dtypes (checked by the caller); here: does every request pass
 // fusable_request, and which prologue runs
 template <typename TS, typename TE>
@@ -770,6 +803,15 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
     if (!fusable_request(*st, bs[r])) return MULTI_NOT_BUILT;
   const bool cfg = st->guidance == DPM_GUIDE_CFG;
   const bool generic = !x0_prologue_ok(*st) || tuning_for(bs[0].opts).force_generic != 0;
+  if (st->flags & DPM_F_NOISE) {
+#define DPM_MULTI_NOISE(FORM_)                                                                                        \
+  (generic ? (cfg ? launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_GENERIC>(st, bs, n_req, c)             \
+                  : launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_GENERIC>(st, bs, n_req, c))           \
+   : cfg   ? launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(st, bs, n_req, c)                   \
+           : launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(st, bs, n_req, c))
+    return st->form == DPM_FORM_LIN1 ? DPM_MULTI_NOISE(DPM_FORM_LIN1) : DPM_MULTI_NOISE(DPM_FORM_TWO);
+#undef DPM_MULTI_NOISE
+  }
 #define DPM_MULTI(FORM_)                                                                                        \
   (generic ? (cfg ? launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_GENERIC>(st, bs, n_req, c)             \
                   : launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_GENERIC>(st, bs, n_req, c))           \
@@ -784,8 +826,8 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
 }
 
 // ---- heterogeneous fused launch (stage_kernel_het): request r advanced by st[r].  The caller (dpm_kernels.hip) has
-// grouped the requests: every one passes fusable_request, and they agree on dtypes, n, batch, model type, guidance kind
-// and DPM_F_TO_X0.  Here: the prologue (compile-time only when every request may run it), the smallest form set that
+// grouped the requests: every one passes fusable_request, and they agree on dtypes, n, batch, model type, guidance kind,
+// DPM_F_TO_X0 and DPM_F_NOISE (a group of SDE stages takes stage_kernel_het_noise, each request with its own KNoise).  Here: the prologue (compile-time only when every request may run it), the smallest form set that
 // covers the group, the launch shape of the lockstep kernel (MultiShape, XCD-contiguous remap).
 template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC>
 void launch_het_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
@@ -793,19 +835,27 @@ void launch_het_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c)
          a);
 }
 
+template <typename TS, typename TE, int GUIDE, int SPEC>
+void launch_het_noise_spec(const HetNoiseArgs& a, const FusedShape& sh, const LaunchCtx& c) {
+  launch(stage_kernel_het_noise<TS, TE, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, a);
+}
+
 template <typename TS, typename TE>
 int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
   if (n_req < 1 || n_req > HET_MAX)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one fused launch", n_req);
   const Tuning tn = tuning_for(bs[0].opts);
-  HetArgs a;
-  std::memset(&a, 0, sizeof a);
+  HetNoiseArgs an;  // (the ODE kernels take its first member)
+  std::memset(&an, 0, sizeof an);
+  HetArgs& a = an.h;
   bool ms3 = false;
+  const bool sde = (st[0].flags & DPM_F_NOISE) != 0;
   bool noise = !tn.force_generic;
   for (int r = 0; r < n_req; ++r) {
     fill_request(a, r, bs[r]);
     a.xo2[r] = bs[r].x_out2;
     a.p[r] = make_params(&st[r]);
+    if (sde) an.nz[r] = noise_of(st[r], bs[r]);
     ms3 = ms3 || st[r].form == DPM_FORM_MS3;
     noise = noise && x0_prologue_ok(st[r]);
   }
@@ -820,7 +870,15 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
                 : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, sh, c))                       \
          : (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_GENERIC>(a, sh, c)                          \
                 : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_GENERIC>(a, sh, c)))
-  if (ms3) DPM_HET(HET_FORMS_3);
+  if (sde) {
+    if (noise) {
+      if (cfg) launch_het_noise_spec<TS, TE, DPM_GUIDE_CFG, SPEC_NOISE_X0>(an, sh, c);
+      else launch_het_noise_spec<TS, TE, DPM_GUIDE_NONE, SPEC_NOISE_X0>(an, sh, c);
+    } else {
+      if (cfg) launch_het_noise_spec<TS, TE, DPM_GUIDE_CFG, SPEC_GENERIC>(an, sh, c);
+      else launch_het_noise_spec<TS, TE, DPM_GUIDE_NONE, SPEC_GENERIC>(an, sh, c);
+    }
+  } else if (ms3) DPM_HET(HET_FORMS_3);
   else DPM_HET(HET_FORMS_2);
 #undef DPM_HET
   return launch_status("fused stage kernel launch failed");

@@ -1,6 +1,6 @@
 // dpm_stage_kernel.hpp -- the streaming stage kernels: per-stage scalars (KParams), prologues, update forms, the KExt
-// extensions, stage_kernel / stage_kernel_multi / stage_kernel_het / stage_kernel_scalar (part of dpm_device.hpp; include
-// that)
+// extensions, stage_kernel / stage_kernel_multi / stage_kernel_het / stage_kernel_scalar and their noise flavours (part of
+// dpm_device.hpp; include that)
 #pragma once
 
 namespace {
@@ -295,6 +295,14 @@ __device__ __forceinline__ float blend_ref(float v, float m, float a, float b, b
 // gives the four z of elements 4g .. 4g+3 by Box-Muller, element i taking output pair p = (i & 3) >> 1, cos for even i and
 // sin for odd i.  A separate kernel argument (KParams' 80 bytes size the heterogeneous launch's records).
 // ------------------------------------------------------------------------------------------------
+// Where the generator runs in the tile body (profiles/r10_sde_requests.md): z depends on no loaded value, so it may be computed
+// FIRST -- the compiler then schedules the ~330 VALU slots of Philox + Box-Muller ahead of the tile's loads, with few live
+// registers, and the short update behind their wait -- or behind the update, with the loaded registers live across it.
+// 2-byte states measure 8 % (fused) to 12 % (lone launch) faster with the generator first; 4-byte states measure equal
+// (fused) or 1 % slower (lone) and keep it behind the update.  The same z and the same bits either way.
+#ifndef DPM_NOISE_FIRST
+#define DPM_NOISE_FIRST(TS) (sizeof(TS) == 2)
+#endif
 struct KNoise {
   uint32_t key0, key1;  // the seed, low and high word
   uint32_t ctr;         // dpm_stage.index
@@ -468,6 +476,21 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
       }
     }
   }
+  // the generator first (DPM_NOISE_FIRST): z of the U tiles, pinned here
+  constexpr bool Z_FIRST = NOISE && DPM_NOISE_FIRST(TS);
+  float zn[Z_FIRST ? U : 1][EPT];
+  if constexpr (Z_FIRST) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool split = can_split && (t0 + u) * 256 + 256 <= ngroups;
+      const uint64_t ga = split ? (uint64_t)(t0 + u) * 512u + tile_lane() : 2u * (uint64_t)((t0 + u) * 256 + tile_lane());
+      const uint64_t gb = split ? ga + 256u : ga + 1u;
+      noise4(*nz, ga, zn[u]);
+      noise4(*nz, gb, zn[u] + 4);
+#pragma unroll
+      for (int j = 0; j < EPT; ++j) asm volatile("" : "+v"(zn[u][j]));  // ahead of the first use of a loaded value
+    }
+  }
   // the model values of all U tiles; SPEC_GENERIC picks the prologue mode here, once per workgroup iteration
   f32x2 mnv[U][EPT / 2];
 #define DPM_MODELS(PM_) tile_models<GUIDE, XE, PM_, U, FT::needs_x, TE>(vx, vxe, v0, v1, vg, need_xe, p, mnv)
@@ -504,7 +527,10 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
       ox[q] = o.x;
       ox[q + 1] = o.y;
     }
-    if constexpr (NOISE) {
+    if constexpr (Z_FIRST) {
+#pragma unroll
+      for (int j = 0; j < EPT; ++j) ox[j] = ox[j] + nz->scale * zn[u][j];
+    } else if constexpr (NOISE) {
       const uint64_t ga = split ? (uint64_t)(t0 + u) * 512u + tile_lane() : 2u * (uint64_t)gi;
       const uint64_t gb = split ? ga + 256u : ga + 1u;
       float z[EPT];
@@ -664,6 +690,44 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_multi(const Mu
   }
 }
 
+// SDE stage (DPM_F_NOISE) of requests in lockstep: stage_kernel_multi's tile space with the noise epilogue.  The stage index
+// and the scale c2 are launch-uniform; every request has its own seed, so the Philox keys travel per request in the
+// argument block next to the pointer table and are read, like it, by scalar loads with the wave-uniform request index.
+// z of element i depends on (seed, stage index, i) only (include/dpm_hip.h, noise contract), whatever the tile mapping: the
+// bits of R stage_kernel_noise launches.  One super-tile per 256-lane group and no loop (the grid covers the tile space,
+// as in stage_kernel_het).  Its own family, so that stage_kernel_multi stays as it is.
+struct MultiKeys {
+  uint32_t k0[MULTI_MAX], k1[MULTI_MAX];  // request r's seed, low and high word
+};
+static_assert(sizeof(MultiTab) + sizeof(MultiKeys) + sizeof(KParams) + 64 <= 4096,
+              "the fused noise launch's argument block must fit HIP's 4 KiB");
+
+template <typename TS, typename TE, int FORM, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_multi_noise(const MultiTab tab, const MultiKeys keys, int64_t n,
+                                                                              uint32_t nreq, uint32_t spr, KParams p,
+                                                                              uint32_t xcd_span, uint32_t ctr, float scale) {
+  static_assert((FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO) && GUIDE != DPM_GUIDE_CLASSIFIER, "noise: LIN1 / TWO, no classifier");
+  const int64_t ngroups = n / EPT;
+  const uint32_t total = nreq * spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (xcd_span && in_xcd >= xcd_span) return;
+  const uint32_t v = xcd_span ? (b & 7u) * xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = v / spr;
+  const int64_t t0 = (int64_t)(v - r * spr) * U;
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = tab.xo2[r];
+  const KNoise nz = {keys.k0[r], keys.k1[r], ctr, scale};
+  stage_tiles<TS, TE, FORM, GUIDE, false, SPEC, U, NT, DUP, false, true>(
+      static_cast<const TS*>(tab.x[r]), nullptr, static_cast<const TE*>(tab.e0[r]), static_cast<const TE*>(tab.e1[r]), nullptr,
+      static_cast<const TS*>(tab.h1[r]), nullptr, static_cast<TS*>(tab.xo[r]), static_cast<TS*>(tab.mo[r]), ngroups, t0, p, ext,
+      nullptr, &nz);
+}
+
 // ------------------------------------------------------------------------------------------------
 // heterogeneous fused stage (continuous batching): the launch shape and tile body of stage_kernel_multi, but every request
 // carries its own stage record -- form, flags and coefficients -- so requests at different positions of different plans
@@ -694,6 +758,13 @@ struct HetArgs {
   uint32_t xcd_span;   // != 0: XCD-contiguous remap (see stage_kernel_multi)
 };
 static_assert(sizeof(HetArgs) <= 4096, "the heterogeneous launch's argument block must fit HIP's 4 KiB");
+// stage_kernel_het_noise: the same block + seed, stage index and scale of every request (256 bytes; about 2.6 KiB).  A struct
+// of its own: a field added to HetArgs moves the hidden arguments behind it, and with them stage_kernel_het's code.
+struct HetNoiseArgs {
+  HetArgs h;
+  KNoise nz[HET_MAX];
+};
+static_assert(sizeof(HetNoiseArgs) <= 4096, "the heterogeneous noise launch's argument block must fit HIP's 4 KiB");
 constexpr unsigned HET_FORMS_2 = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_TWO);
 constexpr unsigned HET_FORMS_3 = HET_FORMS_2 | (1u << DPM_FORM_MS3);
 
@@ -735,6 +806,48 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het(const HetA
       if constexpr ((FORMS >> DPM_FORM_MS3) & 1u) DPM_HET_TILES(DPM_FORM_MS3);
       break;
     default: break;  // (the host groups only forms of FORMS)
+  }
+#undef DPM_HET_TILES
+}
+
+// SDE stages (DPM_F_NOISE) of requests at different positions: stage_kernel_het with the noise epilogue.  Every request has
+// its own stage index and scale next to its seed -- a whole KNoise per request, read in place like the stage record and for
+// the same reason.  SDE plans are made of LIN1, TWO and DENOISE stages (the last carries no noise): the form set is {LIN1, TWO}.
+template <typename TS, typename TE, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het_noise(const HetNoiseArgs args) {
+  static_assert(GUIDE != DPM_GUIDE_CLASSIFIER, "noise: no classifier guidance");
+  (void)args;
+  const HetNoiseArgs& an = *(const HetNoiseArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const HetArgs& a = an.h;
+  const int64_t ngroups = a.n / EPT;
+  const uint32_t total = a.nreq * a.spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (a.xcd_span && in_xcd >= a.xcd_span) return;
+  const uint32_t v = a.xcd_span ? (b & 7u) * a.xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = v / a.spr;
+  const int64_t t0 = (int64_t)(v - r * a.spr) * U;
+  const KParams& p = a.p[r];
+  const KNoise* nz = &an.nz[r];
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = a.xo2[r];
+  const TS* x = static_cast<const TS*>(a.x[r]);
+  const TE* e0 = static_cast<const TE*>(a.e0[r]);
+  const TE* e1 = static_cast<const TE*>(a.e1[r]);
+  const TS* h1 = static_cast<const TS*>(a.h1[r]);
+  TS* xo = static_cast<TS*>(a.xo[r]);
+  TS* mo = static_cast<TS*>(a.mo[r]);
+#define DPM_HET_TILES(F_)                                                                                                    \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP, false, true>(x, nullptr, e0, e1, nullptr, h1, nullptr, xo, mo, ngroups, \
+                                                                       t0, p, ext, nullptr, nz)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_HET_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_HET_TILES(DPM_FORM_TWO); break;
+    default: break;  // (the host groups LIN1 / TWO only)
   }
 #undef DPM_HET_TILES
 }

@@ -17,6 +17,7 @@ from . import _lib as L
 from .correctors import MaskBlend
 from .launch_list import _FastRun, _bind_outputs
 from .plan_cache import _Cloning
+from .sde import request_opts
 
 def run_plan_group(self, plan, xs, sd, cfg):
     """`_run_plan_fast` over several requests: a set of launch records per request (_FastRun), per stage the network
@@ -43,6 +44,8 @@ def run_plan_group(self, plan, xs, sd, cfg):
     first = [first0] + [net(x, 0) for x in xs[1:]]
     sd = self._promoted(sd, first[0][0], plan)
     mf = DV._mf_of(first[0][0]) if first[0][0].shape == shape else None
+    if plan.sde:
+        mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit))
     grp = None if capturing else self._fast_groups.get(key)
     if grp is None:
@@ -59,6 +62,26 @@ def run_plan_group(self, plan, xs, sd, cfg):
                 self._fast_groups.pop(next(iter(self._fast_groups)))
             self._fast_groups[key] = grp
     runs, arrs = grp
+    if not plan.sde:
+        return _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, idx, other)
+    # sample_sde_requests: every request's seed in a dpm_launch_opts of its own, pointed to for the length of this call
+    # only -- the cached records go back to the solver's seedless options
+    base = self._opts_ptr()
+    ropts = [request_opts(s, base) for s in self._group_seeds]
+    try:
+        for a in arrs:
+            for r in range(R):
+                a[r].opts = C.pointer(ropts[r])
+        return _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, idx, other)
+    finally:
+        for a in arrs:
+            for r in range(R):
+                a[r].opts = base
+
+
+def _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, idx, other):
+    """run_plan_group's stage loop: per stage the network on every request, then ONE dpm_stage_launch_multi"""
+    R, shape, device = len(xs), xs[0].shape, xs[0].device
     x0s = [DV._conv(x, sd, mf) for x in xs]
     outs = [DV._empty(shape, sd, device, mf) for _ in range(R)]
     last, roles = runs[0].last, plan.roles
@@ -184,10 +207,18 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
         return self._run_plan_fast(plan, x, sd, cfg)
     if self._group is not None:          # (requests that need the general loop run one after the other)
         grp, self._group = self._group, None
+        seeds = self._group_seeds        # sample_sde_requests: each request with its own seed
         try:
-            return [self._run_plan(plan, xg, method, cxt, keep, intermediates) for xg in grp]
+            outs = []
+            for r, xg in enumerate(grp):
+                if seeds is not None:
+                    self._noise_seed = seeds[r]
+                outs.append(self._run_plan(plan, xg, method, cxt, keep, intermediates))
+            return outs
         finally:
             self._group = grp
+            if seeds is not None:
+                self._noise_seed = None
     V = self._time_views(plan, device, x.shape[0] if x.dim() > 0 else 1, cfg)
     if self.fresh_time_tensors:
         V = dict(V, t_eval_b=_Cloning(V["t_eval_b"]), t_input_b=_Cloning(V["t_input_b"]),

@@ -13,6 +13,11 @@ One tick calls the network once per active request, on its own state at its own 
 dpm_stage_launch_multi whose stage records are per request (dpm_launch_opts.per_request_stages): the library fuses the
 requests its heterogeneous kernel covers and launches the rest one by one.  Every result is bit-identical to
 `sample(x_T, **its kwargs)`, whatever else was in flight.
+
+`submit(..., sde=True, seed=...)` admits an SDE-DPM-Solver++ request (`sample_sde`'s arguments and checks): its seed is
+resolved at submission and travels in a dpm_launch_opts of the request's own, pointed to by its dpm_buffers entry of every
+tick -- never by the launch records, which finished requests hand on to later ones.  The library fuses SDE stages in groups
+of their own, next to the ODE groups of the same tick; the result is bit-identical to `sample_sde(x_T, seed=..., ...)`.
 """
 import ctypes as C
 
@@ -20,6 +25,7 @@ import torch
 
 from . import _device as DV
 from . import _lib as L
+from . import sde as _sde
 from .launch_list import _FastRun, _bind_outputs
 from .plan_cache import _Cloning
 
@@ -28,7 +34,7 @@ _METHODS = ("multistep", "singlestep", "singlestep_fixed")
 
 class _Request:
     """one request in flight: its plan, its launch records (a _FastRun of its own) and its position"""
-    __slots__ = ("x", "plan", "i", "V", "sd", "mf", "fr", "key", "x0", "out", "first")
+    __slots__ = ("x", "plan", "i", "V", "sd", "mf", "fr", "key", "x0", "out", "first", "seed", "opts")
 
 
 class RequestPool:
@@ -50,10 +56,23 @@ class RequestPool:
         return len(self) > 0
 
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
-               lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False):
+               lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False,
+               sde=False, seed=None, generator=None):
         """Admit a request: `x` = its x_T, the rest as for `sample()` (multistep, singlestep and singlestep_fixed methods),
-        validated with sample()'s errors.  Returns the request's handle (an int)."""
+        validated with sample()'s errors.  `sde=True`: an SDE-DPM-Solver++ request -- `sample_sde`'s arguments, checks and
+        seed rules (`seed`, or one draw from `generator` / torch's default CPU generator, made here).  Returns the request's
+        handle (an int)."""
         s = self._s
+        if not sde and (seed is not None or generator is not None):
+            raise ValueError("request pool: `seed` / `generator` belong to an SDE request (sde=True)")
+        if sde:
+            if method != 'multistep':
+                raise ValueError("request pool: sde=True samples by the multistep SDE-DPM-Solver++ (method='multistep'), "
+                                 "got method={!r}".format(method))
+            _sde.check_solver(s, order)
+            seed = _sde.resolve_seed(seed, generator)
+            if torch.is_tensor(x):
+                _sde.check_state(s, x)
         if method == 'adaptive':
             raise NotImplementedError("request pool: method='adaptive' has no plan of stages (its step sizes depend on the "
                                       "state); sample it with sample()")
@@ -78,7 +97,7 @@ class RequestPool:
         assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero,
-                                  solver_type)
+                                  solver_type, sde=bool(sde))
         sd = s._sdtype(x)
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
@@ -92,6 +111,8 @@ class RequestPool:
             return h
         q = _Request()
         q.x, q.plan, q.i, q.sd = x, plan, 0, sd
+        q.seed = seed if sde else None
+        q.opts = L.LaunchOpts() if sde else None      # its own options: the solver's + its seed (step)
         self._active[h] = q
         return h
 
@@ -102,6 +123,8 @@ class RequestPool:
         q.first = self._net(q, q.x, 0, None, cfg)
         q.sd = s._promoted(q.sd, q.first[0], q.plan)
         q.mf = DV._mf_of(q.first[0]) if q.first[0].shape == q.x.shape else None
+        if q.plan.sde:
+            q.mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
         q.key = (id(q.plan), tuple(q.x.shape), q.sd, idx, stream, cfg, q.mf, bool(s.cluster_in_graph), int(s.thr_spin_limit))
         free = self._free.get(q.key)
         q.fr = free.pop() if free else _FastRun(s, q.plan, q.x.shape, q.sd, q.x.device, cfg, q.mf)
@@ -163,17 +186,28 @@ class RequestPool:
                 keep.append(_bind_outputs(b, e[0], e[1], e[2], q.sd, q.x.shape, q.mf))
                 C.memmove(C.byref(sts, r * C.sizeof(L.Stage)), C.byref(fr.stages[i]), C.sizeof(L.Stage))
                 C.memmove(C.byref(bufs, r * C.sizeof(L.Buffers)), C.byref(b), C.sizeof(L.Buffers))
-        # request 0's options carry the per-request flag (the library reads bs[0].opts); the others keep the solver's
+        # request 0's options carry the per-request flag (the library reads bs[0].opts); an SDE request's carry its seed,
+        # each in a dpm_launch_opts of its own; the others keep the solver's.  The seeds live in this tick's array only.
         o = s._opts_ptr()
         if o is not None:
             C.memmove(C.byref(self._opts), o, C.sizeof(L.LaunchOpts))
         self._opts.per_request_stages = 1
+        self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
+        for r, q in enumerate(self._active.values()):
+            if q.seed is None:
+                continue
+            if r == 0:
+                self._opts.noise_seed_lo, self._opts.noise_seed_hi = q.seed & 0xffffffff, q.seed >> 32
+            else:
+                q.opts = _sde.request_opts(q.seed, o)
+                bufs[r].opts = C.pointer(q.opts)
         bufs[0].opts = C.pointer(self._opts)
         if other:
             with torch.cuda.device(idx):
                 rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
         else:
             rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
+        self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
         if rc:
             L.check(rc)
         del keep

@@ -74,6 +74,7 @@ class DPM_Solver:
     # (correcting_xt_fn, a callable correcting_x0_fn), return_intermediate or a host-side adaptive loop are never captured.
     auto_capture = 0
     _noise_seed = None                       # sample_sde: the seed of the call in progress (dpm_launch_opts.noise_seed_*)
+    _group_seeds = None                      # sample_sde_requests: the seeds of the group in progress, one per request
     _sde_opts = None
 
     def __init__(self, model_fn, noise_schedule, algorithm_type="dpmsolver++", correcting_x0_fn=None,
@@ -666,6 +667,7 @@ class DPM_Solver:
             return x
 
     sample_sde = _sde.sample_sde
+    sample_sde_requests = _sde.sample_sde_requests
 
     def sample_requests(self, xs, **sample_kwargs):
         """(extension) `sample()` for several independent requests that are in flight together -- a server's batch of

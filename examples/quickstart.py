@@ -87,6 +87,17 @@ def main():
         y2 = solver.sample_sde(x_T, steps=20, order=2, seed=1234)
     print("sample_sde: reproducible = %s, differs from the ODE sample by %.3g of its scale"
           % (torch.equal(y1, y2), ((y1 - x0).abs().max() / x0.abs().max()).item()))
+    # ... and for requests in flight: a seed per request, one fused launch per stage; in a pool next to ODE requests
+    with torch.no_grad():
+        zs = solver.sample_sde_requests(xs, seeds=range(len(xs)), steps=20, order=2)
+        assert all(torch.equal(z, solver.sample_sde(x, steps=20, order=2, seed=s)) for s, (x, z) in enumerate(zip(xs, zs)))
+        pool = solver.request_pool()
+        h_sde, h_ode = pool.submit(xs[0], steps=20, order=2, sde=True, seed=0), pool.submit(xs[1], steps=12, order=2)
+        done = {}
+        while pool:
+            done.update(pool.step())
+        assert torch.equal(done[h_sde], zs[0]) and torch.equal(done[h_ode], solver.sample(xs[1], steps=12, order=2))
+    print("sample_sde_requests / request_pool(sde=True): %d requests, identical to sample_sde() of each" % len(zs))
 
     # DiffEdit / inpainting: keep the masked-out region on the known image, noised to the current level
     mask = (torch.rand(64, 64, device=dev) > 0.5).float()

@@ -55,11 +55,13 @@ extern "C" {
    requests at different positions of different plans in one fused launch (continuous batching).
    203 DPM_ALGO_SDE_DPMSOLVERPP, DPM_F_NOISE and dpm_launch_opts.noise_seed_lo / _hi (were reserved[0..1]): SDE-DPM-Solver++
    with its Gaussian term generated inside the stage kernel (see "noise contract" below; no struct changed size).
+   204 dpm_stage_launch_multi / dpm_plan_run_multi fuse DPM_F_NOISE stages too -- lockstep and per-request stages -- with the
+   seed of every request taken from its own bs[r].opts (no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 203
+#define DPM_HIP_VERSION 204
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -183,9 +185,10 @@ typedef struct dpm_launch_opts {
   int32_t per_request_stages; /* 1: dpm_stage_launch_multi reads `st` as an array of n_req stage records, request r is
                                advanced by st[r] (version 202; see there)                                             */
   uint32_t noise_seed_lo;   /* version 203: the 64-bit seed of DPM_F_NOISE stages (Philox key), low and high word (were */
-  uint32_t noise_seed_hi;   /* reserved[0..1]).  dpm_stage_launch_multi launches noise stages request by request, each  */
-                            /* with its own bs[r].opts seed; dpm_plan_run_multi hands request r its rbs[r].opts there;  */
-                            /* dpm_graph_create bakes the seed of rb->opts into the graph                              */
+  uint32_t noise_seed_hi;   /* reserved[0..1]).  dpm_stage_launch_multi fuses noise stages like the others (version 204) */
+                            /* and still keys request r's generator with the seed of its own bs[r].opts (NULL: seed 0); */
+                            /* dpm_plan_run_multi hands request r its rbs[r].opts there; dpm_graph_create bakes the     */
+                            /* seed of rb->opts into the graph                                                          */
   int32_t reserved[2];      /* zero                                                                                   */
 } dpm_launch_opts;
 
@@ -335,7 +338,10 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    from HBM (a network ran in between) that is 8.5 -> ~6.7 us per [256,4,64,64] fp16 request-stage.  Stages with
    dynamic thresholding become one thresholding launch over all requests' samples (a batch of n_req * batch: smaller
    clusters or none -- 32 requests of [32,3,64,64] cost about what one [1024,3,64,64] does), provided clustered shapes
-   find a DIFFERENT workspace in every request; classifier-free guidance keeps its duplicate store (x_out2).  Stages
+   find a DIFFERENT workspace in every request; classifier-free guidance keeps its duplicate store (x_out2).  SDE stages
+   (DPM_F_NOISE, version 204) are fused as well: the stage index and the scale are the launch's, the seed is each request's
+   own -- bs[r].opts->noise_seed_lo / _hi, 0 where bs[r].opts is NULL -- and every request gets the bits of its single
+   launch (the noise contract: z depends on seed, stage index and element index only).  Stages
    neither family covers (mask blend, classifier guidance, strided or
    unaligned buffers, the singlestep mid-stages, thresholding with a shared workspace) are launched request by
    request; results are identical either way.
@@ -346,8 +352,9 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    multistep third-order (MS3), without thresholding, mask blend or classifier guidance, whose evaluation state is the
    state and whose buffers are dense and 16-byte aligned, are fused -- 16 per launch: the records travel in the kernel's
    arguments, within HIP's 4 KiB -- with every other
-   request that agrees with them on dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the rest are launched
-   one by one.  Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
+   request that agrees with them on dtypes, n, batch, model type, guidance kind, DPM_F_TO_X0 and DPM_F_NOISE (SDE stages
+   -- LIN1 / TWO -- form groups of their own, each request with its own stage index, scale and seed); the rest are launched
+   one by one. Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
