@@ -102,7 +102,8 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
 
     ext (optional dict): 'dup' -> write x_out twice into one [2B,...] buffer (returned as ext['x2'], x_out is its
     first half): the network input of classifier-free guidance; 'blend' -> (mask, period, a, b, alpha, sigma), the
-    MaskBlend epilogue."""
+    MaskBlend epilogue; 'xc' -> a DPM_FORM_UNIPC stage also stores its corrected state (DPM_F_STORE_XC), returned as
+    ext['xc_out'] (not together with 'dup': both use x_out2)."""
     ref_t = x if x is not None else xe
     dev = ref_t.device
     sd = state_dtype
@@ -136,6 +137,10 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
         b.x_out2 = x2.data_ptr() + x_out.numel() * x_out.element_size()
     else:
         x_out = _empty(shape, sd, dev, mf)
+        if ext is not None and ext.get("xc"):
+            ext["xc_out"] = _empty(shape, sd, dev, mf)
+            b.x_out2 = ext["xc_out"].data_ptr()
+            st.flags |= L.F_STORE_XC
     store = bool(st.flags & L.F_STORE_M) if want_m is None else want_m
     m_out = None
     if store:

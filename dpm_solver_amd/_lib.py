@@ -24,16 +24,19 @@ DPM_OK = 0
 ERR_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_NOMEM, ERR_CALLBACK, ERR_FAULT = -1, -2, -3, -4, -5, -6
 ALGO = {"dpmsolver": 0, "dpmsolver++": 1}
 ALGO_SDE_DPMSOLVERPP = 2      # dpm_plan_create only (DPM_Solver.sample_sde)
+ALGO_UNIPC = 3                # dpm_plan_create only (DPM_Solver.sample_unipc)
 SOLVER = {"dpmsolver": 0, "taylor": 1}
+UNIPC_VARIANT = {"bh1": 2, "bh2": 3}      # dpm_plan_desc.solver_type of a DPM_ALGO_UNIPC plan
 METHOD = {"multistep": 0, "singlestep": 1, "singlestep_fixed": 2}
 SKIP = {"time_uniform": 0, "logSNR": 1, "time_quadratic": 2}
 MODEL = {"noise": 0, "x_start": 1, "v": 2, "score": 3}
 GUIDE = {"uncond": 0, "classifier-free": 1, "classifier": 2}
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_F64 = 0, 1, 2, 3
 EVAL_LOG_ALPHA, EVAL_ALPHA, EVAL_STD, EVAL_LAMBDA, EVAL_INV_LAMBDA = 0, 1, 2, 3, 4
-FORM_LIN1, FORM_TWO, FORM_MS3, FORM_SS3T, FORM_DENOISE = 0, 1, 2, 3, 4
+FORM_LIN1, FORM_TWO, FORM_MS3, FORM_SS3T, FORM_DENOISE, FORM_UNIPC = 0, 1, 2, 3, 4, 5
 F_TO_X0, F_STORE_M, F_BASE_HIST, F_THRESH, F_USER_X0, F_BLEND = 1, 2, 4, 8, 16, 32
 F_NOISE = 64
+F_UNIPC_DP, F_UNIPC_P2, F_STORE_XC = 128, 256, 512
 SRC_STATE, SRC_TMP = 0, 1
 # knobs of the LAB build (include/dpm_lab.h: dpm_tuning_set / dpm_tuning_get; the product library has none)
 TUNE_UNROLL, TUNE_NONTEMPORAL, TUNE_BLOCKS_PER_CU, TUNE_ASSUME_RESIDENT = 0, 1, 2, 3
@@ -271,8 +274,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 202:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 202 -- stale library, rebuild"
+if lib.dpm_version() < 205:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 205 -- stale library, rebuild"
                       % lib.dpm_version())
 
 

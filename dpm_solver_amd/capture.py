@@ -11,6 +11,11 @@ class GraphedSample:
         DV._require_gpu(x)
         self.solver = solver
         self.kwargs = dict(sample_kwargs)
+        # capture(x, unipc=True, ...): a sample_unipc call (its own keyword arguments; `method` is implied)
+        run = solver.sample
+        if self.kwargs.pop("unipc", False):
+            self.kwargs.pop("method", None)
+            run = solver.sample_unipc
         self.static_x = x.clone()
         dev = x.device
         side = torch.cuda.Stream(device=dev)
@@ -20,7 +25,7 @@ class GraphedSample:
             # counters, _Plan.time_views), and the rebuild of the shared time vectors it triggers -- a pageable host-to-device
             # copy and an allocation -- must not land inside the capture
             for _ in range(max(int(warmup), 2)):
-                solver.sample(self.static_x, **self.kwargs)
+                run(self.static_x, **self.kwargs)
         torch.cuda.current_stream(dev).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         # No garbage collection while the stream is capturing: a finaliser that frees device resources inside the capture
@@ -33,7 +38,7 @@ class GraphedSample:
         gc.disable()
         try:
             with torch.cuda.graph(self.graph):
-                self.static_out = solver.sample(self.static_x, **self.kwargs)
+                self.static_out = run(self.static_x, **self.kwargs)
         finally:
             if gc_was_on:
                 gc.enable()

@@ -129,6 +129,8 @@ template <typename TS, typename TE, bool DYN>
 const void* dpm_catchall_scalar();
 template <typename TS, typename TE>
 const void* dpm_catchall_scalar_noise();  // the SDE stages' one-element-per-lane kernel (DPM_F_NOISE)
+template <typename TS, typename TE>
+const void* dpm_catchall_scalar_unipc();  // the UniPC stages' one-element-per-lane kernel (DPM_FORM_UNIPC)
 
 #include "dpm_access.hpp"
 #include "dpm_stage_kernel.hpp"

@@ -562,7 +562,9 @@ namespace {
 template <class S, class ST>
 int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std::vector<typename S::F>& grid, int& slots_out) {
   typedef typename S::F F;
-  const bool pp = d->algorithm_type == DPM_ALGO_DPMSOLVERPP;
+  // (UniPC: the data-prediction multistep plan with UniPC's step orders and stage form; its scalars come from unipc_scalars)
+  const bool unipc = d->algorithm_type == DPM_ALGO_UNIPC;
+  const bool pp = d->algorithm_type == DPM_ALGO_DPMSOLVERPP || unipc;
   const double t_T = d->t_start, t_0 = d->t_end;
   int rc = DPM_OK;
   int last_step = 0;
@@ -588,7 +590,7 @@ int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std:
     // :1185-1201) -- while order=4 with steps >= 7 raises at the first fourth-order update (and steps = 6 at the third-order
     // update of the main loop, see below).  Same here: the step orders
     // first, then the check on what they contain.  The history ring needs min(P, 3) slots.
-    const int PS = std::min(P, 3);
+    const int PS = unipc ? P + 1 : std::min(P, 3);  // UniPC stage i reads m_{i-1} (and m_{i-2}) and writes m_i
     if (P < 1) rc = dpm_set_error(DPM_ERR_ARG, "Solver order must be 1 or 2 or 3, got %d", P);
     if (!rc && S_ < P) rc = dpm_set_error(DPM_ERR_ARG, "multistep needs steps >= order (steps=%d, order=%d)", S_, P);
     if (!rc) {
@@ -598,7 +600,9 @@ int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std:
     std::vector<int> ord(rc ? 0 : S_);
     for (int i = 0; i < (int)ord.size(); ++i) {
       const int step = i + 1;  // the reference's loop variable: this stage produces x at ts[step]
-      if (step < P)
+      if (unipc)  // o_step = min(order, step, steps + 1 - step): lower_order_final at every step count
+        ord[i] = std::min(std::min(P, step), d->lower_order_final ? S_ + 1 - step : P);
+      else if (step < P)
         ord[i] = step;  // warm-up, ref :1185-1187
       else
         ord[i] = (d->lower_order_final && S_ < 10) ? std::min(P, S_ + 1 - step) : P;  // ref :1198-1201
@@ -619,7 +623,23 @@ int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std:
         else
           coef_ms3(s, pp, ts[i - 2], ts[i - 1], ts[i], ts[i + 1], &st);
         st.outer_step = i + 1;
-        if (P >= 2) {
+        if (unipc) {
+          // stage i >= 1 corrects step i (order ord[i - 1]) and predicts step i + 1 (order ord[i]); every stage but the
+          // last stores its model value: the next stage's corrector reads it
+          if (i >= 1) {
+            st.form = DPM_FORM_UNIPC;
+            st.h1_slot = (i - 1) % PS;
+            if (ord[i - 1] == 2) {
+              st.h2_slot = (i - 2) % PS;
+              st.flags |= DPM_F_UNIPC_DP;
+            }
+            if (ord[i] == 2) st.flags |= DPM_F_UNIPC_P2;
+          }
+          if (i + 1 < S_) {
+            st.flags |= DPM_F_STORE_M;
+            st.m_slot = i % PS;
+          }
+        } else if (P >= 2) {
           if (ord[i] >= 2) st.h1_slot = (i - 1) % PS;
           if (ord[i] >= 3) st.h2_slot = (i - 2) % PS;
           bool needed = false;  // does a later stage read this stage's model value?
@@ -632,7 +652,7 @@ int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std:
         }
         finish_stage(st, ts[i], grid_f64 ? 3 : 0);
       }
-      slots_out = P >= 2 ? PS : 0;
+      slots_out = unipc ? (S_ > 1 ? PS : 0) : (P >= 2 ? PS : 0);
       last_step = S_;
     }
   } else {
@@ -746,23 +766,67 @@ void sde_scalars(const dpm_schedule* s, int solver_type, const std::vector<float
     st.flags |= DPM_F_NOISE;
   }
 }
+
+// UniPC (DPM_ALGO_UNIPC; include/dpm_hip.h, DPM_FORM_UNIPC): the scalars of every update stage in double at the plan's
+// times, rounded once.  Stage i predicts step i + 1 (t_i -> t_{i+1}): cx = sigma_t / sigma_s, c0 = alpha_t expm1(-h),
+// k0 = 1 / r0, c1 = alpha_t B / 2 -- DPM-Solver++ 2M's scalars when B = expm1(-h) (bh2) -- and, from stage 1 on, corrects
+// step i (t_{i-1} -> t_i): c2 = alpha_i B (1/2 - rho_1), k1 = alpha_i B rho_last, k2 = 1 / r with rho the solution of
+// [[1, 1], [r, 1]] rho = [b_1, b_2], b_1 = g_1 / B, b_2 = 2 g_2 / B, g_1 = expm1(-h) / (-h) - 1, g_2 = g_1 / (-h) - 1/2
+// (first order: rho = [1/2], no D_p term).
+void unipc_scalars(const dpm_schedule* s, bool bh1, const std::vector<float>& grid, std::vector<dpm_stage>& stages) {
+  const dpmc::SchedView64 v = s->view64();
+  for (dpm_stage& st : stages) {
+    if (st.form == DPM_FORM_DENOISE) continue;
+    const int i = st.index;  // multistep: stage i is evaluated at grid[i] and writes the state at grid[i + 1]
+    const double lam_s = v.lambda((double)grid[i]), lam_t = v.lambda((double)grid[i + 1]);
+    const double a_t = v.alpha((double)grid[i + 1]);
+    const double h = lam_t - lam_s, phi_1 = expm1(-h), B = bh1 ? -h : phi_1;
+    const bool p2 = st.form == DPM_FORM_TWO || (st.form == DPM_FORM_UNIPC && (st.flags & DPM_F_UNIPC_P2));
+    st.cx = (float)(v.std_((double)grid[i + 1]) / v.std_((double)grid[i]));
+    st.c0 = (float)(a_t * phi_1);
+    st.c1 = st.c2 = 0.f;
+    for (float& k : st.k) k = 0.f;
+    if (p2) {
+      st.k[0] = (float)(h / (lam_s - v.lambda((double)grid[i - 1])));
+      st.c1 = (float)(0.5 * (a_t * B));
+    }
+    if (st.form != DPM_FORM_UNIPC) continue;
+    const double lam_p = v.lambda((double)grid[i - 1]), a_i = v.alpha((double)grid[i]);
+    const double hc = lam_s - lam_p, hh = -hc, phc = expm1(hh), Bc = bh1 ? hh : phc;
+    if (st.flags & DPM_F_UNIPC_DP) {
+      const double r = (v.lambda((double)grid[i - 2]) - lam_p) / hc;
+      const double g1 = phc / hh - 1., g2 = g1 / hh - 0.5;
+      const double b1 = g1 / Bc, b2 = 2. * g2 / Bc;
+      const double rho1 = (b2 - b1) / (r - 1.), rho2 = b1 - rho1;
+      st.c2 = (float)(a_i * Bc * (0.5 - rho1));
+      st.k[1] = (float)(a_i * Bc * rho2);
+      st.k[2] = (float)(1. / r);
+    } else {
+      st.k[1] = (float)(a_i * Bc * 0.5);
+    }
+  }
+}
 }  // namespace
 
 extern "C" int dpm_plan_create(const dpm_schedule* s, const dpm_plan_desc* d, dpm_plan** out) {
   if (!s || !d || !out) return dpm_set_error(DPM_ERR_ARG, "null pointer");
-  if (check_enum(d->algorithm_type, 0, 2, "algorithm_type") || check_enum(d->model_type, 0, 3, "model_type") ||
+  if (check_enum(d->algorithm_type, 0, 3, "algorithm_type") || check_enum(d->model_type, 0, 3, "model_type") ||
       check_enum(d->guidance, 0, 2, "guidance_type"))
     return DPM_ERR_ARG;
   if (d->method < 0 || d->method > 2) return dpm_set_error(DPM_ERR_ARG, "Got wrong method %d", d->method);
   if (d->skip_type < 0 || d->skip_type > 2)
     return dpm_set_error(DPM_ERR_ARG, "Unsupported skip_type %d, need to be 'logSNR' or 'time_uniform' or 'time_quadratic'", d->skip_type);
-  if (d->solver_type < 0 || d->solver_type > 1)
+  const bool unipc = d->algorithm_type == DPM_ALGO_UNIPC;
+  if (unipc && d->solver_type != DPM_SOLVER_UNIPC_BH1 && d->solver_type != DPM_SOLVER_UNIPC_BH2)
+    return dpm_set_error(DPM_ERR_ARG, "unipc: 'variant' must be either 'bh1' or 'bh2' (solver_type %d)", d->solver_type);
+  if (!unipc && (d->solver_type < 0 || d->solver_type > 1))
     return dpm_set_error(DPM_ERR_ARG, "'solver_type' must be either 'dpmsolver' or 'taylor', got %d", d->solver_type);
   if (!(d->t_end > 0) || !(d->t_start > 0))
     return dpm_set_error(DPM_ERR_ARG, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array");
   if (d->steps < 1) return dpm_set_error(DPM_ERR_ARG, "steps must be >= 1, got %d", d->steps);
   if (d->precision != 0 && d->precision != 1) return dpm_set_error(DPM_ERR_ARG, "precision must be 0 (fp32) or 1 (double)");
   const bool sde = d->algorithm_type == DPM_ALGO_SDE_DPMSOLVERPP;
+  const bool bh1 = d->solver_type == DPM_SOLVER_UNIPC_BH1;
   dpm_plan_desc ode = *d;  // an SDE plan is the DPM-Solver++ multistep plan with other scalars (sde_scalars)
   if (sde) {
     if (d->method != DPM_METHOD_MULTISTEP)
@@ -776,12 +840,24 @@ extern "C" int dpm_plan_create(const dpm_schedule* s, const dpm_plan_desc* d, dp
     ode.algorithm_type = DPM_ALGO_DPMSOLVERPP;
     d = &ode;
   }
+  if (unipc) {
+    if (d->method != DPM_METHOD_MULTISTEP) return dpm_set_error(DPM_ERR_UNSUPPORTED, "unipc: multistep only (method %d)", d->method);
+    if (d->order < 1 || d->order > 2)
+      return dpm_set_error(DPM_ERR_ARG, "unipc: 'order' must be 1 or 2 (order 3 needs a third cached model value: a follow-up), got %d",
+                           d->order);
+    if (d->thresholding)
+      return dpm_set_error(DPM_ERR_UNSUPPORTED, "unipc with dynamic thresholding: the thresholding kernel has no UniPC form");
+    if (d->precision) return dpm_set_error(DPM_ERR_UNSUPPORTED, "unipc: double-precision plans (no double UniPC kernel)");
+    ode.solver_type = DPM_SOLVER_DPMSOLVER;  // (plan_build's second-order stages; unipc_scalars replaces every scalar)
+    d = &ode;
+  }
   dpm_plan* p = new (std::nothrow) dpm_plan;
   if (!p) return dpm_set_error(DPM_ERR_NOMEM, "out of memory");
   int rc;
   if (d->precision == 0) {
     rc = plan_build(s, d, p->stages, p->grid, p->slots);
     if (!rc && sde) sde_scalars(s, d->solver_type, p->grid, p->stages);
+    if (!rc && unipc) unipc_scalars(s, bh1, p->grid, p->stages);
     p->grid64.assign(p->grid.begin(), p->grid.end());
   } else {
     const dpmc::SchedView64 v = s->view64();

@@ -20,7 +20,7 @@
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
 // pair's catch-all kernels, unit B the heterogeneous fused launcher.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
-constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE);
+constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
 // ---- dpm_stage_unit.hip, instantiated once per pair and unit
 // one stage of the forms in FORMS; `multi` / n_multi: a thresholded stage of n_multi requests fused into one launch

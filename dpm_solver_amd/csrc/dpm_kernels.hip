@@ -73,8 +73,9 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool report =
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
-  const bool needs_h1 = st->form == DPM_FORM_TWO || st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
-  const bool needs_h2 = st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T;
+  const bool unipc = st->form == DPM_FORM_UNIPC;
+  const bool needs_h1 = st->form == DPM_FORM_TWO || st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T || unipc;
+  const bool needs_h2 = st->form == DPM_FORM_MS3 || st->form == DPM_FORM_SS3T || (unipc && (st->flags & DPM_F_UNIPC_DP));
   const bool need_xe = (st->flags & DPM_F_TO_X0) || st->model_type == DPM_MODEL_X_START || st->model_type == DPM_MODEL_V;
   if (!b->e0 || !b->x_out) return fail(DPM_ERR_ARG, "stage_launch: e0 / x_out must not be null");
   if ((needs_x || need_xe) && !b->x && !b->xe) return fail(DPM_ERR_ARG, "stage_launch: x is null");
@@ -100,6 +101,17 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool report =
       return fail(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with DPM_F_THRESH (the thresholding kernel has no noise epilogue)");
     if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
       return fail(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with a double state (no double noise kernel)");
+  }
+  if (unipc) {  // the UniPC form exists in the streaming family only, in the data-prediction form, on 2- and 4-byte states
+    if (st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_USER_X0 | DPM_F_BASE_HIST))
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with thresholding, mask blend, noise or a split stage (flags %u)",
+                  st->flags);
+    if (!(st->flags & DPM_F_TO_X0)) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC is the data-prediction form (DPM_F_TO_X0)");
+    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with a double state (no double UniPC kernel)");
+    if ((st->flags & DPM_F_STORE_XC) && !b->x_out2) return fail(DPM_ERR_ARG, "stage_launch: DPM_F_STORE_XC without x_out2");
+  } else if (st->flags & (DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC)) {
+    return fail(DPM_ERR_ARG, "stage_launch: DPM_F_UNIPC_* / DPM_F_STORE_XC are valid on DPM_FORM_UNIPC stages only (form %d)", st->form);
   }
   if (b->eps_stride != 0 && b->eps_stride < b->n / b->batch)
     return fail(DPM_ERR_ARG, "stage_launch: eps_stride=%lld is smaller than a sample (%lld elements)",
@@ -130,6 +142,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   if (b->n == 0) return DPM_OK;
   if (dyn && (st->flags & DPM_F_NOISE))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with device-resident coefficients");
+  if (dyn && st->form == DPM_FORM_UNIPC)
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with device-resident coefficients");
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -218,9 +232,9 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
   for (int r0 = 0; r0 < n_req; ++r0) {
     if (done[r0]) continue;
     int cnt = 0;
-    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
+    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0], true)) {
       for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
-        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+        if (!done[r] && fusable_request(st[r], bs[r], true) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
           gs[cnt] = st[r];
           gb[cnt] = bs[r];
           gi[cnt++] = r;

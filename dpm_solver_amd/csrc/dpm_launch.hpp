@@ -173,11 +173,17 @@ inline bool plain_request(const dpm_buffers& b) {
 // groups, every buffer 16-byte aligned, a duplicate store only under classifier-free guidance.  The element sizes come from
 // the dtype codes: only 4- and 2-byte pairs fuse.  SDE stages (DPM_F_NOISE) fuse too, with kernels of their own
 // (stage_kernel_multi_noise, stage_kernel_het_noise: LIN1 / TWO); the callers keep them apart from the ODE stages.
-inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
+// UniPC stages (DPM_FORM_UNIPC) fuse in lockstep only (stage_kernel_multi): `per_request` = the heterogeneous launch, whose
+// kernel has no UniPC case -- there they run request by request -- and never with DPM_F_STORE_XC (x_out2 is then the
+// corrected state, which the fused kernels' duplicate store does not write).
+inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b, bool per_request = false) {
   if (st.flags & (DPM_F_THRESH | DPM_F_BLEND)) return false;
   if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
   const bool ms3_ok = !(st.flags & DPM_F_NOISE);
-  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && !(ms3_ok && st.form == DPM_FORM_MS3)) return false;
+  const bool unipc_ok = !per_request && !(st.flags & (DPM_F_NOISE | DPM_F_STORE_XC));
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && !(ms3_ok && st.form == DPM_FORM_MS3) &&
+      !(unipc_ok && st.form == DPM_FORM_UNIPC))
+    return false;
   if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b)) return false;
   const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
   if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
@@ -684,12 +690,52 @@ int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& str
   return launch_status("noise stage kernel launch failed");
 }
 
+// ---- a UniPC stage (DPM_FORM_UNIPC; checked by the caller: no thresholding / blend / noise / device-resident
+// coefficients): stage_kernel where the streaming family's vector conditions hold -- one tile per iteration, the nt mask of
+// the inputs-from-HBM situation, unguided or classifier-free, the evaluation state is the state --,
+// stage_kernel_scalar_unipc otherwise.  DPM_F_STORE_XC rides on the KExt flavour (x_out2).
+template <typename TS, typename TE, int GUIDE, bool XE>
+int launch_unipc(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
+  const KParams& p = op.p;
+  const KExt& ext = op.ext;
+  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
+  constexpr bool BUILT = GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
+  const bool vec = BUILT && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.h2, as) && aligned(op.xo, as) &&
+                   aligned(op.mo, as) && aligned(op.e0, ae) && aligned(op.e1, ae) && ext_vec_ok(op, b);
+  if (!vec) {
+    using ScalarUnipc = decltype(&stage_kernel_scalar_unipc<TS, TE>);
+    launch(reinterpret_cast<ScalarUnipc>(const_cast<void*>(dpm_catchall_scalar_unipc<TS, TE>())), scalar_grid(b->n, op.n_cu),
+           dim3(256), 0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext);
+  } else if constexpr (BUILT) {
+    const Tuning tn = tuning_for(b->opts);
+    const bool x0 = !tn.force_generic && x0_prologue_ok(*st);
+    const Shape sh = stream_grid(b->n, 1, op.n_cu, tn);
+    constexpr int NT = sizeof(TS) == 2 ? 1 : (sizeof(TE) == 4 ? 5 : 1);
+#define DPM_UNIPC_LAUNCH(SPEC_, EXT_)                                                                                       \
+  launch(stage_kernel<TS, TE, DPM_FORM_UNIPC, GUIDE, false, SPEC_, 1, NT, EXT_>, sh.grid, sh.block, 0, stream, op.x, op.xe, \
+         op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, stream.dyn, stream.skip)
+    if (op.use_ext) {
+      if (x0) DPM_UNIPC_LAUNCH(SPEC_NOISE_X0, true);
+      else DPM_UNIPC_LAUNCH(SPEC_GENERIC, true);
+    } else {
+      if (x0) DPM_UNIPC_LAUNCH(SPEC_NOISE_X0, false);
+      else DPM_UNIPC_LAUNCH(SPEC_GENERIC, false);
+    }
+#undef DPM_UNIPC_LAUNCH
+  }
+  return launch_status("unipc stage kernel launch failed");
+}
+
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
 int launch_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream) {
   const Operands<TS, TE> op(st, b);
-  if (st->flags & DPM_F_NOISE) return launch_noise<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
-  return (st->flags & DPM_F_THRESH) ? launch_thresh<TS, TE, FORM, GUIDE, XE>(st, b, stream, op)
-                                    : launch_stream<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
+  if constexpr (FORM == DPM_FORM_UNIPC) {
+    return launch_unipc<TS, TE, GUIDE, XE>(st, b, stream, op);
+  } else {
+    if (st->flags & DPM_F_NOISE) return launch_noise<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
+    return (st->flags & DPM_F_THRESH) ? launch_thresh<TS, TE, FORM, GUIDE, XE>(st, b, stream, op)
+                                      : launch_stream<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
+  }
 }
 
 // Launch shape of the fused kernel (profiles/r02_tune_multi.txt, 32 x [256,4,64,64], kernel-only per request-stage):
@@ -820,6 +866,7 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
   switch (st->form) {
     case DPM_FORM_LIN1: return DPM_MULTI(DPM_FORM_LIN1);
     case DPM_FORM_TWO: return DPM_MULTI(DPM_FORM_TWO);
+    case DPM_FORM_UNIPC: return DPM_MULTI(DPM_FORM_UNIPC);
     default: return DPM_MULTI(DPM_FORM_MS3);
   }
 #undef DPM_MULTI
@@ -914,6 +961,7 @@ int launch_form(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& s) {
     DPM_FORM_CASE(DPM_FORM_MS3)
     DPM_FORM_CASE(DPM_FORM_SS3T)
     DPM_FORM_CASE(DPM_FORM_DENOISE)
+    DPM_FORM_CASE(DPM_FORM_UNIPC)
 #undef DPM_FORM_CASE
   }
   return dpm_set_error(DPM_ERR_ARG, "unknown update form %d", st->form);
@@ -933,5 +981,9 @@ const void* dpm_catchall_scalar() {
 template <typename TS, typename TE>
 const void* dpm_catchall_scalar_noise() {
   return reinterpret_cast<const void*>(&stage_kernel_scalar_noise<TS, TE>);
+}
+template <typename TS, typename TE>
+const void* dpm_catchall_scalar_unipc() {
+  return reinterpret_cast<const void*>(&stage_kernel_scalar_unipc<TS, TE>);
 }
 #endif

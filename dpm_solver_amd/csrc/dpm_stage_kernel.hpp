@@ -193,10 +193,27 @@ __device__ __forceinline__ V mdiff(V a, V b, bool hm) {
   return a - b;
 }
 
+// UniPC stage (DPM_FORM_UNIPC, include/dpm_hip.h): the corrector of step i in its delta form on the predicted state x = x_i^p
+// -> xc, then the predictor of step i+1 (the LIN1 / TWO association) on xc.  Differences first, then coefficients; the
+// two sub-shapes (second-order corrector, second-order predictor) are wave-uniform flags of the stage record.
+template <typename V>
+__device__ __forceinline__ V combine_unipc(V x, V mn, V h1, V h2, const KParams& p, V& xc) {
+  const V d1 = mn - h1;
+  if (p.flags & DPM_F_UNIPC_DP)
+    xc = x + (p.c2 * (p.k2 * (h2 - h1)) - p.k1 * d1);
+  else
+    xc = x - p.k1 * d1;
+  if (p.flags & DPM_F_UNIPC_P2) return (p.cx * xc - p.c0 * mn) - p.c1 * (p.k0 * d1);
+  return p.cx * xc - p.c0 * mn;
+}
+
 // the exponential-integrator combination, reference association
 template <int FORM, typename V, typename TE = float>
 __device__ __forceinline__ V combine(V x, V mn, V h1, V h2, const KParams& p, bool hm = false) {
-  if (FORM == DPM_FORM_LIN1) {
+  if (FORM == DPM_FORM_UNIPC) {
+    V xc;
+    return combine_unipc(x, mn, h1, h2, p, xc);
+  } else if (FORM == DPM_FORM_LIN1) {
     return p.cx * x - p.c0 * mn;  // ref :573-576, :585-588
   } else if (FORM == DPM_FORM_TWO) {
     V D = p.k0 * mdiff<TE>(mn, h1, hm);
@@ -245,19 +262,25 @@ __device__ __forceinline__ bool form_needs_x(const KParams& p) {
 template <int FORM>
 __device__ __forceinline__ bool form_needs_h1(const KParams& p) {
   const int f = FORM == FORM_RT ? p.form : FORM;
-  return f == DPM_FORM_TWO || f == DPM_FORM_MS3 || f == DPM_FORM_SS3T;
+  return f == DPM_FORM_TWO || f == DPM_FORM_MS3 || f == DPM_FORM_SS3T || FORM == DPM_FORM_UNIPC;  // (never dispatched at run time)
 }
 template <int FORM>
 __device__ __forceinline__ bool form_needs_h2(const KParams& p) {
   const int f = FORM == FORM_RT ? p.form : FORM;
   return f == DPM_FORM_MS3 || f == DPM_FORM_SS3T;
 }
+// does this launch read h2?  The form's answer, except for UniPC, where only a second-order corrector does (wave-uniform)
+template <int FORM>
+__device__ __forceinline__ bool reads_h2(const KParams& p) {
+  if (FORM == DPM_FORM_UNIPC) return (p.flags & DPM_F_UNIPC_DP) != 0;
+  return form_needs_h2<FORM>(p);
+}
 
 template <int FORM>
 struct FormTraits {
   static constexpr bool needs_x = FORM != DPM_FORM_DENOISE;
-  static constexpr bool needs_h1 = FORM == DPM_FORM_TWO || FORM == DPM_FORM_MS3 || FORM == DPM_FORM_SS3T;
-  static constexpr bool needs_h2 = FORM == DPM_FORM_MS3 || FORM == DPM_FORM_SS3T;
+  static constexpr bool needs_h1 = FORM == DPM_FORM_TWO || FORM == DPM_FORM_MS3 || FORM == DPM_FORM_SS3T || FORM == DPM_FORM_UNIPC;
+  static constexpr bool needs_h2 = FORM == DPM_FORM_MS3 || FORM == DPM_FORM_SS3T || FORM == DPM_FORM_UNIPC;  // UniPC: see reads_h2
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -460,7 +483,9 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
     if (GUIDE == DPM_GUIDE_CFG) load_tile<(NT & 1) != 0>(e1, ge, split, v1[u]);
     if (GUIDE == DPM_GUIDE_CLASSIFIER) load_tile<(NT & 1) != 0>(g, gi, split, vg[u]);
     if (FT::needs_h1) load_tile<(NT & 1) != 0>(h1, gi, split, vh1[u]);
-    if (FT::needs_h2) load_tile<(NT & 1) != 0>(h2, gi, split, vh2[u]);
+    if constexpr (FORM == DPM_FORM_UNIPC) {
+      if (reads_h2<FORM>(p)) load_tile<(NT & 1) != 0>(h2, gi, split, vh2[u]);
+    } else if (FT::needs_h2) load_tile<(NT & 1) != 0>(h2, gi, split, vh2[u]);
     if (EXT && mask) {
       if (split) {  // mask, known image and noise in the state's split layout: whole 1 KiB runs per access
         const int64_t mtiles = mgroups / 256;
@@ -515,13 +540,23 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
     const int64_t gi = (t0 + u) * 256 + tile_lane();
     const bool split = can_split && (t0 + u) * 256 + 256 <= ngroups;
     float ox[EPT], om[EPT];
+    float oc[FORM == DPM_FORM_UNIPC ? EPT : 1];  // UniPC: the corrected state (DPM_F_STORE_XC)
 #pragma unroll
     for (int q = 0; q < EPT; q += 2) {
       const f32x2 z = {0.f, 0.f};
       const f32x2 mn = mnv[u][q / 2];
-      const f32x2 o = combine<FORM, f32x2, TE>(FT::needs_x ? f32x2{vx[u][q], vx[u][q + 1]} : z, mn,
+      f32x2 o;
+      if constexpr (FORM == DPM_FORM_UNIPC) {
+        f32x2 xc;
+        o = combine_unipc(f32x2{vx[u][q], vx[u][q + 1]}, mn, f32x2{vh1[u][q], vh1[u][q + 1]},
+                          reads_h2<FORM>(p) ? f32x2{vh2[u][q], vh2[u][q + 1]} : z, p, xc);
+        oc[q] = xc.x;
+        oc[q + 1] = xc.y;
+      } else {
+        o = combine<FORM, f32x2, TE>(FT::needs_x ? f32x2{vx[u][q], vx[u][q + 1]} : z, mn,
                                     FT::needs_h1 ? f32x2{vh1[u][q], vh1[u][q + 1]} : z,
                                     FT::needs_h2 ? f32x2{vh2[u][q], vh2[u][q + 1]} : z, p, hm);
+      }
       om[q] = mn.x;
       om[q + 1] = mn.y;
       ox[q] = o.x;
@@ -547,7 +582,12 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
     }
     if (gi < ngroups) {
       store_tile<(NT & 2) != 0>(xo, gi, split, ox);
-      if (EXT && xo2) store_tile<(NT & 2) != 0>(xo2, gi, split, ox);
+      if constexpr (FORM == DPM_FORM_UNIPC) {
+        if (EXT && xo2) {
+          if (p.flags & DPM_F_STORE_XC) store_tile<(NT & 2) != 0>(xo2, gi, split, oc);
+          else store_tile<(NT & 2) != 0>(xo2, gi, split, ox);
+        }
+      } else if (EXT && xo2) store_tile<(NT & 2) != 0>(xo2, gi, split, ox);
       // NT bit 3: the model value leaves by a non-temporal store, not written through (the fused launch, MultiShape)
       if (store_m) store_tile<(NT & 12) != 0, (NT & 8) == 0>(mo, gi, split, om);
     }
@@ -594,7 +634,8 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel(const TS* __re
       const float xev = XE ? (need_xe ? to_f32(xe[i]) : 0.f) : xv;
       const float mn = prologue<GUIDE, SPEC == SPEC_GENERIC ? (int)PM_RT : SPEC, float, TE>(
           xev, to_f32(e0[i]), GUIDE == DPM_GUIDE_CFG ? to_f32(e1[i]) : 0.f, GUIDE == DPM_GUIDE_CLASSIFIER ? to_f32(g[i]) : 0.f, p);
-      xo[i] = from_f32<TS>(combine<FORM, float, TE>(xv, mn, FT::needs_h1 ? to_f32(h1[i]) : 0.f, FT::needs_h2 ? to_f32(h2[i]) : 0.f, p,
+      xo[i] = from_f32<TS>(combine<FORM, float, TE>(xv, mn, FT::needs_h1 ? to_f32(h1[i]) : 0.f,
+                                                    FT::needs_h2 && reads_h2<FORM>(p) ? to_f32(h2[i]) : 0.f, p,
                                                     model_values_are_half<TE>(p)));
       if (store_m) mo[i] = from_f32<TS>(mn);
     }
@@ -857,14 +898,14 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het_noise(cons
 // pair: form and guidance are read from the stage record (wave-uniform branches), xe always points at the state the
 // network saw (= x when there is no separate one).
 // NOISE: the SDE epilogue (stage_kernel_scalar_noise), out += nz.scale * z of the element's flat index
-template <typename TS, typename TE, bool NOISE>
+template <typename TS, typename TE, bool NOISE, int FORM = FORM_RT>
 __device__ __forceinline__ void scalar_elements(const TS* __restrict__ x, const TS* __restrict__ xe, const TE* __restrict__ e0,
                                                 const TE* __restrict__ e1, const TE* __restrict__ g, const TS* __restrict__ h1,
                                                 const TS* __restrict__ h2, TS* __restrict__ xo, TS* __restrict__ mo, int64_t n,
                                                 const KParams& p, const KExt& ext, const KNoise& nz) {
   const bool need_xe = (p.flags & DPM_F_TO_X0) || p.model_type == DPM_MODEL_X_START || p.model_type == DPM_MODEL_V;
   const bool store_m = p.flags & DPM_F_STORE_M;
-  const bool nx = form_needs_x<FORM_RT>(p), nh1 = form_needs_h1<FORM_RT>(p), nh2 = form_needs_h2<FORM_RT>(p);
+  const bool nx = form_needs_x<FORM>(p), nh1 = form_needs_h1<FORM>(p), nh2 = reads_h2<FORM>(p);
   const bool cfg = p.guidance == DPM_GUIDE_CFG, clsg = p.guidance == DPM_GUIDE_CLASSIFIER;
   const bool hm = model_values_are_half<TE>(p);
   const TS* mask = static_cast<const TS*>(ext.mask);
@@ -877,7 +918,11 @@ __device__ __forceinline__ void scalar_elements(const TS* __restrict__ x, const 
     const float xv = nx ? to_f32(x[i]) : 0.f;
     const float xev = need_xe ? to_f32(xe[i]) : 0.f;
     const float mn = prologue<GUIDE_RT, PM_RT, float, TE>(xev, to_f32(e0[ie]), cfg ? to_f32(e1[ie]) : 0.f, clsg ? to_f32(g[i]) : 0.f, p);
-    float o = combine_any<FORM_RT, float, TE>(xv, mn, nh1 ? to_f32(h1[i]) : 0.f, nh2 ? to_f32(h2[i]) : 0.f, p, hm);
+    float o, xc = 0.f;
+    if constexpr (FORM == DPM_FORM_UNIPC)
+      o = combine_unipc(xv, mn, to_f32(h1[i]), nh2 ? to_f32(h2[i]) : 0.f, p, xc);
+    else
+      o = combine_any<FORM, float, TE>(xv, mn, nh1 ? to_f32(h1[i]) : 0.f, nh2 ? to_f32(h2[i]) : 0.f, p, hm);
     if constexpr (NOISE) o = o + nz.scale * noise1(nz, (uint64_t)i);
     if (mask) {
       o = to_f32(from_f32<TS>(o));  // the reference blends the stored state
@@ -885,7 +930,9 @@ __device__ __forceinline__ void scalar_elements(const TS* __restrict__ x, const 
     }
     const TS ov = from_f32<TS>(o);
     xo[i] = ov;
-    if (xo2) xo2[i] = ov;
+    if constexpr (FORM == DPM_FORM_UNIPC) {
+      if (xo2) xo2[i] = (p.flags & DPM_F_STORE_XC) ? from_f32<TS>(xc) : ov;
+    } else if (xo2) xo2[i] = ov;
     if (store_m) mo[i] = from_f32<TS>(mn);
   }
 }
@@ -916,6 +963,19 @@ __global__ __launch_bounds__(256) void stage_kernel_scalar_noise(const TS* __res
                                                                  TS* __restrict__ mo, int64_t n, const KParams p, KExt ext,
                                                                  const KNoise nz) {
   scalar_elements<TS, TE, true>(x, xe, e0, e1, g, h1, h2, xo, mo, n, p, ext, nz);
+}
+
+
+// the UniPC stages the vector family does not take (unaligned or ragged buffers with an extension, classifier guidance, a
+// separate evaluation state): one element per lane, the form fixed at compile time -- a kernel of its own, so that the
+// run-time dispatched catch-all kernels stay as they are
+template <typename TS, typename TE>
+__global__ __launch_bounds__(256) void stage_kernel_scalar_unipc(const TS* __restrict__ x, const TS* __restrict__ xe,
+                                                                 const TE* __restrict__ e0, const TE* __restrict__ e1,
+                                                                 const TE* __restrict__ g, const TS* __restrict__ h1,
+                                                                 const TS* __restrict__ h2, TS* __restrict__ xo,
+                                                                 TS* __restrict__ mo, int64_t n, const KParams p, KExt ext) {
+  scalar_elements<TS, TE, false, DPM_FORM_UNIPC>(x, xe, e0, e1, g, h1, h2, xo, mo, n, p, ext, KNoise{});
 }
 
 }  // namespace

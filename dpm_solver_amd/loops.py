@@ -230,6 +230,11 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     # produces x write both halves of that buffer instead (not possible when an opaque corrector edits x after it)
     dup = cfg and cxt is None and x.dim() > 0
     n_st = len(plan.stages)
+    # sample_unipc(return_intermediate=True): the list holds the CORRECTED states x_1 .. x_{K-1} -- the second store of the
+    # UniPC stages (DPM_F_STORE_XC), which owns x_out2: those launches leave the CFG duplicate to torch.cat -- then the last
+    # update's state (and the denoised one)
+    unipc_keep = keep and plan.unipc
+    n_upd = n_st - (1 if plan.stages[-1].form == L.FORM_DENOISE else 0)
     state, state2 = x, None
     tmp, tmp2 = None, None
     hist = [None] * max(plan.slots, 1)
@@ -247,12 +252,14 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
                 state = cxt(state, V["t_eval"][0], 0)
             elif blend is not None:
                 state = blend.apply(state if state.dtype == sd else state.to(sd), ps.t_eval, 0)
-            if keep:
+            if keep and not unipc_keep:
                 intermediates.append(state)
         h1 = hist[st.h1_slot] if st.h1_slot >= 0 else None
         h2 = hist[st.h2_slot] if st.h2_slot >= 0 else None
         ext = {}
-        if dup and i + 1 < n_st:
+        if unipc_keep and st.form == L.FORM_UNIPC:
+            ext["xc"] = True
+        elif dup and i + 1 < n_st:
             ext["dup"] = True
         if blend is not None and st.emits_state:
             ext["blend"] = blend.operands(x.shape, sd, device, ps.t_out, st.outer_step)
@@ -268,7 +275,9 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
             if cxt is not None:
                 t_cb = V["t_out"][i].reshape(1) if st.form == L.FORM_DENOISE else V["t_out"][i]
                 x_out = cxt(x_out, t_cb, st.outer_step)
-            if keep:
+            if unipc_keep and "xc_out" in ext:
+                intermediates.append(DV._in_layout_of(ext["xc_out"], x))
+            if keep and (not unipc_keep or i >= n_upd - 1):
                 intermediates.append(DV._in_layout_of(x_out, x))
             state, state2 = x_out, ext.get("x2")
             tmp, tmp2 = None, None

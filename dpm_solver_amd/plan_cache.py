@@ -30,6 +30,7 @@ class _Plan:
         self.stages = []
         self.stages64 = None                 # double-precision plans: the dpm_stage_f64 twin of every stage
         self.sde = desc.algorithm_type == L.ALGO_SDE_DPMSOLVERPP   # stages carry DPM_F_NOISE (DPM_Solver.sample_sde)
+        self.unipc = desc.algorithm_type == L.ALGO_UNIPC           # stages 1.. are DPM_FORM_UNIPC (DPM_Solver.sample_unipc)
         for i in range(n):
             st = L.Stage()
             L.check(L.lib.dpm_plan_stage(self.handle, i, C.byref(st)))
@@ -160,12 +161,12 @@ def get_plan(self, precision=0, **kw):
     plan = self._plans.get(key)
     if plan is None:
         d = L.PlanDesc()
-        d.algorithm_type = L.ALGO_SDE_DPMSOLVERPP if kw.get("sde") else self._algo
+        d.algorithm_type = L.ALGO_SDE_DPMSOLVERPP if kw.get("sde") else L.ALGO_UNIPC if kw.get("unipc") else self._algo
         d.method = L.METHOD[kw["method"]]
         d.order = int(kw["order"])
         d.steps = int(kw["steps"])
         d.skip_type = L.SKIP[kw["skip_type"]]
-        d.solver_type = L.SOLVER[kw["solver_type"]]
+        d.solver_type = L.UNIPC_VARIANT[kw["unipc"]] if kw.get("unipc") else L.SOLVER[kw["solver_type"]]
         d.lower_order_final = int(bool(kw["lower_order_final"]))
         d.denoise_to_zero = int(bool(kw["denoise_to_zero"]))
         d.model_type, d.guidance, d.guidance_scale = mt, gd, sc

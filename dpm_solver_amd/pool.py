@@ -57,12 +57,15 @@ class RequestPool:
 
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False,
-               sde=False, seed=None, generator=None):
+               sde=False, seed=None, generator=None, unipc=None):
         """Admit a request: `x` = its x_T, the rest as for `sample()` (multistep, singlestep and singlestep_fixed methods),
         validated with sample()'s errors.  `sde=True`: an SDE-DPM-Solver++ request -- `sample_sde`'s arguments, checks and
         seed rules (`seed`, or one draw from `generator` / torch's default CPU generator, made here).  Returns the request's
         handle (an int)."""
         s = self._s
+        if unipc:
+            raise NotImplementedError("request pool: UniPC requests (unipc=...) are not built -- the per-request-stage launch "
+                                      "has no UniPC form; sample them with sample_unipc / sample_unipc_requests")
         if not sde and (seed is not None or generator is not None):
             raise ValueError("request pool: `seed` / `generator` belong to an SDE request (sde=True)")
         if sde:

@@ -40,6 +40,7 @@ from . import loops as _loops
 from . import plan_cache as _plan_cache
 from . import pool as _pool
 from . import sde as _sde
+from . import unipc as _unipc
 from . import updates as _updates
 from .capture import GraphedSample
 from .correctors import MaskBlend  # noqa: F401  (part of this module's namespace since round 2)
@@ -585,7 +586,7 @@ class DPM_Solver:
     _auto_captured = _capture.auto_captured
 
     def _sample_plan(self, x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero, solver_type,
-                     sde=False):
+                     sde=False, unipc=None):
         """The plan of a multistep / singlestep / singlestep_fixed `sample()` call, with the reference's argument checks and
         errors (shared by sample() and the request pool)."""
         if method == 'multistep':
@@ -622,7 +623,8 @@ class DPM_Solver:
         plan = self._get_plan(precision=self._precision(self._sdtype(x)), method=method, order=order, steps=steps,
                               skip_type=skip_type, solver_type=plan_solver_type,
                               lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
-                              t_T=float(t_T), t_0=float(t_0), **({"sde": True} if sde else {}))
+                              t_T=float(t_T), t_0=float(t_0), **({"sde": True} if sde else {}),
+                              **({"unipc": unipc} if unipc else {}))
         if plan_solver_type is not solver_type and any(st.form in (L.FORM_TWO, L.FORM_SS3T) for st in plan.stages):
             raise ValueError("'solver_type' must be either 'dpmsolver' or 'taylor', got {}".format(solver_type))
         return plan
@@ -668,6 +670,8 @@ class DPM_Solver:
 
     sample_sde = _sde.sample_sde
     sample_sde_requests = _sde.sample_sde_requests
+    sample_unipc = _unipc.sample_unipc
+    sample_unipc_requests = _unipc.sample_unipc_requests
 
     def sample_requests(self, xs, **sample_kwargs):
         """(extension) `sample()` for several independent requests that are in flight together -- a server's batch of

@@ -99,6 +99,15 @@ def main():
         assert torch.equal(done[h_sde], zs[0]) and torch.equal(done[h_ode], solver.sample(xs[1], steps=12, order=2))
     print("sample_sde_requests / request_pool(sde=True): %d requests, identical to sample_sde() of each" % len(zs))
 
+    # UniPC: the corrector re-does every step with the model value the next step needs anyway -- no extra evaluation,
+    # no extra launch (corrector and next predictor share one stage kernel)
+    with torch.no_grad():
+        u = solver.sample_unipc(x_T, steps=20, order=2, variant="bh2")
+        us = solver.sample_unipc_requests(xs, steps=20)
+        assert all(torch.equal(a, solver.sample_unipc(x, steps=20)) for a, x in zip(us, xs))
+    print("sample_unipc: differs from the 2M sample by %.3g of its scale; sample_unipc_requests: %d requests, identical"
+          % (float((u - solver.sample(x_T, steps=20)).abs().max() / u.abs().max()), len(us)))
+
     # DiffEdit / inpainting: keep the masked-out region on the known image, noised to the current level
     mask = (torch.rand(64, 64, device=dev) > 0.5).float()
     known = torch.randn(B, 4, 64, 64, device=dev)

@@ -57,11 +57,14 @@ extern "C" {
    with its Gaussian term generated inside the stage kernel (see "noise contract" below; no struct changed size).
    204 dpm_stage_launch_multi / dpm_plan_run_multi fuse DPM_F_NOISE stages too -- lockstep and per-request stages -- with the
    seed of every request taken from its own bs[r].opts (no entry point added, no struct changed).
+   205 DPM_ALGO_UNIPC, DPM_SOLVER_UNIPC_BH1 / _BH2, DPM_FORM_UNIPC, DPM_F_UNIPC_DP / _P2, DPM_F_STORE_XC: UniPC sampling with
+   the corrector of step i and the predictor of step i+1 in ONE stage launch (see DPM_FORM_UNIPC; no entry point added, no
+   struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 204
+#define DPM_HIP_VERSION 205
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -81,8 +84,16 @@ enum {
 enum { DPM_ALGO_DPMSOLVER = 0, DPM_ALGO_DPMSOLVERPP = 1,          /* algorithm_type, ref :342,:406 */
        DPM_ALGO_SDE_DPMSOLVERPP = 2 /* version 203: the stochastic multistep DPM-Solver++ ("DPM++ 2M SDE", diffusers'
                                        sde-dpmsolver++).  dpm_plan_create only (method multistep, order 1 or 2, fp32
-                                       scalars, no thresholding); the per-update coefficient builders reject it */ };
-enum { DPM_SOLVER_DPMSOLVER = 0, DPM_SOLVER_TAYLOR = 1 };         /* solver_type,    ref :611      */
+                                       scalars, no thresholding); the per-update coefficient builders reject it */,
+       DPM_ALGO_UNIPC = 3 /* version 205: UniPC (Zhao et al. 2023; diffusers' UniPCMultistepScheduler) in the data-prediction
+                             form, predictor AND corrector.  dpm_plan_create only (method multistep, order 1 or 2, fp32
+                             scalars, no thresholding; solver_type = DPM_SOLVER_UNIPC_BH1 / _BH2); the per-update coefficient
+                             builders reject it.  The plan is the multistep DPM-Solver++ plan -- one stage per network
+                             evaluation, same times and buffer roles -- with the step orders o_i = min(order, i, steps + 1 - i)
+                             (lower_order_final; else min(order, i)) and stages 1 .. steps-1 of form DPM_FORM_UNIPC; every
+                             scalar is evaluated in double and rounded once */ };
+enum { DPM_SOLVER_DPMSOLVER = 0, DPM_SOLVER_TAYLOR = 1,           /* solver_type,    ref :611      */
+       DPM_SOLVER_UNIPC_BH1 = 2, DPM_SOLVER_UNIPC_BH2 = 3 /* version 205, DPM_ALGO_UNIPC only: UniPC's B(h) = -h | expm1(-h) */ };
 enum { DPM_METHOD_MULTISTEP = 0, DPM_METHOD_SINGLESTEP = 1, DPM_METHOD_SINGLESTEP_FIXED = 2 }; /* ref :1171,:1214 */
 enum { DPM_SKIP_TIME_UNIFORM = 0, DPM_SKIP_LOGSNR = 1, DPM_SKIP_TIME_QUADRATIC = 2 };          /* ref :468-478    */
 enum { DPM_MODEL_NOISE = 0, DPM_MODEL_X_START = 1, DPM_MODEL_V = 2, DPM_MODEL_SCORE = 3 };     /* ref :288-298    */
@@ -100,7 +111,23 @@ enum {
   DPM_FORM_MS3 = 2,     /* multistep third order (ref :879-903)                                              */
   DPM_FORM_SS3T = 3,    /* singlestep third order, 'taylor' final combination (ref :741-750,:780-789)        */
   DPM_FORM_DENOISE = 4, /* out = mn  (denoise_to_zero, ref :541-545,:1235-1237)                              */
-  DPM_FORM_COUNT = 5
+  DPM_FORM_UNIPC = 5,   /* version 205.  UniPC stage i (1 <= i < steps): the corrector of step i, then the predictor of step
+                           i+1 on the corrected state, which never leaves the registers.  x = x_i^p (the state the network
+                           saw: x = xe), mn = m_i, h1 = m_{i-1}, h2 = m_{i-2} (DPM_F_UNIPC_DP only):
+                             d1 = mn - h1
+                             xc = x + (c2 * (k[2] * (h2 - h1)) - k[1] * d1)     with DPM_F_UNIPC_DP (second-order corrector)
+                             xc = x - k[1] * d1                                  without         (first-order corrector)
+                             out = (cx * xc - c0 * mn) - c1 * (k[0] * d1)        with DPM_F_UNIPC_P2 (second-order predictor)
+                             out = cx * xc - c0 * mn                             without         (first-order predictor)
+                           fp32, one rounding per operation, one rounding of out (and of xc, DPM_F_STORE_XC) to the state dtype.
+                           With h = lambda_i - lambda_{i-1}, B = -h (bh1) | expm1(-h) (bh2), r = (lambda_{i-2} - lambda_{i-1}) / h
+                           and rho^c the solution of [[1, 1], [r, 1]] rho = [b_1, b_2] (rho^c = [1/2] in first order):
+                             c2 = alpha_i B (1/2 - rho^c_1), k[1] = alpha_i B rho^c_last, k[2] = 1 / r -- the published corrector
+                             x_i = xbar_i - alpha_i B (rho^c_1 D_p + rho^c_2 (m_i - m_{i-1})) minus the published predictor
+                             x_i^p = xbar_i - alpha_i B D_p / 2, D_p = (m_{i-2} - m_{i-1}) / r;
+                             cx, c0, c1, k[0]: the DPM_FORM_LIN1 / _TWO scalars of step i+1 with c1 = alpha_{i+1} B_{i+1} / 2.
+                           No thresholding, mask blend, noise, double state or device-resident coefficients: DPM_ERR_UNSUPPORTED */
+  DPM_FORM_COUNT = 6
 };
 
 /* dpm_stage.flags */
@@ -124,6 +151,12 @@ enum {
      25 significant bits);  element i takes the pair p = (i & 3) >> 1:
      z = sqrt(-2 ln u(r[2p])) * (i even ? cos : sin)(2 pi u(r[2p + 1]))
      in fp32 (logf, sqrtf, the hardware sine / cosine of u in revolutions), the same device function on every route. */
+
+#define DPM_F_UNIPC_DP 128u  /* version 205, DPM_FORM_UNIPC: the corrector is second order (reads h2)                       */
+#define DPM_F_UNIPC_P2 256u  /* DPM_FORM_UNIPC: the predictor of the next step is second order                              */
+#define DPM_F_STORE_XC 512u  /* DPM_FORM_UNIPC: dpm_buffers.x_out2 receives the CORRECTED state xc (the solver state x_i a
+                                caller of return_intermediate wants) instead of a second copy of x_out; never set by the
+                                planner.  Such a stage runs on its own in a multi-request launch                          */
 
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
@@ -210,7 +243,8 @@ typedef struct dpm_buffers {
   int32_t eps_dtype;   /* DPM_DTYPE_* of e0, e1, g                                               */
   /* ---- optional extensions (zero / NULL = off) ---- */
   void* x_out2;        /* second copy of x_out: the other half of the [2B,...] network input under
-                          classifier-free guidance (replaces torch.cat([x]*2), ref :326)   [n] state dtype */
+                          classifier-free guidance (replaces torch.cat([x]*2), ref :326)   [n] state dtype;
+                          with DPM_F_STORE_XC: the corrected state of a DPM_FORM_UNIPC stage instead       */
   int64_t eps_stride;  /* elements between consecutive samples of e0 / e1 (0 = contiguous): the network output
                           is a channel slice out[:, :C] of a learned-variance model's [B,2C,H,W] output
                           (runners/diffusion.py:596-603); a sample's C*H*W elements stay contiguous      */
@@ -279,7 +313,7 @@ typedef struct dpm_plan_desc {
   int32_t order;             /* 1..3                              */
   int32_t steps;             /* NFE                               */
   int32_t skip_type;         /* DPM_SKIP_*                        */
-  int32_t solver_type;       /* DPM_SOLVER_*                      */
+  int32_t solver_type;       /* DPM_SOLVER_* (DPM_ALGO_UNIPC: _UNIPC_BH1 / _UNIPC_BH2) */
   int32_t lower_order_final; /* bool                              */
   int32_t denoise_to_zero;   /* bool                              */
   int32_t model_type;        /* DPM_MODEL_*                       */
