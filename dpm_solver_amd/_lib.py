@@ -274,8 +274,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 205:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 205 -- stale library, rebuild"
+if lib.dpm_version() < 206:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 206 -- stale library, rebuild"
                       % lib.dpm_version())
 
 

@@ -212,15 +212,21 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
 
 namespace {
 // May a request that passes fusable_request (dpm_launch.hpp) join the heterogeneous fused launch (stage_kernel_het) of
-// request 0 of a group?  They must agree on the fields that are template arguments or kernel-wide scalars.
+// request 0 of a group?  They must agree on the fields that are template arguments or kernel-wide scalars.  (Which of MS3
+// and UNIPC a group takes is decided as it fills: het_third_form.)
 bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b) {
   return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && b.n == b0.n && b.batch == b0.batch &&
          s.model_type == s0.model_type && s.guidance == s0.guidance &&
          (s.flags & (DPM_F_TO_X0 | DPM_F_NOISE)) == (s0.flags & (DPM_F_TO_X0 | DPM_F_NOISE));  // SDE stages apart from ODE ones
 }
 
+// MS3 and UNIPC records never share a group -- stage_kernel_het dispatches {LIN1, TWO, MS3}, stage_kernel_het_unipc {LIN1, TWO,
+// UNIPC}: the form of the two a record brings, 0 for the forms every group takes
+int het_third_form(const dpm_stage& s) { return s.form == DPM_FORM_MS3 || s.form == DPM_FORM_UNIPC ? s.form : 0; }
+
 // dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
-// HET_MAX (first come, first grouped), launch the rest one by one
+// HET_MAX (first come, first grouped; the first MS3 or UNIPC record to join a group closes it to the other form, whose
+// records wait for a later group), launch the rest one by one
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r])) return rc;
@@ -231,10 +237,13 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
   int gi[HET_MAX];
   for (int r0 = 0; r0 < n_req; ++r0) {
     if (done[r0]) continue;
-    int cnt = 0;
-    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0], true)) {
+    int cnt = 0, third = 0;
+    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
       for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
-        if (!done[r] && fusable_request(st[r], bs[r], true) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+          const int f = het_third_form(st[r]);
+          if (f && third && f != third) continue;
+          if (f) third = f;
           gs[cnt] = st[r];
           gb[cnt] = bs[r];
           gi[cnt++] = r;

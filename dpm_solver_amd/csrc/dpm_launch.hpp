@@ -173,14 +173,19 @@ inline bool plain_request(const dpm_buffers& b) {
 // groups, every buffer 16-byte aligned, a duplicate store only under classifier-free guidance.  The element sizes come from
 // the dtype codes: only 4- and 2-byte pairs fuse.  SDE stages (DPM_F_NOISE) fuse too, with kernels of their own
 // (stage_kernel_multi_noise, stage_kernel_het_noise: LIN1 / TWO); the callers keep them apart from the ODE stages.
-// UniPC stages (DPM_FORM_UNIPC) fuse in lockstep only (stage_kernel_multi): `per_request` = the heterogeneous launch, whose
-// kernel has no UniPC case -- there they run request by request -- and never with DPM_F_STORE_XC (x_out2 is then the
-// corrected state, which the fused kernels' duplicate store does not write).
-inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b, bool per_request = false) {
+// UniPC stages (DPM_FORM_UNIPC) fuse in lockstep (stage_kernel_multi) and at any position (the heterogeneous launch,
+// stage_kernel_het_unipc), never with DPM_F_STORE_XC (x_out2 is then the corrected state, which the fused kernels'
+// duplicate store does not write).
+// Grouping of a per-request-stage call (stage_launch_multi_het, dpm_kernels.hip) is deterministic -- first come, first
+// grouped: the first request not yet launched opens a group, and every later fusable request that agrees with it on dtypes,
+// n, batch, model type, guidance kind, DPM_F_TO_X0 and DPM_F_NOISE joins, in call order, up to HET_MAX.  LIN1 and TWO records
+// join any ODE group; MS3 and UNIPC records never share one (no kernel dispatches both): the first record of either form
+// to join decides which of the two the group takes, records of the other form wait for a later group.
+inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
   if (st.flags & (DPM_F_THRESH | DPM_F_BLEND)) return false;
   if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
   const bool ms3_ok = !(st.flags & DPM_F_NOISE);
-  const bool unipc_ok = !per_request && !(st.flags & (DPM_F_NOISE | DPM_F_STORE_XC));
+  const bool unipc_ok = !(st.flags & (DPM_F_NOISE | DPM_F_STORE_XC));
   if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && !(ms3_ok && st.form == DPM_FORM_MS3) &&
       !(unipc_ok && st.form == DPM_FORM_UNIPC))
     return false;
@@ -874,8 +879,10 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
 
 // ---- heterogeneous fused launch (stage_kernel_het): request r advanced by st[r].  The caller (dpm_kernels.hip) has
 // grouped the requests: every one passes fusable_request, and they agree on dtypes, n, batch, model type, guidance kind,
-// DPM_F_TO_X0 and DPM_F_NOISE (a group of SDE stages takes stage_kernel_het_noise, each request with its own KNoise).  Here: the prologue (compile-time only when every request may run it), the smallest form set that
-// covers the group, the launch shape of the lockstep kernel (MultiShape, XCD-contiguous remap).
+// DPM_F_TO_X0 and DPM_F_NOISE (a group of SDE stages takes stage_kernel_het_noise, each request with its own KNoise), and holds
+// MS3 or UNIPC records, never both (a group with a UNIPC record takes stage_kernel_het_unipc).  Here: the prologue
+// (compile-time only when every request may run it), the smallest form set that covers the group, the launch shape of the
+// lockstep kernel (MultiShape, XCD-contiguous remap).
 template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC>
 void launch_het_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
   launch(stage_kernel_het<TS, TE, FORMS, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c,
@@ -887,6 +894,11 @@ void launch_het_noise_spec(const HetNoiseArgs& a, const FusedShape& sh, const La
   launch(stage_kernel_het_noise<TS, TE, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, a);
 }
 
+template <typename TS, typename TE, int GUIDE, int SPEC>
+void launch_het_unipc_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
+  launch(stage_kernel_het_unipc<TS, TE, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, a);
+}
+
 template <typename TS, typename TE>
 int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
   if (n_req < 1 || n_req > HET_MAX)
@@ -895,7 +907,7 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
   HetNoiseArgs an;  // (the ODE kernels take its first member)
   std::memset(&an, 0, sizeof an);
   HetArgs& a = an.h;
-  bool ms3 = false;
+  bool ms3 = false, unipc = false;
   const bool sde = (st[0].flags & DPM_F_NOISE) != 0;
   bool noise = !tn.force_generic;
   for (int r = 0; r < n_req; ++r) {
@@ -904,8 +916,11 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
     a.p[r] = make_params(&st[r]);
     if (sde) an.nz[r] = noise_of(st[r], bs[r]);
     ms3 = ms3 || st[r].form == DPM_FORM_MS3;
+    unipc = unipc || st[r].form == DPM_FORM_UNIPC;
     noise = noise && x0_prologue_ok(st[r]);
   }
+  if (unipc && (ms3 || sde))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a UniPC stage grouped with a third-order or an SDE stage");
   const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, MultiShape<TS, TE>::U, tn, false);
   a.n = bs[0].n;
   a.nreq = (uint32_t)n_req;
@@ -924,6 +939,14 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
     } else {
       if (cfg) launch_het_noise_spec<TS, TE, DPM_GUIDE_CFG, SPEC_GENERIC>(an, sh, c);
       else launch_het_noise_spec<TS, TE, DPM_GUIDE_NONE, SPEC_GENERIC>(an, sh, c);
+    }
+  } else if (unipc) {
+    if (noise) {
+      if (cfg) launch_het_unipc_spec<TS, TE, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, sh, c);
+      else launch_het_unipc_spec<TS, TE, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, sh, c);
+    } else {
+      if (cfg) launch_het_unipc_spec<TS, TE, DPM_GUIDE_CFG, SPEC_GENERIC>(a, sh, c);
+      else launch_het_unipc_spec<TS, TE, DPM_GUIDE_NONE, SPEC_GENERIC>(a, sh, c);
     }
   } else if (ms3) DPM_HET(HET_FORMS_3);
   else DPM_HET(HET_FORMS_2);

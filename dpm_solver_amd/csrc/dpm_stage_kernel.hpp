@@ -1,6 +1,6 @@
 // dpm_stage_kernel.hpp -- the streaming stage kernels: per-stage scalars (KParams), prologues, update forms, the KExt
-// extensions, stage_kernel / stage_kernel_multi / stage_kernel_het / stage_kernel_scalar and their noise flavours (part of
-// dpm_device.hpp; include that)
+// extensions, stage_kernel / stage_kernel_multi / stage_kernel_het / stage_kernel_scalar, their noise flavours and the
+// heterogeneous UniPC kernel (part of dpm_device.hpp; include that)
 #pragma once
 
 namespace {
@@ -889,6 +889,53 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het_noise(cons
     case DPM_FORM_LIN1: DPM_HET_TILES(DPM_FORM_LIN1); break;
     case DPM_FORM_TWO: DPM_HET_TILES(DPM_FORM_TWO); break;
     default: break;  // (the host groups LIN1 / TWO only)
+  }
+#undef DPM_HET_TILES
+}
+
+// UniPC requests in flight (DPM_FORM_UNIPC stages at different positions): stage_kernel_het with a UniPC case.  A UniPC plan is
+// a first-order stage, then UniPC stages, so a pool of UniPC requests always holds LIN1 records next to UNIPC ones, and plain
+// 2M requests of the same pool bring TWO records: the form set is {LIN1, TWO, UNIPC} -- a newly admitted request costs no
+// launch of its own.  The two sub-shapes of a UniPC stage (DPM_F_UNIPC_DP: second-order corrector, reads h2; DPM_F_UNIPC_P2:
+// second-order predictor) are wave-uniform bits of the request's record (combine_unipc, reads_h2), so stage-1, steady and
+// tail requests share the launch.  HetArgs as it is, read in place; its own family, so that stage_kernel_het stays as it is
+// (MS3 and UNIPC never share a group: the host keeps them apart).
+// (The three heterogeneous kernels repeat their preamble on purpose: with it in a shared force-inlined helper six
+// stage_kernel_het instantiations -- fp32 state, 2-byte network output, CFG -- come out with other listings.)
+template <typename TS, typename TE, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_het_unipc(const HetArgs args) {
+  static_assert(GUIDE != DPM_GUIDE_CLASSIFIER, "unipc: no classifier guidance");
+  (void)args;
+  const HetArgs& a = *(const HetArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  const int64_t ngroups = a.n / EPT;
+  const uint32_t total = a.nreq * a.spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (a.xcd_span && in_xcd >= a.xcd_span) return;
+  const uint32_t v = a.xcd_span ? (b & 7u) * a.xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = v / a.spr;
+  const int64_t t0 = (int64_t)(v - r * a.spr) * U;
+  const KParams& p = a.p[r];
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = a.xo2[r];
+  const TS* x = static_cast<const TS*>(a.x[r]);
+  const TE* e0 = static_cast<const TE*>(a.e0[r]);
+  const TE* e1 = static_cast<const TE*>(a.e1[r]);
+  const TS* h1 = static_cast<const TS*>(a.h1[r]);
+  const TS* h2 = static_cast<const TS*>(a.h2[r]);
+  TS* xo = static_cast<TS*>(a.xo[r]);
+  TS* mo = static_cast<TS*>(a.mo[r]);
+#define DPM_HET_TILES(F_) \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP>(x, nullptr, e0, e1, nullptr, h1, h2, xo, mo, ngroups, t0, p, ext)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_HET_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_HET_TILES(DPM_FORM_TWO); break;
+    case DPM_FORM_UNIPC: DPM_HET_TILES(DPM_FORM_UNIPC); break;
+    default: break;  // (the host groups LIN1 / TWO / UNIPC only)
   }
 #undef DPM_HET_TILES
 }

@@ -1,7 +1,8 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
 // translation unit: compiled ten times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
-//   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het)
+//   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
+//               stage_kernel_het_noise, stage_kernel_het_unipc)
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1>"
 #endif

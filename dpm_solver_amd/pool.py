@@ -18,6 +18,12 @@ requests its heterogeneous kernel covers and launches the rest one by one.  Ever
 resolved at submission and travels in a dpm_launch_opts of the request's own, pointed to by its dpm_buffers entry of every
 tick -- never by the launch records, which finished requests hand on to later ones.  The library fuses SDE stages in groups
 of their own, next to the ODE groups of the same tick; the result is bit-identical to `sample_sde(x_T, seed=..., ...)`.
+
+`submit_unipc(x_T, steps=20, order=2, variant='bh2', ...)` admits a UniPC request (`sample_unipc`'s arguments and checks, minus
+`return_intermediate`).  Its plan is a first-order stage followed by DPM_FORM_UNIPC stages, which the heterogeneous launch
+fuses at any position next to the first- and second-order stages of other requests (stage_kernel_het_unipc), so a pool of
+UniPC requests -- or of UniPC and 2M requests -- is one launch per tick and 16 requests; the result is bit-identical to
+`sample_unipc(x_T, ...)`.  One pool may hold ODE, SDE and UniPC requests at once.
 """
 import ctypes as C
 
@@ -26,6 +32,7 @@ import torch
 from . import _device as DV
 from . import _lib as L
 from . import sde as _sde
+from . import unipc as _unipc
 from .launch_list import _FastRun, _bind_outputs
 from .plan_cache import _Cloning
 
@@ -64,8 +71,8 @@ class RequestPool:
         handle (an int)."""
         s = self._s
         if unipc:
-            raise NotImplementedError("request pool: UniPC requests (unipc=...) are not built -- the per-request-stage launch "
-                                      "has no UniPC form; sample them with sample_unipc / sample_unipc_requests")
+            raise NotImplementedError("request pool: submit() takes sample()'s arguments; admit a UniPC request with "
+                                      "submit_unipc(x, steps=..., order=..., variant=...)")
         if not sde and (seed is not None or generator is not None):
             raise ValueError("request pool: `seed` / `generator` belong to an SDE request (sde=True)")
         if sde:
@@ -88,6 +95,42 @@ class RequestPool:
                                       "sample()")
         if method not in _METHODS:
             raise ValueError("Got wrong method {}".format(method))
+        like = self._check_x(x)
+        t_0 = 1. / s.noise_schedule.total_N if t_end is None else t_end
+        t_T = s.noise_schedule.T if t_start is None else t_start
+        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        with torch.no_grad():
+            plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero,
+                                  solver_type, sde=bool(sde))
+        return self._admit(x, like, plan, seed if sde else None)
+
+    def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
+                     corrector=True, lower_order_final=True, denoise_to_zero=False):
+        """Admit a UniPC request: `x` = its x_T, the rest as for `sample_unipc()` (no `return_intermediate`), validated with
+        sample_unipc()'s errors in its order, then the pool's own (the device requirement, a non-tensor, a shape / dtype /
+        device other than the pool's) -- all before any device work.  `corrector=False` (variant 'bh2') admits sample()'s
+        multistep DPM-Solver++ plan, as sample_unipc runs it.  Returns the request's handle."""
+        s = self._s
+        _unipc.check_solver(s, order, variant)
+        t_0, t_T = _unipc._times(s, t_start, t_end)
+        if not torch.is_tensor(x):
+            self._check_x(x)          # (check_state and the planner read x.dtype: a non-tensor gets the pool's error here)
+        _unipc.check_state(s, x)
+        if not corrector:
+            if variant != 'bh2':
+                raise NotImplementedError("sample_unipc: corrector=False with variant='bh1' (the predictor alone is built for "
+                                          "'bh2', where it is DPM-Solver++ 2M)")
+            return self.submit(x, steps=steps, t_start=t_start, t_end=t_end, order=order, skip_type=skip_type,
+                               method='multistep', lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero,
+                               solver_type='dpmsolver')
+        with torch.no_grad():
+            plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
+                                  'dpmsolver', unipc=variant)
+        return self._admit(x, self._check_x(x), plan, None)
+
+    def _check_x(self, x):
+        """the pool's own checks of a request's x_T: on the GPU, a tensor of the pool's shape, dtype and device; returns
+        (shape, dtype, device)"""
         DV._require_gpu(x)
         if not torch.is_tensor(x) or x.dim() == 0 or x.numel() == 0:
             raise ValueError("request pool: x must be a tensor with at least one dimension and one element")
@@ -95,12 +138,11 @@ class RequestPool:
         if self._like is not None and like != self._like:
             raise ValueError("request pool: x of shape %s, dtype %s on %s does not match the pool's %s, %s on %s"
                              % (like + self._like))
-        t_0 = 1. / s.noise_schedule.total_N if t_end is None else t_end
-        t_T = s.noise_schedule.T if t_start is None else t_start
-        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
-        with torch.no_grad():
-            plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, method, lower_order_final, denoise_to_zero,
-                                  solver_type, sde=bool(sde))
+        return like
+
+    def _admit(self, x, like, plan, seed):
+        """a checked request with its plan joins the pool (seed: an SDE request's); returns its handle"""
+        s = self._s
         sd = s._sdtype(x)
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
@@ -114,8 +156,8 @@ class RequestPool:
             return h
         q = _Request()
         q.x, q.plan, q.i, q.sd = x, plan, 0, sd
-        q.seed = seed if sde else None
-        q.opts = L.LaunchOpts() if sde else None      # its own options: the solver's + its seed (step)
+        q.seed = seed
+        q.opts = L.LaunchOpts() if seed is not None else None      # its own options: the solver's + its seed (step)
         self._active[h] = q
         return h
 

@@ -107,6 +107,19 @@ def main():
         assert all(torch.equal(a, solver.sample_unipc(x, steps=20)) for a, x in zip(us, xs))
     print("sample_unipc: differs from the 2M sample by %.3g of its scale; sample_unipc_requests: %d requests, identical"
           % (float((u - solver.sample(x_T, steps=20)).abs().max() / u.abs().max()), len(us)))
+    # ... and in a pool (continuous batching): UniPC requests admitted while others are mid-trajectory, next to a 2M request;
+    # every tick is one fused launch whatever the positions
+    with torch.no_grad():
+        pool = solver.request_pool()
+        handles = {pool.submit_unipc(xs[0], steps=20): solver.sample_unipc(xs[0], steps=20)}
+        pool.step()
+        handles[pool.submit_unipc(xs[1], steps=12, variant="bh1")] = solver.sample_unipc(xs[1], steps=12, variant="bh1")
+        handles[pool.submit(xs[0], steps=10, order=2)] = solver.sample(xs[0], steps=10, order=2)
+        done = {}
+        while pool:
+            done.update(pool.step())
+        assert all(torch.equal(done[h], want) for h, want in handles.items())
+    print("request_pool().submit_unipc: %d requests at different positions, identical to their own calls" % len(done))
 
     # DiffEdit / inpainting: keep the masked-out region on the known image, noised to the current level
     mask = (torch.rand(64, 64, device=dev) > 0.5).float()

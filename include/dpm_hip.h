@@ -60,11 +60,13 @@ extern "C" {
    205 DPM_ALGO_UNIPC, DPM_SOLVER_UNIPC_BH1 / _BH2, DPM_FORM_UNIPC, DPM_F_UNIPC_DP / _P2, DPM_F_STORE_XC: UniPC sampling with
    the corrector of step i and the predictor of step i+1 in ONE stage launch (see DPM_FORM_UNIPC; no entry point added, no
    struct changed).
+   206 dpm_stage_launch_multi with per-request stages fuses DPM_FORM_UNIPC stages too, at any position and next to first- and
+   second-order stages (UniPC requests in continuous batching; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 205
+#define DPM_HIP_VERSION 206
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -382,13 +384,17 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    Per-request stages (version 202): with bs[0].opts->per_request_stages == 1, `st` points at n_req stage records and
    request r is advanced by st[r] -- requests that arrived at different times, at different positions of plans with
    different step counts or orders (continuous batching).  Every request is checked as dpm_stage_launch checks it (same
-   error texts; nothing is launched when one fails).  Requests whose stage is first-order, 2M-style second-order (TWO) or
-   multistep third-order (MS3), without thresholding, mask blend or classifier guidance, whose evaluation state is the
+   error texts; nothing is launched when one fails).  Requests whose stage is first-order, 2M-style second-order (TWO),
+   multistep third-order (MS3) or -- version 206 -- UniPC (DPM_FORM_UNIPC without DPM_F_STORE_XC, whatever its DPM_F_UNIPC_DP /
+   _P2 bits), without thresholding, mask blend or classifier guidance, whose evaluation state is the
    state and whose buffers are dense and 16-byte aligned, are fused -- 16 per launch: the records travel in the kernel's
    arguments, within HIP's 4 KiB -- with every other
    request that agrees with them on dtypes, n, batch, model type, guidance kind, DPM_F_TO_X0 and DPM_F_NOISE (SDE stages
    -- LIN1 / TWO -- form groups of their own, each request with its own stage index, scale and seed); the rest are launched
-   one by one. Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
+   one by one.  Groups fill in call order (first come, first grouped).  MS3 and UNIPC stages never share a group: the first
+   of the two forms to join a group decides which it takes, stages of the other form open a later group; first- and
+   second-order stages join either, so a pool of UniPC requests -- first-order at stage 0, UNIPC afterwards -- and 2M
+   requests is one launch per 16 requests. Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
