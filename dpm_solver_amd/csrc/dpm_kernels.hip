@@ -65,10 +65,9 @@ int launch_fused(const PairUnits& p, const dpm_stage* st, const dpm_buffers* bs,
   return p.fused(st, bs, n_req, stream, ev_start, ev_stop);
 }
 
-// The argument checks of one request (st and b not null): DPM_OK, or the error of the first check that fails -- set
-// (dpm_set_error) when `report`.  dpm_stage_launch_multi_ev asks without it whether a request may join a fused launch.
-int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool report = true) {
-  auto fail = [report](int code, const char* fmt, auto... args) { return report ? dpm_set_error(code, fmt, args...) : code; };
+// The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails
+int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b) {
+  auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
@@ -184,15 +183,18 @@ extern "C" int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void*
 int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, void** ev_start,
                               void** ev_stop, int* fused_first) {
   if (!st || !bs || n_req < 1) return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: bad arguments");
+  // every request is checked as dpm_stage_launch checks it before anything is launched: a call that reports a request's
+  // error has written nothing, also when the requests take the one-by-one path below
+  for (int r = 0; r < n_req; ++r)
+    if (const int rc = check_stage_buffers(st, &bs[r])) return rc;
   int done = 0;  // requests already advanced by fused launches
-  // a group fuses when its requests agree in size and dtypes and each one passes the single launch's checks; otherwise
-  // every request is launched on its own (and reports its own error)
+  // a group fuses when its requests agree in size and dtypes; otherwise every request is launched on its own
   const PairUnits* p = pair_of(bs[0].state_dtype, bs[0].eps_dtype);
   // (SDE stages fuse like the others: stage_kernel_multi_noise, each request with the seed of its own bs[r].opts)
   bool fuse = p && n_req > 1 && bs[0].n > 0 && tuning_for(bs[0].opts).multi_fuse != 0;
   for (int r = 0; r < n_req && fuse; ++r)
     fuse = bs[r].n == bs[0].n && bs[r].batch == bs[0].batch && bs[r].state_dtype == bs[0].state_dtype &&
-           bs[r].eps_dtype == bs[0].eps_dtype && check_stage_buffers(st, &bs[r], false) == DPM_OK;
+           bs[r].eps_dtype == bs[0].eps_dtype;
   for (int r0 = 0; fuse && r0 < n_req; r0 += MULTI_MAX) {
     const int cnt = std::min(MULTI_MAX, n_req - r0);
     const int rc = launch_fused(*p, st, bs + r0, cnt, stream, ev_start ? ev_start[r0] : nullptr, ev_stop ? ev_stop[r0] : nullptr);

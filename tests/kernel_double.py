@@ -286,7 +286,9 @@ def _wr(ptr, arr, code):
         dst.view(np.uint16)[:] = torch.from_numpy(a).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
 
 
-def launch_raw_double(st_ref, b_ref, stream):
+def launch_raw_double(st_ref, b_ref, stream, allow_blend=False):
+    """allow_blend: the engine's fast path (install_cpu_double) never carries a mask blend -- only the guard-band sweep
+    (tests/guarded.py) asks for the KExt epilogue here"""
     st, b = st_ref._obj, b_ref._obj
     n, B = int(b.n), int(b.batch)
     sd, ed = b.state_dtype, b.eps_dtype
@@ -314,8 +316,21 @@ def launch_raw_double(st_ref, b_ref, stream):
             mn = threshold64(mn.reshape(B, per), c.thr_ratio, c.thr_max).reshape(-1)
         else:
             mn = O.dynamic_threshold(mn.reshape(B, per), F32(st.thr_ratio), F32(st.thr_max)).reshape(-1)
-    assert not (st.flags & L.F_BLEND), "the fast path never carries a blend"
     out = combine(c, x, mn, _rd(b.h1, n, sd), _rd(b.h2, n, sd), half_rounder(ed)).astype(FT)
+    assert allow_blend or not (st.flags & L.F_BLEND), "the fast path never carries a blend"
+    if st.flags & L.F_BLEND:
+        # the KExt epilogue blends the STORED state (rounded to the state dtype), mask indexed i % mask_period
+        period = int(b.mask_period)
+        rs = half_rounder(sd)
+        v = out if rs is None else rs(out)
+        m = np.tile(_rd(b.mask, period, sd), n // period)
+        ba, bb = _rd(b.blend_a, n, sd), _rd(b.blend_b, n, sd)
+        if FT is F64:
+            src = b.coef64.contents if b.coef64 else st
+            r = ba if bb is None else F64(src.blend_alpha) * ba + F64(src.blend_sigma) * bb
+            out = v * m + (F64(1.0) - m) * r
+        else:
+            out = blend(st.blend_alpha, st.blend_sigma, v, m, ba, bb)
     _wr(b.x_out, out, sd)
     if b.x_out2:
         _wr(b.x_out2, out, sd)
