@@ -33,6 +33,27 @@ inline const DeviceInfo& device_info() {
 }
 
 inline bool aligned(const void* p, size_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+// the tensors of a plain request (plain_request: no separate evaluation state; the fused launches take no classifier
+// gradient): state pointers aligned to a_s bytes, network outputs to a_e.  Operands::aligned_to is the single-request twin.
+inline bool buffers_aligned(const dpm_buffers& b, size_t a_s, size_t a_e) {
+  return aligned(b.x, a_s) && aligned(b.h1, a_s) && aligned(b.h2, a_s) && aligned(b.x_out, a_s) && aligned(b.m_out, a_s) &&
+         aligned(b.e0, a_e) && aligned(b.e1, a_e);
+}
+
+// Two run-time booleans -> template arguments: calls f(std::bool_constant<a>{}, std::bool_constant<b>{}).  Every launcher
+// with a compile-time x0 prologue (SPEC_NOISE_X0 against SPEC_GENERIC: spec_of) and a second binary axis -- classifier-free
+// guidance for the fused launchers (guide_of), the KExt extension for the single-request ones -- selects its kernel through it.
+// The instantiations are made in the order (1,1) (1,0) (0,1) (0,0), and a code object lays its kernels out in the order
+// they were first named in: the callers pass their booleans in the order that keeps that layout (profiles/r14_launchers.md).
+template <typename F>
+auto with_flags(bool a, bool b, F&& f) {
+  if (a) return b ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return b ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+template <typename X0>
+constexpr int spec_of(X0) { return X0::value ? SPEC_NOISE_X0 : SPEC_GENERIC; }
+template <typename Cfg>
+constexpr int guide_of(Cfg) { return Cfg::value ? DPM_GUIDE_CFG : DPM_GUIDE_NONE; }
 
 // the division-by-invariant of the specialised prologue is exact unless alpha's significand is all ones (or alpha is
 // not a normal number): then the generic prologue, with a true division, runs instead
@@ -76,29 +97,6 @@ inline KParams make_params(const dpm_stage* st) {
 // Callers that honour Tuning::force_generic test it themselves.
 inline bool x0_prologue_ok(const dpm_stage& st) {
   return st.model_type == DPM_MODEL_NOISE && (st.flags & DPM_F_TO_X0) && div_invariant_ok(st.alpha_e);
-}
-
-// cluster shape of the thresholding kernel: k workgroups per sample, `chunk` elements each.  Depends only on the
-// batch, the sample size and the CU count, so dpm_threshold_workspace_bytes() and the launch agree.
-struct ThrPlan {
-  int64_t k, chunk;
-};
-inline ThrPlan thr_plan(int64_t batch, int64_t per_sample, int n_cu) {
-  const int64_t kmin = (per_sample + THR_CHUNK_MAX - 1) / THR_CHUNK_MAX;        // what LDS allows
-  const int64_t kfill = (2 * (int64_t)n_cu) / (batch < 1 ? 1 : batch);          // spread a small batch over the chip
-  const int64_t kmax = std::max<int64_t>(1, per_sample / 2048);                 // but keep >= 2 elements per lane
-  int64_t k = std::max(kmin, std::min(std::min(kfill, kmax), (int64_t)n_cu));
-  if (k < 1) k = 1;
-  int64_t chunk = (per_sample + k - 1) / k;
-  chunk = (chunk + 3) / 4 * 4;
-  return ThrPlan{k, chunk};
-}
-// words per sample: the merged histograms / lists / counters of the general route + one slot per workgroup of the cluster
-// (two slot areas: the attempt with a predicted bound and the one with a searched bound each publish into their own)
-inline int64_t thr_ws_stride(int64_t k) { return (int64_t)THR_WS_WORDS + 2 * k * (int64_t)THR_SLOTW; }
-inline int64_t thr_ws_bytes(int64_t batch, int64_t per_sample, int n_cu) {
-  const ThrPlan pl = thr_plan(batch, per_sample, n_cu);
-  return pl.k > 1 ? batch * thr_ws_stride(pl.k) * 4 : 0;
 }
 
 // launch-shape defaults (measured on MI355X: profiles/r01_tuning.md, r01_tuning_v3.txt, and r01_tuning_v4.txt with the
@@ -192,8 +190,7 @@ inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
   if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b)) return false;
   const size_t as = (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT, ae = (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2) * EPT;
   if (b.x_out2 && (st.guidance != DPM_GUIDE_CFG || !aligned(b.x_out2, as))) return false;
-  return aligned(b.x, as) && aligned(b.h1, as) && aligned(b.h2, as) && aligned(b.x_out, as) && aligned(b.m_out, as) &&
-         aligned(b.e0, ae) && aligned(b.e1, ae);
+  return buffers_aligned(b, as, ae);
 }
 
 // the generator's parameters of one request's SDE stage: the seed from the request's own dpm_launch_opts (none: seed 0),
@@ -255,6 +252,13 @@ struct Operands {
     ext.blend_sigma = st->blend_sigma;
     use_ext = ext.xo2 || ext.mask || ext.eps_stride;
   }
+  // every state pointer aligned to a_s bytes, every network-output pointer to a_e (null pointers are).  The full list for
+  // every launcher: a pointer a kernel does not read is either null or one of the library's own allocations (the callers
+  // bind h2 only to stages with an h2 slot and rebind g with the network outputs of every call).
+  bool aligned_to(size_t a_s, size_t a_e) const {
+    return aligned(x, a_s) && aligned(xe, a_s) && aligned(h1, a_s) && aligned(h2, a_s) && aligned(xo, a_s) &&
+           aligned(mo, a_s) && aligned(e0, a_e) && aligned(e1, a_e) && aligned(g, a_e);
+  }
 };
 
 // the KExt half of the vector kernels' 16-byte test: the extended vector kernel has no ragged tail and indexes whole
@@ -290,13 +294,10 @@ inline Shape stream_grid(int64_t n, int u, int n_cu, const Tuning& tn) {
   return Shape{dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3((unsigned)bt)};
 }
 
-// ---- a thresholded stage (stage_thresh_kernel): cluster shape, select parameters, kernel flavour, the launch
+// ---- a thresholded stage (stage_thresh_kernel): the plan (thr_launch_plan, dpm_thresh_plan.hpp: cluster shape, select
+// parameters), the kernel flavour, the launch
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
 int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
-  const KParams& p = op.p;
-  const TS *x = op.x, *xe = op.xe, *h1 = op.h1, *h2 = op.h2;
-  const TE *e0 = op.e0, *e1 = op.e1, *g = op.g;
-  TS *xo = op.xo, *mo = op.mo;
   const KExt& ext = op.ext;
   const int n_cu = op.n_cu;
   const Tuning tn = tuning_for(b->opts);
@@ -306,39 +307,17 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   // clusters -- whose sample s lives in the tensors of request s / batch (ThrTab)
   const bool multi = stream.multi != nullptr;
   const int64_t batch = multi ? (int64_t)stream.n_multi * b->batch : b->batch;
-  if (batch > 0x7fffffff || per_sample > ((int64_t)1 << 40))
-    return dpm_set_error(DPM_ERR_UNSUPPORTED, "thresholding: batch / sample size out of range");
-  ThrPlan pl = thr_plan(batch, per_sample, n_cu);
   hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(stream.stream, &cap_status);
   const bool capturing = cap_status != hipStreamCaptureStatusNone;
-  // Clusters wait for each other inside the kernel, which is only safe while no OTHER clustered launch can hold part of
-  // the chip at the same time.  Eager launches of this process are chained device-wide (below); a captured graph is
-  // replayed outside that chain, possibly next to another graph on another stream.  Under capture a sample that fits
-  // one workgroup's LDS therefore takes the cluster-free shape (one workgroup per sample) unless the caller opts in
-  // (dpm_launch_opts.cluster_in_graph); larger samples have no such shape and keep their clusters, with bounded waits.
-  if (capturing && pl.k > 1 && per_sample <= THR_CHUNK_MAX && !tn.cluster_in_graph) {
-    pl.k = 1;
-    pl.chunk = (per_sample + 3) / 4 * 4;
-  }
-  ThrParams tp;
-  std::memset(&tp, 0, sizeof tp);
-  tp.per_sample = per_sample;
-  // torch.quantile: rank = q * (n - 1) evaluated in fp32 (q is an fp32 tensor)
-  const float rank = st->thr_ratio * (float)(per_sample - 1);
-  tp.lo = (int32_t)floorf(rank);
-  tp.hi = (int32_t)ceilf(rank);
-  tp.w = rank - (float)tp.lo;
-  tp.max_val = st->thr_max;
-  tp.chunk = (int32_t)pl.chunk;
-  tp.k = (int32_t)pl.k;
-  tp.batch = (int32_t)batch;
-  tp.fastdiv = x0_prologue_ok(*st);
   const size_t a4s = sizeof(TS) * 4, a4e = sizeof(TE) * 4;
-  tp.vec = per_sample % 4 == 0 && ext.eps_stride % 4 == 0 && ext.mask_period % 4 == 0 && aligned(x, a4s) &&
-           aligned(xe, a4s) && aligned(h1, a4s) && aligned(h2, a4s) && aligned(xo, a4s) && aligned(mo, a4s) &&
-           aligned(ext.xo2, a4s) && aligned(ext.mask, a4s) && aligned(ext.ba, a4s) && aligned(ext.bb, a4s) &&
-           aligned(e0, a4e) && aligned(e1, a4e) && aligned(g, a4e);
+  bool vec = per_sample % 4 == 0 && ext.eps_stride % 4 == 0 && ext.mask_period % 4 == 0 && op.aligned_to(a4s, a4e) &&
+             aligned(ext.xo2, a4s) && aligned(ext.mask, a4s) && aligned(ext.ba, a4s) && aligned(ext.bb, a4s);
+  for (int r = 0; multi && r < stream.n_multi; ++r) vec = vec && buffers_aligned(stream.multi[r], a4s, a4e);
+  ThrLaunchPlan lp = thr_launch_plan(*st, batch, per_sample, n_cu, ThrKnobs{tn.cluster_in_graph, tn.cluster_one_hop},
+                                     capturing, vec, x0_prologue_ok(*st));
+  if (lp.err) return dpm_set_error(DPM_ERR_UNSUPPORTED, "thresholding: batch / sample size out of range");
+  ThrParams& tp = lp.tp;
   static const ThrTab no_tab = {};
   ThrTab tab_multi;
   if (multi) {
@@ -350,55 +329,16 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     for (int r = 0; r < stream.n_multi; ++r) {
       const dpm_buffers& q = stream.multi[r];
       if (!plain_request(q) || q.x_out2) return MULTI_NOT_BUILT;
-      if (pl.k > 1) {
+      if (lp.k > 1) {
         if (!q.workspace) return MULTI_NOT_BUILT;
         for (int r2 = 0; r2 < r; ++r2)
           if (stream.multi[r2].workspace == q.workspace) return MULTI_NOT_BUILT;
       }
-      tp.vec = tp.vec && aligned(q.x, a4s) && aligned(q.h1, a4s) && aligned(q.h2, a4s) && aligned(q.x_out, a4s) &&
-               aligned(q.m_out, a4s) && aligned(q.e0, a4e) && aligned(q.e1, a4e);
       fill_request(tab_multi, r, q);
       tab_multi.ws[r] = static_cast<uint32_t*>(q.workspace);
     }
   }
   const ThrTab& tab = multi ? tab_multi : no_tab;
-  {
-    // top-K front end: a = the K-th largest element.  It needs at most one wanted element per contributing thread and
-    // pays when the K-th largest per-thread maximum sits in the sparse upper tail (K a small part of the threads) and
-    // the candidates (a small multiple of K) fit the rank-counting finish (<= THR_THREADS of them).
-    const int64_t K = per_sample - (int64_t)tp.lo;
-    int64_t P = 0;
-    for (int64_t c = 0; c < pl.k; ++c) {
-      const int64_t n_c = std::max<int64_t>(0, std::min<int64_t>(pl.chunk, per_sample - c * pl.chunk));
-      P += std::min<int64_t>(THR_THREADS, tp.vec ? (n_c + 3) / 4 : n_c);
-    }
-    if (K >= 1 && K <= P / 4 && K <= THR_THREADS / 4) {  // beyond: the candidates outgrow the rank-counting finish
-      tp.topk = (int32_t)K;
-      tp.mrank = (int32_t)(P - K);
-    }
-    // single-exchange cluster route (cluster_select_once): a chunk's share of the K largest is ~ K/k; publishing the
-    // ~quota = K/k + 6 sigma + 8 largest values of every chunk makes the one-hop answer exact except for samples whose
-    // large values sit in one chunk (those fall back inside the kernel).  Needs room in the slots for the 14-bit digit's
-    // granularity (x1.5) and a union that fits the LDS list.
-    if (pl.k > 1 && pl.k <= THR_KMAX && K >= 1 && K < ((int64_t)1 << 30)) {
-      const double mu = (double)K / (double)pl.k;
-      const int64_t quota = (int64_t)std::ceil(mu + 6.0 * std::sqrt(mu) + 8.0);
-      // slot size: the smallest power of two >= 64 with room for the quota and the digit granularity (fewer words to
-      // fetch per slot); at most THR_SLOT_CAP and THR_CAP / k
-      int slot_shift = 6;
-      while (((int64_t)1 << slot_shift) < quota * 3 / 2 && slot_shift < 8) ++slot_shift;
-      while (slot_shift > 0 && ((int64_t)1 << slot_shift) > std::min<int64_t>(THR_SLOT_CAP, THR_CAP / pl.k)) --slot_shift;
-      const int64_t slot_cap = (int64_t)1 << slot_shift;
-      if (quota * 3 / 2 <= slot_cap && tn.cluster_one_hop) {
-        tp.quota = (int32_t)quota;
-        tp.kbig = (int32_t)K;
-        tp.slot_cap = (int32_t)slot_cap;
-        tp.slot_pub = (int32_t)std::min<int64_t>(slot_cap, quota + quota / 4 + 4);
-        tp.slot_shift = slot_shift;
-        tp.debug_reject = tn.cluster_one_hop == 2;
-      }
-    }
-  }
 #ifdef DPM_THR_TIMING
   static_assert(DPM_LAB, "DPM_THR_TIMING instruments the lab build only");
   // debug build only: the DPM_THR_TIMING_LAUNCH-th thresholding launch of the process (default 40) is synchronised
@@ -425,7 +365,6 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
 #else
   auto t_dump = [](int64_t) {};
 #endif
-  const size_t lds_bytes = (size_t)pl.chunk * 4 + THR_NB * 4 + THR_MISC * 4 + (THR_CAP + 32) * 4;
   // the compile-time specialisation exists for the forms / guidance kinds samplers combine with thresholding
   // (classifier guidance -- the reference's own ImageNet-256 example samples with it AND thresholding, sample.sh:40-50 --
   // has the HOT = 3 flavour only: its two load loops cover the noise fast path and everything else)
@@ -450,10 +389,10 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     }
     if (!chosen && hot && front) kern = stage_thresh_kernel<TS, TE, FORM, GUIDE, XE, THR_THREADS, 3>;
   }
-  if (!xe) xe = x;
   int64_t grid = batch;
   tp.groups = (int32_t)batch;
-  if (pl.k > 1) {
+  DeviceContext* chain = nullptr;  // != null: an eager clustered launch, chained device-wide (below)
+  if (lp.k > 1) {
     // clusters synchronise through spin barriers: every workgroup of the grid must be resident at once
     // (cached per thread for the last (device, kernel, LDS size): kernels of different flavours may differ in occupancy)
     static thread_local int occ_dev = -1, occ = 0;
@@ -461,30 +400,29 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     static thread_local const void* occ_kern = nullptr;
     int dev = 0;
     (void)hipGetDevice(&dev);
-    if (dev != occ_dev || lds_bytes != occ_lds || occ_kern != reinterpret_cast<const void*>(kern)) {
+    if (dev != occ_dev || lp.lds_bytes != occ_lds || occ_kern != reinterpret_cast<const void*>(kern)) {
       int nb = 0;
       hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(kern), THR_THREADS,
-                                                                  lds_bytes);
+                                                                  lp.lds_bytes);
       if (e != hipSuccess) return dpm_set_error((int)e, "hipOccupancyMaxActiveBlocksPerMultiprocessor: %s", hipGetErrorString(e));
       occ_dev = dev;
-      occ_lds = lds_bytes;
+      occ_lds = lp.lds_bytes;
       occ_kern = reinterpret_cast<const void*>(kern);
       occ = nb;
     }
     const int64_t cap = (int64_t)n_cu * (occ < 1 ? 1 : (occ > 2 ? 2 : occ));
-    if (pl.k > cap)
+    if (lp.k > cap)
       return dpm_set_error(DPM_ERR_UNSUPPORTED, "dynamic thresholding: a sample of %lld elements needs %lld co-resident "
-                           "workgroups, the device holds %lld", (long long)per_sample, (long long)pl.k, (long long)cap);
+                           "workgroups, the device holds %lld", (long long)per_sample, (long long)lp.k, (long long)cap);
     if (!b->workspace)
       return dpm_set_error(DPM_ERR_ARG,
                            "dynamic thresholding of %lld samples x %lld elements needs a workspace of "
                            "dpm_threshold_workspace_bytes() = %lld bytes",
                            (long long)b->batch, (long long)per_sample, (long long)thr_ws_bytes(b->batch, per_sample, n_cu));
-    const int64_t groups = std::min<int64_t>(batch, cap / pl.k);
+    const int64_t groups = std::min<int64_t>(batch, cap / lp.k);
     tp.groups = (int32_t)groups;
     tp.ws = static_cast<uint32_t*>(b->workspace);
-    tp.ws_stride = thr_ws_stride(pl.k);
-    grid = groups * pl.k;
+    grid = groups * lp.k;
     // No clearing of the workspace here: the caller hands it over zero-filled once, the kernel leaves it zero-filled
     // (dpm_threshold_workspace_bytes).  A wait on a peer that times out is recovered from inside the kernel (solo_select:
     // same results, no error); the host-mapped word only records that it happened (dpm_cluster_timeout_poll).
@@ -509,19 +447,18 @@ int launch_thresh(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     // Two clustered launches on different streams could each hold part of the CUs with spinning workgroups and
     // starve the other's missing peers.  Within this process they are therefore chained device-wide: wait for the
     // previous clustered launch (whatever its stream), record after this one.  (Not under stream capture, where an
-    // event recorded outside the capture cannot be waited on; see above.)
-    if (!capturing) {
-      DeviceContext& ch = device_context(dev);
-      std::lock_guard<std::mutex> lk(ch.mu);
-      if (!ch.ev && hipEventCreateWithFlags(&ch.ev, hipEventDisableTiming) != hipSuccess) ch.ev = nullptr;
-      if (ch.ev && ch.recorded) (void)hipStreamWaitEvent(stream.stream, ch.ev, 0);
-      launch(kern, dim3((unsigned)grid), dim3(THR_THREADS), lds_bytes, stream, x, xe, e0, e1, g, h1, h2, xo, mo, p, tp, ext, tab);
-      if (ch.ev && hipEventRecord(ch.ev, stream.stream) == hipSuccess) ch.recorded = true;
-      t_dump(grid);
-      return launch_status("stage kernel launch failed");
-    }
+    // event recorded outside the capture cannot be waited on; see thr_launch_plan.)
+    if (!capturing) chain = &device_context(dev);
   }
-  launch(kern, dim3((unsigned)grid), dim3(THR_THREADS), lds_bytes, stream, x, xe, e0, e1, g, h1, h2, xo, mo, p, tp, ext, tab);
+  std::unique_lock<std::mutex> lk;
+  if (chain) {
+    lk = std::unique_lock<std::mutex>(chain->mu);
+    if (!chain->ev && hipEventCreateWithFlags(&chain->ev, hipEventDisableTiming) != hipSuccess) chain->ev = nullptr;
+    if (chain->ev && chain->recorded) (void)hipStreamWaitEvent(stream.stream, chain->ev, 0);
+  }
+  launch(kern, dim3((unsigned)grid), dim3(THR_THREADS), lp.lds_bytes, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g,
+         op.h1, op.h2, op.xo, op.mo, op.p, tp, ext, tab);
+  if (chain && chain->ev && hipEventRecord(chain->ev, stream.stream) == hipSuccess) chain->recorded = true;
   t_dump(grid);
   return launch_status("stage kernel launch failed");
 }
@@ -536,9 +473,7 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   const KExt& ext = op.ext;
   const int n_cu = op.n_cu;
   const bool use_ext = op.use_ext;
-  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
-  const bool vec = aligned(x, as) && aligned(xe, as) && aligned(h1, as) && aligned(h2, as) && aligned(xo, as) &&
-                   aligned(mo, as) && aligned(e0, ae) && aligned(e1, ae) && aligned(g, ae) && ext_vec_ok(op, b);
+  const bool vec = op.aligned_to(sizeof(TS) * EPT, sizeof(TE) * EPT) && ext_vec_ok(op, b);
   // what the streaming family instantiates (binary size, build time and first-call cost: one kernel per combination and
   // dtype pair).  Round 5 measured what a compile-time prologue is worth against the run-time one (SPEC_GENERIC: the mode is
   // chosen once per workgroup iteration, the same straight-line code) -- 0-7 % per launch, profiles/r05_kernel_budget.md --
@@ -660,84 +595,60 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
   return launch_status("stage kernel launch failed");
 }
 
-// ---- an SDE stage (DPM_F_NOISE; checked by the caller: LIN1 / TWO, no thresholding, no device-resident coefficients):
-// stage_kernel_noise where the streaming family's vector conditions hold, stage_kernel_scalar_noise otherwise.  The seed
-// comes from the call's dpm_launch_opts, the Philox counter is the stage index, the scale the stage's c2.
+// ---- an SDE stage (DPM_F_NOISE; checked by the caller: LIN1 / TWO, no thresholding, no device-resident coefficients) or
+// a UniPC stage (DPM_FORM_UNIPC; checked by the caller: no thresholding / blend / noise / device-resident coefficients):
+// the family's vector kernel where the streaming family's vector conditions hold -- one tile per iteration at stage_kernel's
+// launch shape, unguided or classifier-free, the evaluation state is the state --, the pair's one-element-per-lane kernel
+// of the family otherwise.
+//   SDE:   stage_kernel_noise (whole 8-element groups only) / stage_kernel_scalar_noise.  The seed comes from the call's
+//          dpm_launch_opts, the Philox counter is the stage index, the scale the stage's c2.
+//   UniPC: stage_kernel with the nt mask of the inputs-from-HBM situation / stage_kernel_scalar_unipc.  DPM_F_STORE_XC
+//          rides on the KExt flavour (x_out2).
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
-int launch_noise(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
-  const KNoise nz = noise_of(*st, *b);
+int launch_noise_unipc(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
+  constexpr bool UNIPC = FORM == DPM_FORM_UNIPC;
+  constexpr bool BUILT = (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO || UNIPC) && GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
   const KParams& p = op.p;
   const KExt& ext = op.ext;
-  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
-  constexpr bool BUILT = (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO) && GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
-  const bool vec = BUILT && b->n % EPT == 0 && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.xo, as) &&
-                   aligned(op.mo, as) && aligned(op.e0, ae) && aligned(op.e1, ae) && ext_vec_ok(op, b);
+  const bool vec = BUILT && (UNIPC || b->n % EPT == 0) && op.aligned_to(sizeof(TS) * EPT, sizeof(TE) * EPT) && ext_vec_ok(op, b);
   if (!vec) {
-    using ScalarNoise = decltype(&stage_kernel_scalar_noise<TS, TE>);
-    launch(reinterpret_cast<ScalarNoise>(const_cast<void*>(dpm_catchall_scalar_noise<TS, TE>())), scalar_grid(b->n, op.n_cu),
-           dim3(256), 0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, nz);
-  } else if constexpr (BUILT) {
-    const Tuning tn = tuning_for(b->opts);
-    const bool x0 = !tn.force_generic && x0_prologue_ok(*st);
-    const Shape sh = stream_grid(b->n, 1, op.n_cu, tn);  // stage_kernel's, one tile per iteration
-#define DPM_NOISE_LAUNCH(SPEC_, EXT_)                                                                                   \
-  launch(stage_kernel_noise<TS, TE, FORM, GUIDE, SPEC_, EXT_>, sh.grid, sh.block, 0, stream, op.x, op.e0, op.e1, op.h1, \
-         op.xo, op.mo, b->n, p, ext, nz)
-    if (op.use_ext) {
-      if (x0) DPM_NOISE_LAUNCH(SPEC_NOISE_X0, true);
-      else DPM_NOISE_LAUNCH(SPEC_GENERIC, true);
+    const dim3 grid = scalar_grid(b->n, op.n_cu);
+    const TS* xe = op.xe ? op.xe : op.x;
+    if constexpr (UNIPC) {
+      using ScalarUnipc = decltype(&stage_kernel_scalar_unipc<TS, TE>);
+      launch(reinterpret_cast<ScalarUnipc>(const_cast<void*>(dpm_catchall_scalar_unipc<TS, TE>())), grid, dim3(256), 0, stream,
+             op.x, xe, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext);
     } else {
-      if (x0) DPM_NOISE_LAUNCH(SPEC_NOISE_X0, false);
-      else DPM_NOISE_LAUNCH(SPEC_GENERIC, false);
+      using ScalarNoise = decltype(&stage_kernel_scalar_noise<TS, TE>);
+      launch(reinterpret_cast<ScalarNoise>(const_cast<void*>(dpm_catchall_scalar_noise<TS, TE>())), grid, dim3(256), 0, stream,
+             op.x, xe, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, noise_of(*st, *b));
     }
-#undef DPM_NOISE_LAUNCH
-  }
-  return launch_status("noise stage kernel launch failed");
-}
-
-// ---- a UniPC stage (DPM_FORM_UNIPC; checked by the caller: no thresholding / blend / noise / device-resident
-// coefficients): stage_kernel where the streaming family's vector conditions hold -- one tile per iteration, the nt mask of
-// the inputs-from-HBM situation, unguided or classifier-free, the evaluation state is the state --,
-// stage_kernel_scalar_unipc otherwise.  DPM_F_STORE_XC rides on the KExt flavour (x_out2).
-template <typename TS, typename TE, int GUIDE, bool XE>
-int launch_unipc(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream, const Operands<TS, TE>& op) {
-  const KParams& p = op.p;
-  const KExt& ext = op.ext;
-  const size_t as = sizeof(TS) * EPT, ae = sizeof(TE) * EPT;
-  constexpr bool BUILT = GUIDE != DPM_GUIDE_CLASSIFIER && !XE;
-  const bool vec = BUILT && aligned(op.x, as) && aligned(op.h1, as) && aligned(op.h2, as) && aligned(op.xo, as) &&
-                   aligned(op.mo, as) && aligned(op.e0, ae) && aligned(op.e1, ae) && ext_vec_ok(op, b);
-  if (!vec) {
-    using ScalarUnipc = decltype(&stage_kernel_scalar_unipc<TS, TE>);
-    launch(reinterpret_cast<ScalarUnipc>(const_cast<void*>(dpm_catchall_scalar_unipc<TS, TE>())), scalar_grid(b->n, op.n_cu),
-           dim3(256), 0, stream, op.x, op.xe ? op.xe : op.x, op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext);
   } else if constexpr (BUILT) {
     const Tuning tn = tuning_for(b->opts);
-    const bool x0 = !tn.force_generic && x0_prologue_ok(*st);
     const Shape sh = stream_grid(b->n, 1, op.n_cu, tn);
-    constexpr int NT = sizeof(TS) == 2 ? 1 : (sizeof(TE) == 4 ? 5 : 1);
-#define DPM_UNIPC_LAUNCH(SPEC_, EXT_)                                                                                       \
-  launch(stage_kernel<TS, TE, DPM_FORM_UNIPC, GUIDE, false, SPEC_, 1, NT, EXT_>, sh.grid, sh.block, 0, stream, op.x, op.xe, \
-         op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, stream.dyn, stream.skip)
-    if (op.use_ext) {
-      if (x0) DPM_UNIPC_LAUNCH(SPEC_NOISE_X0, true);
-      else DPM_UNIPC_LAUNCH(SPEC_GENERIC, true);
-    } else {
-      if (x0) DPM_UNIPC_LAUNCH(SPEC_NOISE_X0, false);
-      else DPM_UNIPC_LAUNCH(SPEC_GENERIC, false);
-    }
-#undef DPM_UNIPC_LAUNCH
+    with_flags(op.use_ext, !tn.force_generic && x0_prologue_ok(*st), [&](auto use_ext, auto x0) {
+      constexpr bool EXT = decltype(use_ext)::value;
+      constexpr int SPEC = spec_of(x0);
+      if constexpr (UNIPC) {
+        constexpr int NT = sizeof(TS) == 2 ? 1 : (sizeof(TE) == 4 ? 5 : 1);
+        launch(stage_kernel<TS, TE, DPM_FORM_UNIPC, GUIDE, false, SPEC, 1, NT, EXT>, sh.grid, sh.block, 0, stream, op.x, op.xe,
+               op.e0, op.e1, op.g, op.h1, op.h2, op.xo, op.mo, b->n, p, ext, stream.dyn, stream.skip);
+      } else {
+        launch(stage_kernel_noise<TS, TE, FORM, GUIDE, SPEC, EXT>, sh.grid, sh.block, 0, stream, op.x, op.e0, op.e1, op.h1,
+               op.xo, op.mo, b->n, p, ext, noise_of(*st, *b));
+      }
+    });
   }
-  return launch_status("unipc stage kernel launch failed");
+  return launch_status(UNIPC ? "unipc stage kernel launch failed" : "noise stage kernel launch failed");
 }
 
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE>
 int launch_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& stream) {
   const Operands<TS, TE> op(st, b);
   if constexpr (FORM == DPM_FORM_UNIPC) {
-    return launch_unipc<TS, TE, GUIDE, XE>(st, b, stream, op);
+    return launch_noise_unipc<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
   } else {
-    if (st->flags & DPM_F_NOISE) return launch_noise<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
+    if (st->flags & DPM_F_NOISE) return launch_noise_unipc<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
     return (st->flags & DPM_F_THRESH) ? launch_thresh<TS, TE, FORM, GUIDE, XE>(st, b, stream, op)
                                       : launch_stream<TS, TE, FORM, GUIDE, XE>(st, b, stream, op);
   }
@@ -854,27 +765,27 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
     if (!fusable_request(*st, bs[r])) return MULTI_NOT_BUILT;
   const bool cfg = st->guidance == DPM_GUIDE_CFG;
   const bool generic = !x0_prologue_ok(*st) || tuning_for(bs[0].opts).force_generic != 0;
+  using Lin1 = std::integral_constant<int, DPM_FORM_LIN1>;
+  using Two = std::integral_constant<int, DPM_FORM_TWO>;
   if (st->flags & DPM_F_NOISE) {
-#define DPM_MULTI_NOISE(FORM_)                                                                                        \
-  (generic ? (cfg ? launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_GENERIC>(st, bs, n_req, c)             \
-                  : launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_GENERIC>(st, bs, n_req, c))           \
-   : cfg   ? launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(st, bs, n_req, c)                   \
-           : launch_multi_noise_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(st, bs, n_req, c))
-    return st->form == DPM_FORM_LIN1 ? DPM_MULTI_NOISE(DPM_FORM_LIN1) : DPM_MULTI_NOISE(DPM_FORM_TWO);
-#undef DPM_MULTI_NOISE
+    auto go = [&](auto form) {
+      return with_flags(generic, cfg, [&](auto gen, auto cfg_) {
+        return launch_multi_noise_spec<TS, TE, decltype(form)::value, guide_of(cfg_), spec_of(std::bool_constant<!gen>{})>(st, bs, n_req, c);
+      });
+    };
+    return st->form == DPM_FORM_LIN1 ? go(Lin1{}) : go(Two{});
   }
-#define DPM_MULTI(FORM_)                                                                                        \
-  (generic ? (cfg ? launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_GENERIC>(st, bs, n_req, c)             \
-                  : launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_GENERIC>(st, bs, n_req, c))           \
-   : cfg   ? launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(st, bs, n_req, c)                   \
-           : launch_multi_spec<TS, TE, FORM_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(st, bs, n_req, c))
+  auto go = [&](auto form) {
+    return with_flags(generic, cfg, [&](auto gen, auto cfg_) {
+      return launch_multi_spec<TS, TE, decltype(form)::value, guide_of(cfg_), spec_of(std::bool_constant<!gen>{})>(st, bs, n_req, c);
+    });
+  };
   switch (st->form) {
-    case DPM_FORM_LIN1: return DPM_MULTI(DPM_FORM_LIN1);
-    case DPM_FORM_TWO: return DPM_MULTI(DPM_FORM_TWO);
-    case DPM_FORM_UNIPC: return DPM_MULTI(DPM_FORM_UNIPC);
-    default: return DPM_MULTI(DPM_FORM_MS3);
+    case DPM_FORM_LIN1: return go(Lin1{});
+    case DPM_FORM_TWO: return go(Two{});
+    case DPM_FORM_UNIPC: return go(std::integral_constant<int, DPM_FORM_UNIPC>{});
+    default: return go(std::integral_constant<int, DPM_FORM_MS3>{});
   }
-#undef DPM_MULTI
 }
 
 // ---- heterogeneous fused launch (stage_kernel_het): request r advanced by st[r].  The caller (dpm_kernels.hip) has
@@ -883,22 +794,6 @@ int launch_multi_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, co
 // MS3 or UNIPC records, never both (a group with a UNIPC record takes stage_kernel_het_unipc).  Here: the prologue
 // (compile-time only when every request may run it), the smallest form set that covers the group, the launch shape of the
 // lockstep kernel (MultiShape, XCD-contiguous remap).
-template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC>
-void launch_het_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
-  launch(stage_kernel_het<TS, TE, FORMS, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c,
-         a);
-}
-
-template <typename TS, typename TE, int GUIDE, int SPEC>
-void launch_het_noise_spec(const HetNoiseArgs& a, const FusedShape& sh, const LaunchCtx& c) {
-  launch(stage_kernel_het_noise<TS, TE, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, a);
-}
-
-template <typename TS, typename TE, int GUIDE, int SPEC>
-void launch_het_unipc_spec(const HetArgs& a, const FusedShape& sh, const LaunchCtx& c) {
-  launch(stage_kernel_het_unipc<TS, TE, GUIDE, SPEC, MultiShape<TS, TE>::U, MultiShape<TS, TE>::NT>, sh.grid, sh.block, 0, c, a);
-}
-
 template <typename TS, typename TE>
 int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const LaunchCtx& c) {
   if (n_req < 1 || n_req > HET_MAX)
@@ -909,7 +804,7 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
   HetArgs& a = an.h;
   bool ms3 = false, unipc = false;
   const bool sde = (st[0].flags & DPM_F_NOISE) != 0;
-  bool noise = !tn.force_generic;
+  bool x0 = !tn.force_generic;
   for (int r = 0; r < n_req; ++r) {
     fill_request(a, r, bs[r]);
     a.xo2[r] = bs[r].x_out2;
@@ -917,7 +812,7 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
     if (sde) an.nz[r] = noise_of(st[r], bs[r]);
     ms3 = ms3 || st[r].form == DPM_FORM_MS3;
     unipc = unipc || st[r].form == DPM_FORM_UNIPC;
-    noise = noise && x0_prologue_ok(st[r]);
+    x0 = x0 && x0_prologue_ok(st[r]);
   }
   if (unipc && (ms3 || sde))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a UniPC stage grouped with a third-order or an SDE stage");
@@ -927,30 +822,24 @@ int launch_het_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, cons
   a.spr = sh.spr;
   a.xcd_span = sh.xcd_span;
   const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
-#define DPM_HET(FS_)                                                                                            \
-  (noise ? (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, sh, c)                         \
-                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, sh, c))                       \
-         : (cfg ? launch_het_spec<TS, TE, FS_, DPM_GUIDE_CFG, SPEC_GENERIC>(a, sh, c)                          \
-                : launch_het_spec<TS, TE, FS_, DPM_GUIDE_NONE, SPEC_GENERIC>(a, sh, c)))
+  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT;
   if (sde) {
-    if (noise) {
-      if (cfg) launch_het_noise_spec<TS, TE, DPM_GUIDE_CFG, SPEC_NOISE_X0>(an, sh, c);
-      else launch_het_noise_spec<TS, TE, DPM_GUIDE_NONE, SPEC_NOISE_X0>(an, sh, c);
-    } else {
-      if (cfg) launch_het_noise_spec<TS, TE, DPM_GUIDE_CFG, SPEC_GENERIC>(an, sh, c);
-      else launch_het_noise_spec<TS, TE, DPM_GUIDE_NONE, SPEC_GENERIC>(an, sh, c);
-    }
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_het_noise<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, an);
+    });
   } else if (unipc) {
-    if (noise) {
-      if (cfg) launch_het_unipc_spec<TS, TE, DPM_GUIDE_CFG, SPEC_NOISE_X0>(a, sh, c);
-      else launch_het_unipc_spec<TS, TE, DPM_GUIDE_NONE, SPEC_NOISE_X0>(a, sh, c);
-    } else {
-      if (cfg) launch_het_unipc_spec<TS, TE, DPM_GUIDE_CFG, SPEC_GENERIC>(a, sh, c);
-      else launch_het_unipc_spec<TS, TE, DPM_GUIDE_NONE, SPEC_GENERIC>(a, sh, c);
-    }
-  } else if (ms3) DPM_HET(HET_FORMS_3);
-  else DPM_HET(HET_FORMS_2);
-#undef DPM_HET
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_het_unipc<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, a);
+    });
+  } else if (ms3) {
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_het<TS, TE, HET_FORMS_3, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, a);
+    });
+  } else {
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_het<TS, TE, HET_FORMS_2, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, a);
+    });
+  }
   return launch_status("fused stage kernel launch failed");
 }
 

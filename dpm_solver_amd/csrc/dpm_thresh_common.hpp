@@ -1,7 +1,10 @@
 // dpm_thresh_common.hpp -- dynamic thresholding (ref :416-425), part 1 of 3: the constants of the LDS / workspace layout,
 // ThrParams / ThrTab, the 4-element accessors and the primitives of the cluster protocol (bounded waits, give-up, barrier).
-// Part of dpm_device.hpp (include that); dpm_thresh_select.hpp and dpm_thresh_kernel.hpp build on it.
+// Part of dpm_device.hpp (include that); dpm_thresh_select.hpp and dpm_thresh_kernel.hpp build on it.  What the host-side
+// plan of a launch reads -- THR_THREADS, THR_NB, THR_WS_WORDS, THR_CHUNK_MAX, THR_CAP, THR_KMAX, THR_MISC, THR_SLOT* -- and
+// ThrParams itself live in dpm_thresh_plan.hpp, which a host compiler reads without HIP.
 #pragma once
+#include "dpm_thresh_plan.hpp"
 
 namespace {
 
@@ -31,22 +34,15 @@ namespace {
 // Cluster barriers are single-use counters in a zeroed workspace (agent-scope atomics); the launch keeps the grid
 // within the number of co-resident workgroups, so waiting workgroups can always be joined by their peers.
 // ------------------------------------------------------------------------------------------------
-constexpr int THR_THREADS = 512;
 // wavefronts per SIMD the run-time dispatched catch-all thresholding kernel (HOT = 0) is compiled for: 4 = two workgroups per
 // CU at a 128-register budget (a handful of spills to scratch), 2 = no register limit, one workgroup per CU
 #ifndef DPM_THR_CATCHALL_WAVES
 #define DPM_THR_CATCHALL_WAVES 4
 #endif
-constexpr int THR_NB = 2048;                 // bins per radix level
-// workspace words per sample (k > 1): 3 level histograms, the histogram of the per-thread maxima and the candidate list
-// of the top-K front end, counters (a 256-byte multiple)
-constexpr int THR_WS_WORDS = 5 * THR_NB + 64;
 constexpr int THR_WS_MAXH = 3 * THR_NB;
 constexpr int THR_WS_LIST = 4 * THR_NB;
 constexpr int THR_WS_CNT = 5 * THR_NB;  // [0..3] barriers of the radix levels / min-above, [4..5] barriers of the top-K front
                                         // end, [8] min-above complement, [9], [10] list cursors
-constexpr int THR_CHUNK_MAX = 12288;         // elements of a sample one workgroup keeps in LDS (48 KiB)
-constexpr int THR_CAP = 4096;                // candidates (elements sharing the selected top digit) kept compacted
 constexpr int THR_GCAP = THR_NB;             // cluster-wide candidates exchanged through the level-1 histogram's words
 // single-exchange route of a cluster (cluster_select_once): every workgroup publishes the elements of its chunk that
 // can still be among the sample's K largest into its own slot of the workspace -- header + values, every word tagged
@@ -55,11 +51,6 @@ constexpr int THR_ROWS = 2;  // tile rows a thread keeps in flight in the stream
 // THR_NB of them below a maximum (a factor 54).  Measured against 1.5 % bins (shift 17) on [64,3,256,256]: 55.7 -> 53.1 us
 // per stage -- the union's values crowd into ~40 of the coarse bins and their LDS atomics serialise.
 constexpr int THR_FSHIFT = 14;
-constexpr int THR_KMAX = 256;                // largest cluster the single-exchange route serves
-constexpr int THR_MISC = 32 + 2 * THR_KMAX;  // scalar LDS words of the thresholding kernel (see stage_thresh_kernel)
-constexpr int THR_SLOT_CAP = 256;            // values one workgroup may publish
-constexpr int THR_SLOT_HDR = 8;              // [0] tag | count (or overflow), [1] tag | bound, [2] tag | chunk maximum
-constexpr int THR_SLOTW = THR_SLOT_CAP + THR_SLOT_HDR;  // (128-byte aligned slots, 288 words, were measured: no difference)
 constexpr uint32_t THR_TAG = 0x80000000u;    // |x0| bit patterns have bit 31 clear: a tagged word is never 0
 constexpr uint32_t THR_OVERFLOW = 0x40000000u;
 constexpr int THR_WS_DONE = THR_WS_CNT + 12; // workgroups of the cluster that are through with the workspace
@@ -75,49 +66,6 @@ constexpr int THR_WS_RESULT = THR_WS_CNT + 24;
 // Giving up is safe (the workgroup then computes the sample's order statistics alone, solo_select), so the limit only
 // trades a stall against redundant work when the peers are off the chip (ThrParams.spin_limit, DPM_TUNE_THR_SPIN_LIMIT)
 constexpr uint32_t THR_SPIN_LIMIT = 1u << 12;
-
-struct ThrParams {
-  int64_t per_sample;
-  int32_t lo, hi;  // floor / ceil of the fp32 rank (ascending order)
-  float w;         // fractional part
-  float max_val;
-  int32_t chunk;   // elements per workgroup of a cluster (multiple of 4 when the vector path is on)
-  int32_t k;       // workgroups per cluster
-  int32_t groups;  // clusters in the grid
-  int32_t batch;
-  int32_t vec;     // 1: 4-element vector accesses are legal for every tensor of this launch
-  int32_t topk;    // > 0: K = per_sample - lo is small enough for the top-K front end of the select
-  int32_t mrank;   // top-K: ascending rank of the K-th largest per-thread maximum among the contributing threads
-  int32_t fastdiv; // 1: noise-prediction network + eps -> x0 with a divisor that passes div_invariant_ok (see div_by_alpha)
-  int32_t quota;   // > 0: single-exchange cluster route; values beyond this rank of the per-thread maxima are not published
-  int32_t kbig;    // K = per_sample - lo (the wanted element is the K-th largest of the sample)
-  int32_t bpr;      // > 0: the launch fuses several requests of bpr samples each (ThrTab); sample s belongs to request s / bpr
-  int32_t slot_pub; // entries of a slot that are always written (values, then the bare tag)
-  int32_t slot_cap; // values per workgroup slot: a power of two <= THR_SLOT_CAP with k * slot_cap <= THR_CAP
-  int32_t slot_shift; // log2(slot_cap)
-  int32_t debug_reject; // testing: run the single-exchange select but always take the general route afterwards
-  int64_t ws_stride; // words per sample in ws
-  uint32_t* ws;    // k > 1: batch x ws_stride words, all zero between launches (the kernel cleans up after itself)
-  uint32_t* fault; // host-mapped word: set when a cluster wait timed out and was recovered from (diagnostics only:
-                   // dpm_cluster_timeout_poll; the launch's results are correct either way)
-  uint32_t spin_limit;  // polls before a wait on a peer gives up (THR_SPIN_LIMIT)
-#if DPM_LAB
-  int32_t debug_fault;  // LAB build only (DPM_TUNE_THR_DEBUG_FAULT): 2 / 3 = workgroup 1 of every cluster takes no part in its cluster
-  int32_t elect;        // LAB build only (DPM_TUNE_THR_ELECT): workgroup 0 of a cluster reads the k slots, selects on the union
-                        // and publishes the verdict; its peers make one wait and read three words -- k slot reads per sample
-                        // instead of k^2 (profiles/r05_thresholding.md)
-  int32_t stagger;      // LAB build only (DPM_TUNE_THR_STAGGER): cluster g starts (g % groups) * ticks of 0.1 us late -- low 16
-                        // bits = ticks, high bits = groups (0 = 2): clusters that walk several large samples stay out of
-                        // phase, so that one group streams while another selects (profiles/r05_thresholding.md)
-#endif
-  float* hint;     // dpm_buffers.thr_hint (THR_HINT_W floats per sample) or null: the selected order statistic of the
-                   // previous two stages -> predicted select bound of this one (cluster_select_once, `pbound`)
-  int32_t hint_reset; // this is the first stage of a trajectory: the stored values are stale, overwrite without reading
-  int32_t hint_predict; // 0: maintain the hint but do not use it (DPM_TUNE_THR_PREDICT)
-#ifdef DPM_THR_TIMING  // (lab build only)
-  uint64_t* tdbg;  // 16 timestamps per workgroup (tools/thr_timeline.py)
-#endif
-};
 
 // pointer table of a fused multi-request thresholding launch (a kernel argument, like MultiTab): request r's tensors
 // and its workspace
