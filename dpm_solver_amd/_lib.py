@@ -80,7 +80,7 @@ class LaunchOpts(C.Structure):
     """dpm_launch_opts: what a caller may choose per call (zero = defaults)"""
     _fields_ = [("cluster_in_graph", C.c_int32), ("no_fuse", C.c_int32), ("thr_spin_limit", C.c_int32),
                 ("per_request_stages", C.c_int32), ("noise_seed_lo", C.c_uint32), ("noise_seed_hi", C.c_uint32),
-                ("reserved", C.c_int32 * 2)]
+                ("fuse_shapes", C.c_int32), ("reserved", C.c_int32 * 1)]
 
 
 class Buffers(C.Structure):
@@ -274,8 +274,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 206:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 206 -- stale library, rebuild"
+if lib.dpm_version() < 207:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 207 -- stale library, rebuild"
                       % lib.dpm_version())
 
 

@@ -18,7 +18,7 @@
 
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
-// pair's catch-all kernels, unit B the heterogeneous fused launcher.
+// pair's catch-all kernels, unit B the heterogeneous fused launchers.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -33,6 +33,10 @@ int dpm_launch_fused(const dpm_stage* st, const dpm_buffers* bs, int n_req, void
 // (unit B) one heterogeneous fused launch: request r advanced by st[r]; the requests are grouped by the caller
 template <typename TS, typename TE>
 int dpm_launch_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
+// (unit B) the same for a group whose members differ in n (dpm_launch_opts.fuse_shapes); MULTI_NOT_BUILT when the group's
+// tile space does not fit the kernel's 32-bit index
+template <typename TS, typename TE>
+int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -28,7 +28,7 @@ uint32_t* cluster_fault_word(int dev, bool create) {
 
 namespace {
 // The stage launchers of one dtype pair (dpm_stage_unit.hip, dpm_internal.hpp): unit A's and unit B's single-request
-// launchers, unit A's fused multi-request one and unit B's heterogeneous one.  One row per entry of DPM_PAIRS.
+// launchers, unit A's fused multi-request one and unit B's heterogeneous ones.  One row per entry of DPM_PAIRS.
 using UnitFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*, const dpm_stage*, const int32_t*,
                        const dpm_buffers*, int);
 using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
@@ -37,11 +37,12 @@ struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
   FusedFn fused;
-  HetFn het;  // unit B's heterogeneous fused launcher (per-request stage records)
+  HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
+  HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
-   dpm_launch_het<TS, TE>},
+   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -215,9 +216,10 @@ int dpm_stage_launch_multi_ev(const dpm_stage* st, const dpm_buffers* bs, int n_
 namespace {
 // May a request that passes fusable_request (dpm_launch.hpp) join the heterogeneous fused launch (stage_kernel_het) of
 // request 0 of a group?  They must agree on the fields that are template arguments or kernel-wide scalars.  (Which of MS3
-// and UNIPC a group takes is decided as it fills: het_third_form.)
-bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b) {
-  return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && b.n == b0.n && b.batch == b0.batch &&
+// and UNIPC a group takes is decided as it fills: het_third_form.)  `shapes` (dpm_launch_opts.fuse_shapes): n and batch may
+// differ -- the mixed-shape kernels give every request its own tile count.
+bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage& s, const dpm_buffers& b, bool shapes) {
+  return b.state_dtype == b0.state_dtype && b.eps_dtype == b0.eps_dtype && (shapes || (b.n == b0.n && b.batch == b0.batch)) &&
          s.model_type == s0.model_type && s.guidance == s0.guidance &&
          (s.flags & (DPM_F_TO_X0 | DPM_F_NOISE)) == (s0.flags & (DPM_F_TO_X0 | DPM_F_NOISE));  // SDE stages apart from ODE ones
 }
@@ -228,11 +230,14 @@ int het_third_form(const dpm_stage& s) { return s.form == DPM_FORM_MS3 || s.form
 
 // dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
 // HET_MAX (first come, first grouped; the first MS3 or UNIPC record to join a group closes it to the other form, whose
-// records wait for a later group), launch the rest one by one
+// records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
+// all share one n still takes the kernels it always took, one with at least two takes the mixed-shape family -- or, should
+// its tile space not fit that family's 32-bit index, single launches.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r])) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
+  const bool shapes = bs[0].opts->fuse_shapes == 1;
   std::vector<char> done((size_t)n_req, 0);
   dpm_stage gs[HET_MAX];
   dpm_buffers gb[HET_MAX];
@@ -242,7 +247,7 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
     int cnt = 0, third = 0;
     if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
       for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
-        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r])) {
+        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r], shapes)) {
           const int f = het_third_form(st[r]);
           if (f && third && f != third) continue;
           if (f) third = f;
@@ -252,7 +257,14 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
         }
     }
     if (cnt > 1) {
-      const int rc = pair_of(bs[r0].state_dtype, bs[r0].eps_dtype)->het(gs, gb, cnt, stream);
+      const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
+      bool mixed = false;
+      for (int k = 1; k < cnt; ++k) mixed = mixed || gb[k].n != gb[0].n;
+      int rc = mixed ? p.het_shapes(gs, gb, cnt, stream) : p.het(gs, gb, cnt, stream);
+      if (rc == MULTI_NOT_BUILT) {
+        rc = DPM_OK;
+        for (int k = 0; k < cnt && !rc; ++k) rc = dpm_stage_launch_ev(&gs[k], &gb[k], stream, nullptr, nullptr);
+      }
       if (rc) return rc;
       for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
     } else {

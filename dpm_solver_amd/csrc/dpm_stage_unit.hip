@@ -2,7 +2,8 @@
 // translation unit: compiled ten times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
-//               stage_kernel_het_noise, stage_kernel_het_unipc)
+//               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
+//               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1>"
 #endif
@@ -55,4 +56,11 @@ int dpm_launch_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* 
   return launch_het_typed<TS, TE>(st, bs, n_req, s);
 }
 template int dpm_launch_het<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
+
+template <typename TS, typename TE>
+int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_het_shapes_typed<TS, TE>(st, bs, n_req, s);
+}
+template int dpm_launch_het_shapes<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
 #endif

@@ -24,6 +24,14 @@ of their own, next to the ODE groups of the same tick; the result is bit-identic
 fuses at any position next to the first- and second-order stages of other requests (stage_kernel_het_unipc), so a pool of
 UniPC requests -- or of UniPC and 2M requests -- is one launch per tick and 16 requests; the result is bit-identical to
 `sample_unipc(x_T, ...)`.  One pool may hold ODE, SDE and UniPC requests at once.
+
+`request_pool(mixed_shapes=True)` admits requests of ANY shape -- 512^2, 768^2 and 1024^2 latents, different images per prompt
+-- into one pool; dtype and device stay the first submit's.  The tick's options then carry dpm_launch_opts.fuse_shapes, and
+the library fuses requests of different element counts in one launch of its mixed-shape kernels (stage_kernel_shapes: the
+members' tiles back to back, each request advanced over its own size), 16 requests per launch as before.  A request the fused
+kernels do not take (an element count that is no multiple of 8, for one) is launched on its own in the same call.  Results
+stay bit-identical to `sample` / `sample_sde` / `sample_unipc` on the request alone.  The default pool fixes the shape at the
+first submit and launches exactly as it did before the flag existed.
 """
 import ctypes as C
 
@@ -45,15 +53,17 @@ class _Request:
 
 
 class RequestPool:
-    """Requests of one shape, dtype and device (fixed by the first submit), each with its own `sample()` arguments."""
+    """Requests of one shape, dtype and device (fixed by the first submit), each with its own `sample()` arguments.
+    `mixed_shapes=True`: of one dtype and device, any shape."""
 
-    def __init__(self, solver):
+    def __init__(self, solver, mixed_shapes=False):
         self._s = solver
+        self._mixed = bool(mixed_shapes)
         self._active = {}        # handle -> _Request, in submission order
         self._finished = {}      # handle -> result of a request without update stages (returned by the next step)
         self._free = {}          # launch-record key -> [_FastRun]: scratch of finished requests, reused by later ones
         self._next = 0
-        self._like = None        # (shape, dtype, device) of the pool
+        self._like = None        # (shape, dtype, device) of the pool; a mixed-shape pool: (None, dtype, device)
         self._opts = L.LaunchOpts()
 
     def __len__(self):
@@ -129,16 +139,16 @@ class RequestPool:
         return self._admit(x, self._check_x(x), plan, None)
 
     def _check_x(self, x):
-        """the pool's own checks of a request's x_T: on the GPU, a tensor of the pool's shape, dtype and device; returns
-        (shape, dtype, device)"""
+        """the pool's own checks of a request's x_T: on the GPU, a tensor of the pool's shape (unless it mixes shapes), dtype
+        and device; returns what _admit stores as the pool's (shape, dtype, device)"""
         DV._require_gpu(x)
         if not torch.is_tensor(x) or x.dim() == 0 or x.numel() == 0:
             raise ValueError("request pool: x must be a tensor with at least one dimension and one element")
         like = (tuple(x.shape), x.dtype, x.device)
-        if self._like is not None and like != self._like:
+        if self._like is not None and like[1 if self._mixed else 0:] != self._like[1 if self._mixed else 0:]:
             raise ValueError("request pool: x of shape %s, dtype %s on %s does not match the pool's %s, %s on %s"
-                             % (like + self._like))
-        return like
+                             % (like + (self._like[0] or "any shape",) + self._like[1:]))
+        return ((None,) + like[1:]) if self._mixed else like
 
     def _admit(self, x, like, plan, seed):
         """a checked request with its plan joins the pool (seed: an SDE request's); returns its handle"""
@@ -237,6 +247,7 @@ class RequestPool:
         if o is not None:
             C.memmove(C.byref(self._opts), o, C.sizeof(L.LaunchOpts))
         self._opts.per_request_stages = 1
+        self._opts.fuse_shapes = 1 if self._mixed else 0
         self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
         for r, q in enumerate(self._active.values()):
             if q.seed is None:

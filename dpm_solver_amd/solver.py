@@ -700,12 +700,13 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self):
+    def request_pool(self, mixed_shapes=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
-        bit-identical to `sample()`; see dpm_solver_amd/pool.py."""
-        return _pool.RequestPool(self)
+        bit-identical to `sample()`; see dpm_solver_amd/pool.py.  `mixed_shapes=True`: the requests may differ in shape (latent
+        size, images per prompt) and still share the tick's launch."""
+        return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):
         """hipGraph-capture `sample(x, **sample_kwargs)` for a fixed shape (extension).

@@ -62,11 +62,14 @@ extern "C" {
    struct changed).
    206 dpm_stage_launch_multi with per-request stages fuses DPM_FORM_UNIPC stages too, at any position and next to first- and
    second-order stages (UniPC requests in continuous batching; no entry point added, no struct changed).
+   207 dpm_launch_opts.fuse_shapes (was reserved[0]): dpm_stage_launch_multi with per-request stages fuses requests of
+   DIFFERENT n and batch in one launch (a server's 512^2, 768^2 and 1024^2 latents side by side; no entry point added, no
+   struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 206
+#define DPM_HIP_VERSION 207
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -224,7 +227,10 @@ typedef struct dpm_launch_opts {
                             /* and still keys request r's generator with the seed of its own bs[r].opts (NULL: seed 0); */
                             /* dpm_plan_run_multi hands request r its rbs[r].opts there; dpm_graph_create bakes the     */
                             /* seed of rb->opts into the graph                                                          */
-  int32_t reserved[2];      /* zero                                                                                   */
+  int32_t fuse_shapes;      /* version 207 (was reserved[0]); read from bs[0].opts, together with per_request_stages == 1
+                               only.  1: the requests of a fused group need not agree on n and batch (see
+                               dpm_stage_launch_multi); 0: every call groups and launches as before version 207          */
+  int32_t reserved[1];      /* zero                                                                                   */
 } dpm_launch_opts;
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
@@ -394,7 +400,13 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    one by one.  Groups fill in call order (first come, first grouped).  MS3 and UNIPC stages never share a group: the first
    of the two forms to join a group decides which it takes, stages of the other form open a later group; first- and
    second-order stages join either, so a pool of UniPC requests -- first-order at stage 0, UNIPC afterwards -- and 2M
-   requests is one launch per 16 requests. Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own. */
+   requests is one launch per 16 requests. Results are identical either way; dpm_launch_opts.no_fuse launches every request on its own.
+   Mixed shapes (version 207): with bs[0].opts->fuse_shapes == 1 as well, a group's requests need not agree on n and batch --
+   every other rule above stays (dtypes, model type, guidance kind, DPM_F_TO_X0, DPM_F_NOISE, dense 16-byte aligned buffers of
+   whole 8-element groups, call order, 16 per launch, MS3 apart from UNIPC).  A group whose members share one n is launched
+   exactly as without the flag; a group with at least two different n is ONE launch whose tile space is the members' tiles
+   back to back, each request advanced over its own n with the bits of its single launch.  (A group of 2^31 or more
+   super-tiles of 2048 or 4096 elements is launched member by member.) */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
