@@ -56,6 +56,32 @@ _stage_launch_raw = L.lib.dpm_stage_launch
 _stage_launch_multi_raw = L.lib.dpm_stage_launch_multi
 
 
+# ---- the slab pool's staging (dpm_solver_amd/slab.py): pinned host memory and the one host-to-device copy of a tick.  Names of
+# this module like the launch entry points above, so that the CPU test suite can replace them (a CPU-only machine cannot pin)
+def _pinned_bytes(nbytes):
+    """`nbytes` of pinned host memory as a uint8 tensor (64-byte aligned, like every torch allocation)"""
+    return torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True)
+
+
+def _device_bytes(nbytes, device):
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def _copy_to_device(dst, src):
+    """one asynchronous copy of the pinned `src` into the device tensor `dst` on the current stream; returns the event behind
+    it (the pinned buffer may be refilled once it has passed)"""
+    dst.copy_(src, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(dst.device))
+    return ev
+
+
+def _event_wait(ev):
+    """host-side wait for a _copy_to_device event (None: nothing to wait for); a no-op when it has passed"""
+    if ev is not None and not ev.query():
+        ev.synchronize()
+
+
 def _mf_of(t):
     """The memory format of a dense tensor that is NOT laid out in the default order: torch.channels_last (4-D, NHWC) /
     torch.channels_last_3d (5-D); None = default-contiguous, or neither.  The stage kernels are elementwise over the flat

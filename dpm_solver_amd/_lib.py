@@ -46,6 +46,9 @@ TUNE_THR_PREDICT = 9
 TUNE_THR_SPIN_LIMIT, TUNE_THR_DEBUG_FAULT, TUNE_BLOCK_THREADS = 10, 11, 12
 TUNE_FORCE_GENERIC, TUNE_THR_ELECT, TUNE_LDS_DMA, TUNE_THR_STAGGER, TUNE_BIG_TILES = 13, 14, 15, 16, 17
 MULTI_MAX = 32
+TABLE_FILL, TABLE_LAUNCH = 1, 2           # dpm_launch_opts.table_mode (version 208)
+TABLE_MAGIC = 0x4c425444
+SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
 THR_HINT_WORDS = 4
 
 
@@ -76,11 +79,18 @@ class StageF64(C.Structure):
                [("time_f64", C.c_int32), ("reserved", C.c_int32)]
 
 
+class _LastWord(C.Union):
+    """the last word of dpm_launch_opts: `table_mode` since version 208; `reserved` is the name it had before (bindings
+    written against 207 zero it through that name)"""
+    _fields_ = [("table_mode", C.c_int32), ("reserved", C.c_int32 * 1)]
+
+
 class LaunchOpts(C.Structure):
     """dpm_launch_opts: what a caller may choose per call (zero = defaults)"""
+    _anonymous_ = ("_last",)
     _fields_ = [("cluster_in_graph", C.c_int32), ("no_fuse", C.c_int32), ("thr_spin_limit", C.c_int32),
                 ("per_request_stages", C.c_int32), ("noise_seed_lo", C.c_uint32), ("noise_seed_hi", C.c_uint32),
-                ("fuse_shapes", C.c_int32), ("reserved", C.c_int32 * 1)]
+                ("fuse_shapes", C.c_int32), ("_last", _LastWord)]
 
 
 class Buffers(C.Structure):
@@ -274,9 +284,11 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 207:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 207 -- stale library, rebuild"
+if lib.dpm_version() < 208:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 208 -- stale library, rebuild"
                       % lib.dpm_version())
+TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
+TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16
 
 
 if IS_LAB and os.environ.get("DPM_LAB_TUNE"):

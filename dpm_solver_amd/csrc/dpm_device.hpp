@@ -141,3 +141,4 @@ const void* dpm_catchall_scalar_unipc();  // the UniPC stages' one-element-per-l
 #include "dpm_aux_kernels.hpp"
 #include "dpm_launch.hpp"
 #include "dpm_shapes_kernel.hpp"
+#include "dpm_table_kernel.hpp"

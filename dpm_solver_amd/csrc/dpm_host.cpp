@@ -46,6 +46,8 @@ extern "C" size_t dpm_sizeof(int which) {
     case DPM_SIZEOF_ADAPTIVE_DESC: return sizeof(dpm_adaptive_desc);
     case DPM_SIZEOF_LAUNCH_OPTS: return sizeof(dpm_launch_opts);
     case DPM_SIZEOF_STAGE_F64: return sizeof(dpm_stage_f64);
+    case DPM_SIZEOF_TABLE_HEADER: return DPM_TABLE_HEADER_BYTES;
+    case DPM_SIZEOF_TABLE_ROW: return DPM_TABLE_ROW_BYTES;
   }
   return 0;
 }

@@ -2,6 +2,7 @@
 // (state dtype, network-output dtype) pairs the stage kernels are built for, and ONE declaration of every function that
 // is defined in one translation unit and called from another.  Included by dpm_device.hpp and by dpm_host.cpp.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "dpm_hip.h"
@@ -18,7 +19,7 @@
 
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
-// pair's catch-all kernels, unit B the heterogeneous fused launchers.
+// pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -37,6 +38,16 @@ int dpm_launch_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* 
 // tile space does not fit the kernel's 32-bit index
 template <typename TS, typename TE>
 int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
+
+// (unit C) the table of dpm_launch_opts.table_mode (include/dpm_hip.h): a 16-byte header, then rows of 8 pointers and the
+// kernels' 80-byte stage scalars (TableRow, dpm_table_kernel.hpp)
+constexpr size_t DPM_TABLE_HEADER_BYTES = 16, DPM_TABLE_ROW_BYTES = 8 * 8 + 80;
+// DPM_TABLE_FILL: the rows of one group, members in call order, into HOST memory (no HIP call)
+template <typename TS, typename TE>
+int dpm_table_fill(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows);
+// DPM_TABLE_LAUNCH: one launch over the group's run of rows in DEVICE memory
+template <typename TS, typename TE>
+int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

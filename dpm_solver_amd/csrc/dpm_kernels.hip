@@ -33,16 +33,20 @@ using UnitFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*
                        const dpm_buffers*, int);
 using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
+using TableFillFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
+using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
   FusedFn fused;
   HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
+  TableFillFn table_fill;      // unit C's table-driven launcher (dpm_launch_opts.table_mode): the rows of a group, on the host,
+  TableLaunchFn table_launch;  // ... and the one launch over them
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
-   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>},
+   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -233,52 +237,108 @@ int het_third_form(const dpm_stage& s) { return s.form == DPM_FORM_MS3 || s.form
 // records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
 // all share one n still takes the kernels it always took, one with at least two takes the mixed-shape family -- or, should
 // its tile space not fit that family's 32-bit index, single launches.
-int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
+// table_mode (DPM_TABLE_FILL / DPM_TABLE_LAUNCH; `table` = bs[0].workspace, checked by the caller): the same walk without
+// the cap of HET_MAX -- a group is bounded by its launch's 2^31 super-tiles only.  A group of TABLE_MIN members or more owns
+// a run of consecutive table rows, members in call order, the runs in the order the groups open: FILL writes them (host
+// memory, no HIP call, nothing launched) and the header, LAUNCH launches one table kernel per run; every smaller group and
+// every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this one function, so
+// their row order is the same.
+int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r])) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
+  const bool fill = table_mode == DPM_TABLE_FILL;
+  char* const rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
+  int64_t n_rows = 0;
+  uint32_t n_runs = 0;
   std::vector<char> done((size_t)n_req, 0);
-  dpm_stage gs[HET_MAX];
-  dpm_buffers gb[HET_MAX];
-  int gi[HET_MAX];
+  std::vector<dpm_stage> gs((size_t)HET_MAX);
+  std::vector<dpm_buffers> gb((size_t)HET_MAX);
+  std::vector<int> gi((size_t)HET_MAX);
   for (int r0 = 0; r0 < n_req; ++r0) {
     if (done[r0]) continue;
     int cnt = 0, third = 0;
     if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
-      for (int r = r0; r < n_req && cnt < HET_MAX; ++r)
+      const int64_t cap = table_mode ? table_group_cap(bs[r0].n) : HET_MAX;
+      for (int r = r0; r < n_req && cnt < cap; ++r)
         if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r], shapes)) {
           const int f = het_third_form(st[r]);
           if (f && third && f != third) continue;
           if (f) third = f;
+          if ((size_t)cnt == gs.size()) {
+            gs.resize(2 * gs.size());
+            gb.resize(gs.size());
+            gi.resize(gs.size());
+          }
           gs[cnt] = st[r];
           gb[cnt] = bs[r];
           gi[cnt++] = r;
         }
     }
-    if (cnt > 1) {
+    // SDE groups have no table kernel: beyond HET_MAX members they go in launches of HET_MAX, as in mode 0
+    const bool tabled = table_mode && cnt >= TABLE_MIN && !(st[r0].flags & DPM_F_NOISE);
+    if (tabled) {
       const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
-      bool mixed = false;
-      for (int k = 1; k < cnt; ++k) mixed = mixed || gb[k].n != gb[0].n;
-      int rc = mixed ? p.het_shapes(gs, gb, cnt, stream) : p.het(gs, gb, cnt, stream);
-      if (rc == MULTI_NOT_BUILT) {
-        rc = DPM_OK;
-        for (int k = 0; k < cnt && !rc; ++k) rc = dpm_stage_launch_ev(&gs[k], &gb[k], stream, nullptr, nullptr);
-      }
+      void* run = rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
+      const int rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch(gs.data(), gb.data(), cnt, run, stream);
       if (rc) return rc;
+      n_rows += cnt;
+      n_runs += 1;
+      for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
+    } else if (cnt > 1) {
+      const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
+      for (int k0 = 0; k0 < cnt && !fill; k0 += HET_MAX) {  // (mode 0: one round, cnt <= HET_MAX)
+        const int m = std::min(HET_MAX, cnt - k0);
+        const dpm_stage* ms = gs.data() + k0;
+        const dpm_buffers* mb = gb.data() + k0;
+        bool mixed = false;
+        for (int k = 1; k < m; ++k) mixed = mixed || mb[k].n != mb[0].n;
+        int rc = m < 2 ? MULTI_NOT_BUILT : mixed ? p.het_shapes(ms, mb, m, stream) : p.het(ms, mb, m, stream);
+        if (rc == MULTI_NOT_BUILT) {
+          rc = DPM_OK;
+          for (int k = 0; k < m && !rc; ++k) rc = dpm_stage_launch_ev(&ms[k], &mb[k], stream, nullptr, nullptr);
+        }
+        if (rc) return rc;
+      }
       for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
     } else {
-      if (const int rc = dpm_stage_launch_ev(&st[r0], &bs[r0], stream, nullptr, nullptr)) return rc;
+      if (!fill)
+        if (const int rc = dpm_stage_launch_ev(&st[r0], &bs[r0], stream, nullptr, nullptr)) return rc;
       done[r0] = 1;
     }
   }
+  if (fill) {
+    const uint32_t header[4] = {DPM_TABLE_MAGIC, (uint32_t)DPM_HIP_VERSION, (uint32_t)n_req, n_runs};
+    static_assert(sizeof header == DPM_TABLE_HEADER_BYTES, "the table header is four words");
+    std::memcpy(table, header, sizeof header);
+  }
+  return DPM_OK;
+}
+
+// the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
+int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
+  if (o->table_mode != DPM_TABLE_FILL && o->table_mode != DPM_TABLE_LAUNCH)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH)", o->table_mode);
+  if (o->per_request_stages != 1)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");
+  if (o->fuse_shapes == 1)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with fuse_shapes (the table kernels take one n per launch)");
+  if (!bs[0].workspace || reinterpret_cast<uintptr_t>(bs[0].workspace) % 16 != 0)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs the table in bs[0].workspace, 16-byte aligned");
+  if (st[0].flags & DPM_F_THRESH)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with DPM_F_THRESH in st[0] (bs[0].workspace is the table)");
   return DPM_OK;
 }
 }  // namespace
 
 extern "C" int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream) {
-  if (st && bs && n_req >= 1 && bs[0].opts && bs[0].opts->per_request_stages == 1)
-    return stage_launch_multi_het(st, bs, n_req, stream);
+  const dpm_launch_opts* o = st && bs && n_req >= 1 ? bs[0].opts : nullptr;
+  if (o && o->table_mode != 0) {
+    if (const int rc = check_table_mode(o, st, bs)) return rc;
+    return stage_launch_multi_het(st, bs, n_req, stream, o->table_mode, bs[0].workspace);
+  }
+  if (o && o->per_request_stages == 1) return stage_launch_multi_het(st, bs, n_req, stream, 0, nullptr);
   return dpm_stage_launch_multi_ev(st, bs, n_req, stream, nullptr, nullptr, nullptr);
 }
 

@@ -1,11 +1,13 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled ten times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1> (__graft_entry__.py).
+// translation unit: compiled fifteen times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
 //               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
+//   unit C (2): the table-driven heterogeneous launcher (stage_kernel_table, stage_kernel_table_unipc) and nothing else -- a
+//               unit of its own, so that units A and B compile to the code they compiled to before it existed
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -29,6 +31,7 @@ template const void* dpm_catchall_scalar_noise<State, Eps>();
 template const void* dpm_catchall_scalar_unipc<State, Eps>();
 #endif
 
+#if DPM_UNIT != 2
 template <typename TS, typename TE, unsigned FORMS>
 int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
                     const dpm_stage* dyn, const int32_t* skip, const dpm_buffers* multi, int n_multi) {
@@ -39,6 +42,7 @@ int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, voi
 template int dpm_launch_unit<State, Eps, DPM_UNIT == 0 ? FORMS_A : FORMS_B>(const dpm_stage*, const dpm_buffers*, void*,
                                                                              void*, void*, const dpm_stage*, const int32_t*,
                                                                              const dpm_buffers*, int);
+#endif
 
 #if DPM_UNIT == 0
 template <typename TS, typename TE>
@@ -63,4 +67,20 @@ int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req,
   return launch_het_shapes_typed<TS, TE>(st, bs, n_req, s);
 }
 template int dpm_launch_het_shapes<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
+#endif
+
+#if DPM_UNIT == 2
+template <typename TS, typename TE>
+int dpm_table_fill(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows) {
+  table_fill_rows(st, bs, n_req, rows);
+  return DPM_OK;
+}
+template int dpm_table_fill<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
+
+template <typename TS, typename TE>
+int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_typed<TS, TE>(st, bs, n_req, rows, s);
+}
+template int dpm_table_launch<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 #endif

@@ -1,0 +1,190 @@
+// dpm_table_kernel.hpp -- the table-driven heterogeneous fused stage (dpm_launch_opts.table_mode): stage_kernel_het /
+// stage_kernel_het_unipc with their per-request records in DEVICE memory instead of the kernel arguments, and their
+// launcher (part of dpm_device.hpp; include that)
+#pragma once
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// A server's common case is hundreds of requests of one or a few images each.  The heterogeneous kernels keep their records
+// in the kernel arguments -- HET_MAX = 16 per launch, HIP's 4 KiB -- so 256 single-image requests advance as 16 launches of
+// half a megabyte each, every one of them latency-bound.  Here request r's record is row r of a table in global memory: a
+// kernel-argument pointer to fixed-size rows, the 8 pointers in HetArgs order, then the KParams (make_params, as for every
+// other launch).  The host fills the table (DPM_TABLE_FILL, no HIP call), the CALLER copies it to the device, and
+// DPM_TABLE_LAUNCH launches one kernel over a run of rows, whatever their number.
+// Everything else is stage_kernel_het's: one n per launch, r = v / spr, one super-tile per 256-lane group, no loop, MultiShape's
+// tiles and cache policy, the XCD-contiguous remap, stage_tiles called with the request's pointers and record -- every request
+// gets the bits of its own single launch.
+// The row is read IN PLACE through the const __restrict__ table pointer with the wave-uniform r: every field is a scalar
+// load (the kernel never writes the table, and writes nothing with scalar instructions).  No row is expanded into a local
+// KParams: see the comment above HetArgs on what the backend does with such a copy.
+// ------------------------------------------------------------------------------------------------
+// A pointer loaded from the kernarg segment is known to the compiler to be a global one; a plain `void*` loaded from a table
+// in global memory is a flat one, and every access through it a flat_load / flat_store (two counters to wait on, an
+// aperture check per access).  The rows hold device-memory pointers only, and their fields say so: the tile body's accesses
+// are stage_kernel_het's global_load / global_store again.
+#define DPM_GLOBAL_PTR __attribute__((address_space(1)))
+struct TableRow {
+  const DPM_GLOBAL_PTR void* x;
+  const DPM_GLOBAL_PTR void* e0;
+  const DPM_GLOBAL_PTR void* e1;
+  const DPM_GLOBAL_PTR void* h1;
+  const DPM_GLOBAL_PTR void* h2;
+  DPM_GLOBAL_PTR void* xo;
+  DPM_GLOBAL_PTR void* mo;
+  DPM_GLOBAL_PTR void* xo2;  // classifier-free guidance: the second half of the [2B, ...] network input (or null)
+  KParams p;
+};
+static_assert(sizeof(TableRow) == DPM_TABLE_ROW_BYTES && sizeof(TableRow) % 16 == 0,
+              "include/dpm_hip.h documents the table row: 8 pointers, then 20 words of stage scalars");
+// the smallest group that takes the table family: one more than the kernarg records hold.  Groups of 2..HET_MAX keep
+// stage_kernel_het, whose records need no dependent global load in front of the tile's own.
+constexpr int TABLE_MIN = HET_MAX + 1;
+// an nt-mask bit stage_tiles does not read (see NT_SHAPES): these kernels get tile bodies of their own, and the kernels a
+// pool without a table was measured with keep their listings
+constexpr int NT_TABLE = 32;
+
+// FORMS = HET_FORMS_2 or HET_FORMS_3, as stage_kernel_het
+template <typename TS, typename TE, unsigned FORMS, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_table(const TableRow* __restrict__ rows, int64_t n,
+                                                                        uint32_t nreq, uint32_t spr, uint32_t xcd_span) {
+  const int64_t ngroups = n / EPT;
+  const uint32_t total = nreq * spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (xcd_span && in_xcd >= xcd_span) return;
+  const uint32_t v = xcd_span ? (b & 7u) * xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v / spr));
+  const int64_t t0 = (int64_t)(v - r * spr) * U;
+  const TableRow& row = rows[r];
+  const KParams& p = row.p;
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = (void*)row.xo2;
+  const TS* x = (const TS*)row.x;
+  const TE* e0 = (const TE*)row.e0;
+  const TE* e1 = (const TE*)row.e1;
+  const TS* h1 = (const TS*)row.h1;
+  const TS* h2 = (const TS*)row.h2;
+  TS* xo = (TS*)row.xo;
+  TS* mo = (TS*)row.mo;
+#define DPM_TABLE_TILES(F_) \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP>(x, nullptr, e0, e1, nullptr, h1, h2, xo, mo, ngroups, t0, p, ext)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_TABLE_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_TABLE_TILES(DPM_FORM_TWO); break;
+    case DPM_FORM_MS3:
+      if constexpr ((FORMS >> DPM_FORM_MS3) & 1u) DPM_TABLE_TILES(DPM_FORM_MS3);
+      break;
+    default: break;  // (the host groups only forms of FORMS)
+  }
+#undef DPM_TABLE_TILES
+}
+
+// {LIN1, TWO, UNIPC}, as stage_kernel_het_unipc: the UniPC sub-shapes are wave-uniform bits of the row's record
+template <typename TS, typename TE, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_table_unipc(const TableRow* __restrict__ rows, int64_t n,
+                                                                              uint32_t nreq, uint32_t spr, uint32_t xcd_span) {
+  static_assert(GUIDE != DPM_GUIDE_CLASSIFIER, "unipc: no classifier guidance");
+  const int64_t ngroups = n / EPT;
+  const uint32_t total = nreq * spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (xcd_span && in_xcd >= xcd_span) return;
+  const uint32_t v = xcd_span ? (b & 7u) * xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v / spr));
+  const int64_t t0 = (int64_t)(v - r * spr) * U;
+  const TableRow& row = rows[r];
+  const KParams& p = row.p;
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = (void*)row.xo2;
+  const TS* x = (const TS*)row.x;
+  const TE* e0 = (const TE*)row.e0;
+  const TE* e1 = (const TE*)row.e1;
+  const TS* h1 = (const TS*)row.h1;
+  const TS* h2 = (const TS*)row.h2;
+  TS* xo = (TS*)row.xo;
+  TS* mo = (TS*)row.mo;
+#define DPM_TABLE_TILES(F_) \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP>(x, nullptr, e0, e1, nullptr, h1, h2, xo, mo, ngroups, t0, p, ext)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_TABLE_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_TABLE_TILES(DPM_FORM_TWO); break;
+    case DPM_FORM_UNIPC: DPM_TABLE_TILES(DPM_FORM_UNIPC); break;
+    default: break;  // (the host groups LIN1 / TWO / UNIPC only)
+  }
+#undef DPM_TABLE_TILES
+}
+
+// the most members a table group of n-element requests may have: the launch's super-tiles (and its workgroups, eight
+// XCD spans rounded up) stay below 2^31.  Counted at one tile per super-tile, whatever the pair's U: one rule for every dtype.
+inline int64_t table_group_cap(int64_t n) {
+  const int64_t spr = (n / EPT + 255) / 256;
+  return std::max<int64_t>(1, (((int64_t)1 << 31) - 16) / std::max<int64_t>(spr, 1));
+}
+
+// ---- DPM_TABLE_FILL: the rows of one group (grouped by the caller as for launch_het_typed), members in call order.  Host
+// memory, no HIP call.
+inline void table_fill_rows(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows) {
+  TableRow* out = static_cast<TableRow*>(rows);
+  for (int r = 0; r < n_req; ++r) {
+    TableRow row;
+    std::memset(&row, 0, sizeof row);
+    const void* const ptrs[8] = {bs[r].x, bs[r].e0, bs[r].e1, bs[r].h1, bs[r].h2, bs[r].x_out, bs[r].m_out, bs[r].x_out2};
+    static_assert(offsetof(TableRow, p) == sizeof ptrs, "a row is its 8 pointers, then the stage scalars");
+    std::memcpy(&row, ptrs, sizeof ptrs);
+    row.p = make_params(&st[r]);
+    std::memcpy(&out[r], &row, sizeof row);
+  }
+}
+
+// ---- DPM_TABLE_LAUNCH: ONE launch over the group's run of rows (device memory: a byte copy of what table_fill_rows wrote for
+// the same st / bs).  The prologue and the form set come from the host's records, as in launch_het_typed; the launch shape
+// is the het kernels' (fused_grid).
+template <typename TS, typename TE>
+int launch_table_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const LaunchCtx& c) {
+  if (n_req < 1 || (int64_t)n_req > table_group_cap(bs[0].n))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one table launch", n_req);
+  const Tuning tn = tuning_for(bs[0].opts);
+  bool ms3 = false, unipc = false;
+  bool x0 = !tn.force_generic;
+  for (int r = 0; r < n_req; ++r) {
+    ms3 = ms3 || st[r].form == DPM_FORM_MS3;
+    unipc = unipc || st[r].form == DPM_FORM_UNIPC;
+    x0 = x0 && x0_prologue_ok(st[r]);
+  }
+  if ((st[0].flags & DPM_F_NOISE) || (unipc && ms3))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: an SDE stage, or UniPC next to third-order stages, in a table launch");
+  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
+  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  const TableRow* tab = static_cast<const TableRow*>(rows);
+  const int64_t n = bs[0].n;
+  const uint32_t nreq = (uint32_t)n_req;
+  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
+  if (unipc) {
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_table_unipc<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq, sh.spr,
+             sh.xcd_span);
+    });
+  } else if (ms3) {
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_table<TS, TE, HET_FORMS_3, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq,
+             sh.spr, sh.xcd_span);
+    });
+  } else {
+    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+      launch(stage_kernel_table<TS, TE, HET_FORMS_2, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq,
+             sh.spr, sh.xcd_span);
+    });
+  }
+  return launch_status("table stage kernel launch failed");
+}
+
+}  // namespace

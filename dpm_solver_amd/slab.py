@@ -1,0 +1,435 @@
+"""Continuous batching of SMALL requests: a slab pool (`DPM_Solver.request_pool(slots=S)`).
+
+`RequestPool` calls the network once per active request and advances 16 requests per stage launch; with hundreds of requests of
+one or a few images each, a tick is hundreds of batch-1 network calls.  The slab pool turns the tick around:
+
+    pool = dpm_solver.request_pool(slots=256)
+    h = pool.submit(x_T, steps=20, order=2, condition=c)        # x_T of [b, *sample_shape] takes b of the 256 rows
+    done = pool.step()                                          # {handle: result} of the requests that finished
+    while pool:
+        done.update(pool.step())
+
+One row of the pool is one sample.  The pool owns two state slabs `[S, *sample_shape]` it ping-pongs between (`[2S, ...]` under
+classifier-free guidance: a stage's duplicate store goes to row S + s, replacing torch.cat([x] * 2)), three history slabs for
+the cached model values and, for a conditional network, a condition slab (`[2S, *cond_shape]` under guidance, the
+unconditional half first).  A tick is
+
+  * ONE network call on the whole current slab with a per-row time vector -- idle rows included, their output is ignored;
+  * ONE host-to-device copy carrying the tick's table and the NEXT tick's time vector;
+  * ONE stage kernel: dpm_stage_launch_multi in table mode (dpm_launch_opts.table_mode: DPM_TABLE_FILL on the host, the copy,
+    DPM_TABLE_LAUNCH), every row a request of n = one sample with the stage record of its own position in its own plan.
+    (Groups of 16 rows or fewer, and rows the fused kernels do not take, are launched as in a `RequestPool`, in the same call.)
+
+The host side of a tick does not loop over requests: the stage records of every plan live in one numpy array, a tick gathers
+them by (plan, position) and computes every pointer as base + row * stride.  Staging is a small ring of pinned buffers, each
+guarded by the event behind its copy: no host synchronisation in steady state.  (A tick that admits requests pays a second,
+small copy: the time vector that rode with the previous tick's table does not know them.)
+
+Guarantee: every result is bit-identical to `sample(x, ...)` / `sample_unipc(x, ...)` on the request alone -- for a network
+whose output row depends only on its input row, its time and its condition row.  A real network's own batch-variance (kernels
+chosen by batch size, batch statistics) is outside this.  Occupancy below S wastes network work in proportion: every tick
+evaluates all S rows; compaction of a sparse slab is out of scope.
+
+Admitted: multistep ODE requests (`submit`) and UniPC requests (`submit_unipc`), unconditional or classifier-free (the guidance
+scale stays the wrapper's; conditions may be per request).  Everything else is refused with NotImplementedError: see `submit`.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _device as DV
+from . import _lib as L
+from . import unipc as _unipc
+
+_RING = 4
+_STAGE = np.dtype(L.Stage)
+_BUFS = np.dtype(dict(names=[n for n, _ in L.Buffers._fields_],
+                      formats=[{4: np.int32, 8: np.uint64}[getattr(L.Buffers, n).size] for n, _ in L.Buffers._fields_],
+                      offsets=[getattr(L.Buffers, n).offset for n, _ in L.Buffers._fields_], itemsize=C.sizeof(L.Buffers)))
+assert _STAGE.itemsize == C.sizeof(L.Stage)
+
+
+def _runs(rows):
+    """the sorted row list as (first, count) runs of consecutive rows"""
+    out = []
+    for r in rows:
+        if out and out[-1][0] + out[-1][1] == r:
+            out[-1][1] += 1
+        else:
+            out.append([r, 1])
+    return out
+
+
+class _Waiting:
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf")
+
+
+class SlabPool:
+    """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
+
+    def __init__(self, solver, slots):
+        slots = int(slots)
+        if slots < 1:
+            raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
+        self._s, self.S = solver, slots
+        self._wait = []                  # FIFO of _Waiting: requests that found too few free rows
+        self._rows = {}                  # handle -> (rows, memory format of x_T) of the admitted requests
+        self._free = list(range(slots))  # sorted
+        self._next = 0
+        self._like = None                # (sample shape, dtype, device)
+        self._plans = {}                 # id(plan) -> (offset into the record arrays, plan)
+        self._recs = np.zeros(0, dtype=_STAGE)
+        self._off = np.zeros(slots, dtype=np.int64)      # per row: its plan's offset, its position, its plan's length,
+        self._pos = np.zeros(slots, dtype=np.int64)      # its request's handle (-1: idle)
+        self._len = np.zeros(slots, dtype=np.int64)
+        self._req = np.full(slots, -1, dtype=np.int64)
+        self._opts = L.LaunchOpts()
+        self._tick = 0
+        self._t_next = None              # host copy of the time vector that rode with the last table, and where it is
+        self._t_dev = None
+        self.copies = 0                  # host-to-device copies issued (diagnostics: one per tick in steady state)
+
+    def __len__(self):
+        return len(self._rows) + len(self._wait)
+
+    def __bool__(self):
+        return len(self) > 0
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # submitting
+    # ------------------------------------------------------------------------------------------------------------------
+    def _refuse(self, method='multistep', sde=False, return_intermediate=False):
+        s = self._s
+        if method != 'multistep':
+            raise NotImplementedError("slab pool: method={!r} -- a singlestep or adaptive update evaluates the network on an "
+                                      "intermediate state, and a slab row's evaluation state is its state; use "
+                                      "request_pool() without slots".format(method))
+        if sde:
+            raise NotImplementedError("slab pool: sde=True -- SDE stages have no table kernel; use request_pool() without slots")
+        if s._thresholding:
+            raise NotImplementedError("slab pool: correcting_x0_fn='dynamic_thresholding' -- thresholded stages have no table "
+                                      "kernel; use request_pool() without slots")
+        if s._wrapped is not None and s._wrapped.effective_guidance == "classifier":
+            raise NotImplementedError("slab pool: classifier guidance -- the classifier's gradient is a second network call per "
+                                      "request; use request_pool() without slots")
+        if s._user_x0 is not None or s.correcting_xt_fn is not None:
+            raise NotImplementedError("slab pool: a correcting_x0_fn / correcting_xt_fn runs Python between stages; sample with "
+                                      "sample()")
+        if return_intermediate:
+            raise NotImplementedError("slab pool: return_intermediate is not supported; sample it with sample()")
+
+    def _check_state(self, x):
+        """the refusals that depend on x's dtype, then the device requirement and the pool's own checks"""
+        s = self._s
+        sd = s._sdtype(x)
+        if sd is torch.float64:
+            raise NotImplementedError("slab pool: double-precision states (the table kernels take 2- and 4-byte states)")
+        if sd in (torch.float16, torch.bfloat16) and s._state_dtype is None:
+            raise NotImplementedError("slab pool: a half-precision slab needs a solver built with an explicit state_dtype -- "
+                                      "the reference's type promotion would depend on the first network output")
+        DV._require_gpu(x)
+        if not torch.is_tensor(x) or x.dim() < 1 or x.numel() == 0:
+            raise ValueError("slab pool: x must be a tensor [b, *sample_shape] with at least one element")
+        like = (tuple(x.shape[1:]), x.dtype, x.device)
+        if self._like is not None and like != self._like:
+            raise ValueError("slab pool: x of sample shape %s, dtype %s on %s does not match the pool's %s, %s on %s"
+                             % (like + self._like))
+        if x.shape[0] > self.S:
+            raise ValueError("slab pool: a request of %d samples does not fit %d slots" % (x.shape[0], self.S))
+        return like, sd
+
+    def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
+               lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
+               condition=None, unconditional_condition=None):
+        """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
+        validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
+        request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
+        adaptive methods, sde=True, a thresholding solver, classifier guidance, correcting_x0_fn / correcting_xt_fn,
+        return_intermediate, double states, and a half-precision slab on a solver without an explicit state_dtype.  A request
+        that finds fewer than b free rows waits (first in, first out) and is admitted by a later step().  Returns the
+        request's handle."""
+        s = self._s
+        self._refuse(method, sde, return_intermediate)
+        t_0 = 1. / s.noise_schedule.total_N if t_end is None else t_end
+        t_T = s.noise_schedule.T if t_start is None else t_start
+        assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
+        with torch.no_grad():
+            plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
+                                  solver_type)
+        return self._enqueue(x, plan, condition, unconditional_condition)
+
+    def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
+                     corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
+                     condition=None, unconditional_condition=None):
+        """Admit a UniPC request: `sample_unipc()`'s arguments, checks and errors in its order, then the pool's; the two
+        condition arguments as for `submit`.  `corrector=False` (variant 'bh2') admits sample()'s multistep plan."""
+        s = self._s
+        _unipc.check_solver(s, order, variant)
+        t_0, t_T = _unipc._times(s, t_start, t_end)
+        self._refuse(return_intermediate=return_intermediate)
+        if not torch.is_tensor(x):
+            DV._require_gpu(x)
+        _unipc.check_state(s, x)
+        if not corrector:
+            if variant != 'bh2':
+                raise NotImplementedError("sample_unipc: corrector=False with variant='bh1' (the predictor alone is built for "
+                                          "'bh2', where it is DPM-Solver++ 2M)")
+            return self.submit(x, steps=steps, t_start=t_start, t_end=t_end, order=order, skip_type=skip_type,
+                               lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero, solver_type='dpmsolver',
+                               condition=condition, unconditional_condition=unconditional_condition)
+        with torch.no_grad():
+            plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
+                                  'dpmsolver', unipc=variant)
+        return self._enqueue(x, plan, condition, unconditional_condition)
+
+    def _conditions(self, b, cond, uncond):
+        """the request's condition tensors, checked against the wrapper's guidance kind (None where the network takes none)"""
+        w = self._s._wrapped
+        if w is None or w.guidance_type != "classifier-free":
+            if cond is not None or uncond is not None:
+                raise ValueError("slab pool: `condition` / `unconditional_condition` belong to a classifier-free wrapper")
+            return None, None
+        cfg = w.effective_guidance == "classifier-free"
+        cond = w.condition if cond is None else cond
+        uncond = (w.unconditional_condition if uncond is None else uncond) if cfg else None
+        for name, c in (("condition", cond), ("unconditional_condition", uncond)):
+            if c is None and (name == "condition" or cfg):
+                raise ValueError("slab pool: the request has no %s and the wrapper has none" % name)
+            if c is not None and (not torch.is_tensor(c) or c.dim() < 1 or c.shape[0] not in (1, b)):
+                raise ValueError("slab pool: %s must be a tensor of leading dimension %d or 1" % (name, b))
+        if uncond is not None and (uncond.shape[1:] != cond.shape[1:] or uncond.dtype != cond.dtype):
+            raise ValueError("slab pool: condition and unconditional_condition differ in shape or dtype")
+        return cond, uncond
+
+    def _enqueue(self, x, plan, cond, uncond):
+        like, sd = self._check_state(x)
+        if plan.slots > 3:
+            raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
+        cond, uncond = self._conditions(int(x.shape[0]), cond, uncond)
+        if self._like is None:
+            self._allocate(like, sd, cond)
+        elif cond is not None and (tuple(cond.shape[1:]), cond.dtype) != (tuple(self._cslab.shape[1:]), self._cslab.dtype):
+            raise ValueError("slab pool: a condition of shape %s, dtype %s does not match the pool's %s, %s"
+                             % (tuple(cond.shape[1:]), cond.dtype, tuple(self._cslab.shape[1:]), self._cslab.dtype))
+        q = _Waiting()
+        q.h, q.x, q.plan, q.cond, q.uncond, q.mf = self._next, x, plan, cond, uncond, DV._mf_of(x)
+        self._next += 1
+        self._wait.append(q)
+        return q.h
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # storage
+    # ------------------------------------------------------------------------------------------------------------------
+    def _allocate(self, like, sd, cond):
+        s, S = self._s, self.S
+        shape, _, dev = like
+        self._like, self._sd = like, sd
+        w = s._wrapped
+        self._cfg = w is not None and w.effective_guidance == "classifier-free"
+        self._nS = nS = 2 * S if self._cfg else S
+        self._per = per = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        self._rowb = per * torch.empty((), dtype=sd).element_size()
+        self._x = [torch.zeros((nS,) + shape, dtype=sd, device=dev) for _ in range(2)]
+        self._hist = [torch.zeros((S,) + shape, dtype=sd, device=dev) for _ in range(3)]
+        self._hbase = np.array([t.data_ptr() for t in self._hist], dtype=np.uint64)
+        self._cur = 0
+        self._cslab = None
+        if cond is not None:
+            self._cslab = torch.zeros((nS,) + tuple(cond.shape[1:]), dtype=cond.dtype, device=dev)
+        # staging: per ring slot a pinned buffer [table | next tick's times | this tick's times | stage array | buffers array]
+        # and a device buffer for its first two parts (and one for the third: the copy an admitting tick adds)
+        self._tabb = (L.TABLE_HEADER_BYTES + S * L.TABLE_ROW_BYTES + 15) // 16 * 16
+        self._copyb = self._tabb + 4 * nS
+        o_cur = (self._copyb + 15) // 16 * 16
+        o_st = (o_cur + 4 * nS + 15) // 16 * 16
+        o_bs = o_st + S * _STAGE.itemsize
+        self._pin, self._dev, self._devt, self._ev, self._views = [], [], [], [None] * _RING, []
+        for _ in range(_RING):
+            pin = DV._pinned_bytes(o_bs + S * _BUFS.itemsize)
+            a = pin.numpy()
+            self._pin.append(pin)
+            self._dev.append(DV._device_bytes(self._copyb, dev))
+            self._devt.append(DV._device_bytes(4 * nS, dev))
+            self._views.append((a[self._tabb:self._copyb].view(np.float32), a[o_cur:o_cur + 4 * nS].view(np.float32),
+                                a[o_st:o_bs].view(_STAGE), a[o_bs:].view(_BUFS), pin[o_cur:o_cur + 4 * nS], a[o_bs:]))
+        self._t_attr = "t_input" if w is not None else "t_eval"
+
+    def _plan_offset(self, plan):
+        hit = self._plans.get(id(plan))
+        if hit is None:
+            n = len(plan.stages)
+            arr = (L.Stage * n)(*[self._s._prep_stage(st.copy()) for st in plan.stages])
+            hit = (len(self._recs), plan)
+            self._recs = np.concatenate([self._recs, np.frombuffer(arr, dtype=_STAGE).copy()])
+            self._plans[id(plan)] = hit
+        return hit[0]
+
+    def _admit(self):
+        """waiting requests, first in first out, into free rows: their x_T (both halves under guidance) and conditions"""
+        S, cur = self.S, self._x[self._cur]
+        while self._wait and int(self._wait[0].x.shape[0]) <= len(self._free):
+            q = self._wait.pop(0)
+            b = int(q.x.shape[0])
+            rows, self._free = self._free[:b], self._free[b:]
+            x = q.x.to(self._sd)
+            k = 0
+            for r0, cnt in _runs(rows):
+                cur[r0:r0 + cnt].copy_(x[k:k + cnt])
+                if self._cfg:
+                    cur[S + r0:S + r0 + cnt].copy_(x[k:k + cnt])
+                if q.cond is not None:
+                    c = q.cond.to(self._cslab.device)
+                    self._cslab[(S if self._cfg else 0) + r0:(S if self._cfg else 0) + r0 + cnt].copy_(
+                        c if c.shape[0] == 1 else c[k:k + cnt])
+                if q.uncond is not None:
+                    u = q.uncond.to(self._cslab.device)
+                    self._cslab[r0:r0 + cnt].copy_(u if u.shape[0] == 1 else u[k:k + cnt])
+                k += cnt
+            ra = np.asarray(rows, dtype=np.int64)
+            self._off[ra], self._pos[ra], self._len[ra], self._req[ra] = self._plan_offset(q.plan), 0, len(q.plan.stages), q.h
+            self._rows[q.h] = (rows, q.mf)
+
+    def _network(self, x, t):
+        """ONE call on the whole slab: the raw output(s) as (e0, e1), e1 the unconditional half under guidance"""
+        s = self._s
+        w = s._wrapped
+        if w is None:
+            return s._model_fn(x, t), None
+        if w.guidance_type != "classifier-free":
+            return w.model(x, t, **w.model_kwargs), None
+        out = w.model(x, t, self._cslab, **w.model_kwargs)
+        if not self._cfg:
+            return out, None
+        e1, e0 = out.chunk(2)
+        return e0, e1
+
+    def _times_of(self, rows, idx):
+        """the [S] (or [2S]) model-time vector of a tick whose active `rows` stand at the records `idx`; idle rows take the
+        first active row's time (their output is ignored)"""
+        t = np.empty(self._nS, dtype=np.float32)
+        ta = self._recs[self._t_attr][idx]
+        t[:] = ta[0] if len(ta) else 0.
+        t[rows] = ta
+        if self._cfg:
+            t[self.S + rows] = ta
+        return t
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # one tick
+    # ------------------------------------------------------------------------------------------------------------------
+    def step(self):
+        """One stage of every active row: one network call, one table launch.  Returns {handle: result} of the requests that
+        finished, fresh tensors in the layout of their x_T."""
+        done = {}
+        if self._like is None or not (self._rows or self._wait):
+            return done
+        s, S = self._s, self.S
+        stream, idx_dev, capturing, other = DV._launch_ctx(self._like[2])
+        if capturing:
+            raise RuntimeError("slab pool: ticks are not captured into graphs")
+        with torch.no_grad():
+            self._admit()
+            rows = np.flatnonzero(self._req >= 0)
+            R = len(rows)
+            if R == 0:
+                return done
+            j = self._tick % _RING
+            self._tick += 1
+            DV._event_wait(self._ev[j])
+            t_next_v, t_cur_v, st_v, b_v, pin_cur, b_raw = self._views[j]
+            idx = self._off[rows] + self._pos[rows]
+            rec = self._recs[idx]
+            # the model-time vector: the one that rode with the previous tick's table, unless rows were admitted since
+            t_now = self._times_of(rows, idx)
+            if self._t_dev is not None and np.array_equal(t_now, self._t_next):
+                t_dev = self._t_dev
+            else:
+                t_cur_v[:] = t_now
+                DV._copy_to_device(self._devt[j], pin_cur)
+                self.copies += 1
+                t_dev = self._devt[j].view(torch.float32)
+            xin, xout = self._x[self._cur], self._x[1 - self._cur]
+            e0, e1 = self._network(xin if self._cfg else xin[:S], t_dev)
+            e0, e1, ed = self._bind(e0, e1)
+            # the tick's records, vectorised: stage r = the record of row rows[r] at its position, pointers = base + row * stride
+            st_v[:R] = rec
+            b = b_v[:R]
+            b_raw[:R * _BUFS.itemsize] = 0
+            rb = rows.astype(np.uint64) * np.uint64(self._rowb)
+            eb = rows.astype(np.uint64) * np.uint64(self._per * e0.element_size())
+            last = self._pos[rows] + 1 == self._len[rows]
+            b["x"] = np.uint64(xin.data_ptr()) + rb
+            b["x_out"] = np.uint64(xout.data_ptr()) + rb
+            if self._cfg:
+                b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + S * self._rowb) + rb)
+                b["e1"] = np.uint64(e1.data_ptr()) + eb
+            b["e0"] = np.uint64(e0.data_ptr()) + eb
+            for name, slot, used in (("h1", rec["h1_slot"], rec["h1_slot"] >= 0), ("h2", rec["h2_slot"], rec["h2_slot"] >= 0),
+                                     ("m_out", rec["m_slot"], (rec["flags"] & L.F_STORE_M) != 0)):
+                b[name] = np.where(used, self._hbase[np.clip(slot, 0, 2)] + rb, np.uint64(0))
+            b["n"], b["batch"] = self._per, 1
+            b["state_dtype"], b["eps_dtype"] = DV._DT[self._sd], DV._DT[ed]
+            o = s._opts_ptr()
+            if o is not None:
+                C.memmove(C.byref(self._opts), o, C.sizeof(L.LaunchOpts))
+                b["opts"] = C.addressof(o.contents)
+            self._opts.per_request_stages, self._opts.fuse_shapes = 1, 0
+            self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
+            b["opts"][0] = C.addressof(self._opts)
+            # next tick's time vector rides with this tick's table
+            go = ~last
+            t_next = self._times_of(rows[go], idx[go] + 1)
+            t_next_v[:] = t_next
+            sts = C.cast(st_v.ctypes.data, C.POINTER(L.Stage))
+            bufs = C.cast(b_v.ctypes.data, C.POINTER(L.Buffers))
+            pin, dev = self._pin[j], self._dev[j]
+
+            def tick():
+                self._opts.table_mode = L.TABLE_FILL
+                b["workspace"][0] = pin.data_ptr()
+                rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
+                if rc == 0:
+                    self._ev[j] = DV._copy_to_device(dev, pin[:self._copyb])
+                    self.copies += 1
+                    self._opts.table_mode = L.TABLE_LAUNCH
+                    b["workspace"][0] = dev.data_ptr()
+                    rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
+                self._opts.table_mode = 0
+                return rc
+            if other:
+                with torch.cuda.device(idx_dev):
+                    rc = tick()
+            else:
+                rc = tick()
+            if rc:
+                L.check(rc)
+            del e0, e1
+            self._t_next, self._t_dev = t_next, dev[self._tabb:self._copyb].view(torch.float32)
+            self._cur = 1 - self._cur
+            self._pos[rows] += 1
+            # finished requests: their rows, cloned from the output slab, are free again
+            for h in np.unique(self._req[rows[last]]).tolist():
+                rws, mf = self._rows.pop(h)
+                parts = [xout[r0:r0 + cnt] for r0, cnt in _runs(rws)]
+                out = parts[0].clone() if len(parts) == 1 else torch.cat(parts)
+                done[h] = out if mf is None else DV._conv(out, out.dtype, mf)
+                self._req[np.asarray(rws, dtype=np.int64)] = -1
+                self._free = sorted(self._free + rws)
+        return done
+
+    def _bind(self, e0, e1):
+        """the network's output as dense slabs of a dtype the kernels pair with the state's (launch_list._bind_outputs)"""
+        sd = self._sd
+        want = (self.S,) + self._like[0]
+        if tuple(e0.shape) != want:
+            raise NotImplementedError("slab pool: a network output of shape %s for an input of %s (channel slices of a wider "
+                                      "output are not bound per row)" % (tuple(e0.shape), want))
+        if e0.dtype is torch.float64 and self._s._state_dtype is None:
+            raise NotImplementedError("slab pool: a double network output promotes the state to double")
+        ed = e0.dtype
+        if ed is not sd and (sd is not torch.float32 or ed not in DV._DT):
+            ed = sd
+        e0 = DV._conv(e0, ed)
+        e1 = DV._conv(e1, ed)
+        return e0, e1, ed

@@ -39,6 +39,7 @@ from . import capture as _capture
 from . import loops as _loops
 from . import plan_cache as _plan_cache
 from . import pool as _pool
+from . import slab as _slab
 from . import sde as _sde
 from . import unipc as _unipc
 from . import updates as _updates
@@ -700,12 +701,20 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False):
+    def request_pool(self, mixed_shapes=False, slots=None):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
         bit-identical to `sample()`; see dpm_solver_amd/pool.py.  `mixed_shapes=True`: the requests may differ in shape (latent
-        size, images per prompt) and still share the tick's launch."""
+        size, images per prompt) and still share the tick's launch.
+        `slots=S`: a `SlabPool` (dpm_solver_amd/slab.py) for MANY SMALL requests -- S rows of one sample each in slabs the
+        pool owns; a tick is one network call on the whole slab, one host-to-device copy and one table-driven stage launch
+        (dpm_launch_opts.table_mode), and every request may bring its own condition."""
+        if slots is not None:
+            if mixed_shapes:
+                raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
+                                 "RequestPool's")
+            return _slab.SlabPool(self, slots)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -65,11 +65,15 @@ extern "C" {
    207 dpm_launch_opts.fuse_shapes (was reserved[0]): dpm_stage_launch_multi with per-request stages fuses requests of
    DIFFERENT n and batch in one launch (a server's 512^2, 768^2 and 1024^2 latents side by side; no entry point added, no
    struct changed size).
+   208 dpm_launch_opts.table_mode (was reserved[0]), DPM_TABLE_FILL / DPM_TABLE_LAUNCH, DPM_SIZEOF_TABLE_HEADER / _ROW:
+   dpm_stage_launch_multi with per-request stages launches a group of MORE than 16 requests as ONE kernel whose per-request
+   records are rows of a table in device memory (hundreds of single-image requests per tick; see "Table mode" at
+   dpm_stage_launch_multi; no entry point added, no struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 207
+#define DPM_HIP_VERSION 208
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -230,8 +234,12 @@ typedef struct dpm_launch_opts {
   int32_t fuse_shapes;      /* version 207 (was reserved[0]); read from bs[0].opts, together with per_request_stages == 1
                                only.  1: the requests of a fused group need not agree on n and batch (see
                                dpm_stage_launch_multi); 0: every call groups and launches as before version 207          */
-  int32_t reserved[1];      /* zero                                                                                   */
+  int32_t table_mode;       /* version 208 (was reserved[0]); read from bs[0].opts, together with per_request_stages == 1
+                               only.  0: every call as before version 208; DPM_TABLE_FILL / DPM_TABLE_LAUNCH: see "Table
+                               mode" at dpm_stage_launch_multi                                                            */
 } dpm_launch_opts;
+enum { DPM_TABLE_FILL = 1, DPM_TABLE_LAUNCH = 2 };
+#define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -406,7 +414,33 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    whole 8-element groups, call order, 16 per launch, MS3 apart from UNIPC).  A group whose members share one n is launched
    exactly as without the flag; a group with at least two different n is ONE launch whose tile space is the members' tiles
    back to back, each request advanced over its own n with the bits of its single launch.  (A group of 2^31 or more
-   super-tiles of 2048 or 4096 elements is launched member by member.) */
+   super-tiles of 2048 or 4096 elements is launched member by member.)
+   Table mode (version 208): the 16 requests per launch above are what HIP's 4 KiB of kernel arguments hold.  With
+   bs[0].opts->table_mode != 0 (and per_request_stages == 1, fuse_shapes == 0) the records of a group of MORE than 16 requests
+   travel as rows of a table in device memory, and the group -- whatever its size, below 2^31 super-tiles -- is ONE launch
+   (stage_kernel_table / stage_kernel_table_unipc).  The table lives in bs[0].workspace: at least
+   dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * dpm_sizeof(DPM_SIZEOF_TABLE_ROW) bytes, 16-byte aligned (NULL or misaligned:
+   DPM_ERR_ARG; so is DPM_F_THRESH in st[0], whose workspace would mean two things -- thresholded requests at r > 0 keep
+   theirs).  Two calls with the SAME st / bs arrays make a tick:
+     DPM_TABLE_FILL    bs[0].workspace is HOST memory.  Checks every request as mode 0 does (same error texts, nothing written
+                       when one fails), groups them by the rules above without the cap of 16, and writes
+                         header  4 x uint32: DPM_TABLE_MAGIC, 208, n_req, the number of groups with rows
+                         rows    from byte dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) on, dpm_sizeof(DPM_SIZEOF_TABLE_ROW) bytes
+                                 each: for every group of more than 16 members a run of consecutive rows, members in call
+                                 order, the runs in the order their groups open.  A row is 8 pointers -- x, e0, e1, h1, h2,
+                                 x_out, m_out, x_out2 of the request's dpm_buffers -- followed by 20 32-bit words of stage
+                                 scalars in the kernels' own layout (opaque: made by the library, read by the library).
+                       Groups of 2..16 members write no rows.  Launches nothing and makes no HIP call at all: it runs on a
+                       machine without a GPU.
+     DPM_TABLE_LAUNCH  bs[0].workspace is DEVICE memory holding a byte copy of what DPM_TABLE_FILL wrote; the copy is the
+                       CALLER's (one hipMemcpyAsync on `stream` between the two calls), and a stale copy is the caller's
+                       error like any stale pointer in dpm_buffers.  Repeats checks and grouping on the host (the same
+                       function: the same row order); a group with rows is ONE launch over its run of rows, every other
+                       group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
+                       allocates nothing and synchronises nothing.
+   SDE stages, mixed n (fuse_shapes), thresholding, mask blend, classifier guidance and DPM_F_STORE_XC are outside the table
+   kernels: in a table call such requests take exactly the path they take in mode 0.  Every request gets the bits of its own
+   dpm_stage_launch.  Any other table_mode, a non-zero one without per_request_stages, or with fuse_shapes == 1: DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
@@ -543,7 +577,8 @@ DPM_API void dpm_graph_destroy(dpm_graph* g);
 DPM_API int dpm_version(void);
 /* sizeof() of the ABI structs as compiled, so a binding can verify its own layout at load time */
 enum { DPM_SIZEOF_STAGE = 0, DPM_SIZEOF_BUFFERS = 1, DPM_SIZEOF_PLAN_DESC = 2, DPM_SIZEOF_RUN_BUFFERS = 3,
-       DPM_SIZEOF_ADAPTIVE_DESC = 4, DPM_SIZEOF_LAUNCH_OPTS = 5, DPM_SIZEOF_STAGE_F64 = 6 };
+       DPM_SIZEOF_ADAPTIVE_DESC = 4, DPM_SIZEOF_LAUNCH_OPTS = 5, DPM_SIZEOF_STAGE_F64 = 6,
+       DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */ };
 DPM_API size_t dpm_sizeof(int which);
 DPM_API const char* dpm_last_error(void); /* thread-local text of the last non-zero return */
 DPM_API int dpm_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len);
