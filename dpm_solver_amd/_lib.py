@@ -47,8 +47,10 @@ TUNE_THR_SPIN_LIMIT, TUNE_THR_DEBUG_FAULT, TUNE_BLOCK_THREADS = 10, 11, 12
 TUNE_FORCE_GENERIC, TUNE_THR_ELECT, TUNE_LDS_DMA, TUNE_THR_STAGGER, TUNE_BIG_TILES = 13, 14, 15, 16, 17
 MULTI_MAX = 32
 TABLE_FILL, TABLE_LAUNCH = 1, 2           # dpm_launch_opts.table_mode (version 208)
+TABLE_NOISE = 4                           # ... a flag on either: SDE stages take rows and noise records too (version 209)
 TABLE_MAGIC = 0x4c425444
 SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
+SIZEOF_TABLE_NOISE = 10                           # ... and of a noise record (9 is unassigned)
 THR_HINT_WORDS = 4
 
 
@@ -93,7 +95,14 @@ class LaunchOpts(C.Structure):
                 ("fuse_shapes", C.c_int32), ("_last", _LastWord)]
 
 
+class _NoiseSample0(C.Union):
+    """the word of dpm_buffers behind `inputs_resident`: `noise_sample0` since version 209; `reserved` is the name it had
+    before, kept on the same bytes"""
+    _fields_ = [("noise_sample0", C.c_int32), ("reserved", C.c_int32)]
+
+
 class Buffers(C.Structure):
+    _anonymous_ = ("_ns0",)
     _fields_ = [
         ("x", C.c_void_p), ("xe", C.c_void_p), ("e0", C.c_void_p), ("e1", C.c_void_p), ("g", C.c_void_p),
         ("h1", C.c_void_p), ("h2", C.c_void_p), ("x_out", C.c_void_p), ("m_out", C.c_void_p),
@@ -101,7 +110,7 @@ class Buffers(C.Structure):
         ("state_dtype", C.c_int32), ("eps_dtype", C.c_int32),
         ("x_out2", C.c_void_p), ("eps_stride", C.c_int64), ("mask", C.c_void_p), ("blend_a", C.c_void_p),
         ("blend_b", C.c_void_p), ("mask_period", C.c_int64),
-        ("inputs_resident", C.c_int32), ("reserved", C.c_int32), ("thr_hint", C.c_void_p),
+        ("inputs_resident", C.c_int32), ("_ns0", _NoiseSample0), ("thr_hint", C.c_void_p),
         ("opts", C.POINTER(LaunchOpts)), ("coef64", C.POINTER(StageF64)),
     ]
 
@@ -284,11 +293,12 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 208:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 208 -- stale library, rebuild"
+if lib.dpm_version() < 209:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 209 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16
+TABLE_NOISE_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_NOISE))        # (TABLE_NOISE) behind the rows, one noise record per row
 
 
 if IS_LAB and os.environ.get("DPM_LAB_TUNE"):

@@ -35,6 +35,8 @@ using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*,
 using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 using TableFillFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+using TableFillNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+using TableLaunchNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
@@ -43,10 +45,13 @@ struct PairUnits {
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
   TableFillFn table_fill;      // unit C's table-driven launcher (dpm_launch_opts.table_mode): the rows of a group, on the host,
   TableLaunchFn table_launch;  // ... and the one launch over them
+  TableFillNoiseFn table_fill_noise;      // (DPM_TABLE_NOISE) rows and noise records of a group of SDE stages
+  TableLaunchNoiseFn table_launch_noise;  // ... and the one launch over them
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
-   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>},
+   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>,      \
+   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -70,11 +75,15 @@ int launch_fused(const PairUnits& p, const dpm_stage* st, const dpm_buffers* bs,
   return p.fused(st, bs, n_req, stream, ev_start, ev_stop);
 }
 
-// The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails
-int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b) {
+// The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
+// base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base)
+int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
+  if (b->noise_sample0 != 0 && !base_ok)
+    return fail(DPM_ERR_ARG, "stage_launch: noise_sample0=%d (honoured by the SDE rows of a DPM_TABLE_NOISE call only)",
+                b->noise_sample0);
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -237,19 +246,51 @@ int het_third_form(const dpm_stage& s) { return s.form == DPM_FORM_MS3 || s.form
 // records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
 // all share one n still takes the kernels it always took, one with at least two takes the mixed-shape family -- or, should
 // its tile space not fit that family's 32-bit index, single launches.
+// dpm_buffers.noise_sample0 of one request of a DPM_TABLE_NOISE call: honoured by a request that will own a noise row (`row`),
+// an error on every other; non-negative, a whole number of Philox blocks
+int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
+  const int32_t k = b.noise_sample0;
+  if (k == 0) return DPM_OK;
+  if (k < 0) return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: noise_sample0=%d is negative", k);
+  if (!(st.flags & DPM_F_NOISE))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: noise_sample0=%d on a stage without DPM_F_NOISE", k);
+  if (!row)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: noise_sample0=%d on a request that fits no fused group (dense, "
+                         "16-byte aligned buffers of whole 8-element groups)", k);
+  const int64_t per = b.n / b.batch;
+  if (per > 0 && (int64_t)k > INT64_MAX / per)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: noise_sample0=%d times %lld elements overflows", k, (long long)per);
+  if (((int64_t)k * per) % 4 != 0)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: noise_sample0=%d times %lld elements is not a multiple of 4 (a "
+                         "row starts at a Philox block)", k, (long long)per);
+  return DPM_OK;
+}
+
 // table_mode (DPM_TABLE_FILL / DPM_TABLE_LAUNCH; `table` = bs[0].workspace, checked by the caller): the same walk without
 // the cap of HET_MAX -- a group is bounded by its launch's 2^31 super-tiles only.  A group of TABLE_MIN members or more owns
 // a run of consecutive table rows, members in call order, the runs in the order the groups open: FILL writes them (host
 // memory, no HIP call, nothing launched) and the header, LAUNCH launches one table kernel per run; every smaller group and
 // every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this one function, so
 // their row order is the same.
+// With DPM_TABLE_NOISE on the mode, SDE groups own rows too, from ONE member on -- a row's noise_sample0 has no other way to
+// the kernel -- and a noise record each behind the n_req rows the table has room for, record i beside row i.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
+  const bool noise_rows = (table_mode & DPM_TABLE_NOISE) != 0;
+  table_mode &= ~DPM_TABLE_NOISE;
   for (int r = 0; r < n_req; ++r)
-    if (const int rc = check_stage_buffers(&st[r], &bs[r])) return rc;
+    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;
+  // does request r own a row of stage_kernel_table_noise?  (a group's first member decides for the group: het_same_group)
+  auto noise_row = [&](int r) {
+    return noise_rows && fuse && (st[r].flags & DPM_F_NOISE) && bs[r].n > 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) &&
+           fusable_request(st[r], bs[r]);
+  };
+  for (int r = 0; noise_rows && r < n_req; ++r)
+    if (const int rc = check_noise_base(st[r], bs[r], noise_row(r))) return rc;
   char* const rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
+  char* const recs = rows + (int64_t)n_req * (int64_t)DPM_TABLE_ROW_BYTES;
   int64_t n_rows = 0;
   uint32_t n_runs = 0;
   std::vector<char> done((size_t)n_req, 0);
@@ -276,12 +317,20 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
           gi[cnt++] = r;
         }
     }
-    // SDE groups have no table kernel: beyond HET_MAX members they go in launches of HET_MAX, as in mode 0
-    const bool tabled = table_mode && cnt >= TABLE_MIN && !(st[r0].flags & DPM_F_NOISE);
+    // SDE groups take the table with DPM_TABLE_NOISE only (stage_kernel_table_noise, from one member on); without the flag
+    // they go as in mode 0, beyond HET_MAX members in launches of HET_MAX
+    const bool sde = (st[r0].flags & DPM_F_NOISE) != 0;
+    const bool tabled = table_mode && (sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
     if (tabled) {
       const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
       void* run = rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
-      const int rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch(gs.data(), gb.data(), cnt, run, stream);
+      void* nzs = recs + n_rows * (int64_t)DPM_TABLE_NOISE_BYTES;
+      int rc;
+      if (sde)
+        rc = fill ? p.table_fill_noise(gs.data(), gb.data(), cnt, run, nzs)
+                  : p.table_launch_noise(gs.data(), gb.data(), cnt, run, nzs, stream);
+      else
+        rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch(gs.data(), gb.data(), cnt, run, stream);
       if (rc) return rc;
       n_rows += cnt;
       n_runs += 1;
@@ -318,8 +367,10 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  if (o->table_mode != DPM_TABLE_FILL && o->table_mode != DPM_TABLE_LAUNCH)
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH)", o->table_mode);
+  const int mode = o->table_mode & ~DPM_TABLE_NOISE;
+  if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
+                         "without DPM_TABLE_NOISE)", o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");
   if (o->fuse_shapes == 1)

@@ -331,6 +331,17 @@ struct KNoise {
   uint32_t ctr;         // dpm_stage.index
   float scale;          // dpm_stage.c2: sigma_t * sqrt(-expm1(-2h))
 };
+// a table row's noise record (stage_kernel_table_noise, dpm_table_kernel.hpp): the request's KNoise and a 64-bit BASE added to
+// the Philox block index.  The row holds samples [k, k + 1) of a request whose flat [B, C, H, W] tensor the noise contract
+// indexes: element i of the row is element k * per + i of the request, block g of the row is block g0 + g, g0 = k * per / 4.
+// stage_tiles<..., BASE = true> reads it through its KNoise pointer; every other kernel has BASE = false and no such code.
+// g0 is ONE 8-byte field: read as two words and put together, the backend merges the loads itself and the merged load is a
+// vector one; a 64-bit load of a wave-uniform address stays a scalar load.
+struct alignas(16) KNoiseTab : KNoise {
+  uint64_t g0;      // low word first
+  uint32_t pad[2];  // (zero)
+};
+static_assert(sizeof(KNoiseTab) == 32 && alignof(KNoiseTab) == 16, "include/dpm_hip.h documents the noise record: 8 words");
 
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -361,6 +372,8 @@ __device__ __forceinline__ void philox_block(const KNoise& nz, uint64_t g, uint3
   c[3] = 0u;
   philox4x32_10(c, nz.key0, nz.key1);
 }
+// the base of a table row's block indices (wave-uniform: two scalar words of the row's record)
+__device__ __forceinline__ uint64_t noise_base(const KNoiseTab& nz) { return nz.g0; }
 // z of the four elements 4g .. 4g+3
 __device__ __forceinline__ void noise4(const KNoise& nz, uint64_t g, float* z) {
   uint32_t c[4];
@@ -417,8 +430,9 @@ __device__ __forceinline__ void tile_models(const float (&vx)[U][EPT], const flo
 // NOISE = the SDE epilogue (stage_kernel_noise): out += nz.scale * z before the store rounding (and before a mask blend, the
 // corrector that runs after the update).  The element index of ox[j]: split layout -> 4-element runs at tile*2048 + 4*lane and
 // tile*2048 + 1024 + 4*lane, else the 8 consecutive elements of group gi -- two Philox blocks per lane either way.
+// BASE (with NOISE) = nz points at a KNoiseTab: its g0 is added to both block indices (64-bit, the carry into the high word).
 template <typename TS, typename TE, int FORM, int GUIDE, bool XE, int SPEC, int U, int NT, bool EXT, bool DMA = false,
-          bool NOISE = false>
+          bool NOISE = false, bool BASE = false>
 __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* __restrict__ xe,
                                             const TE* __restrict__ e0, const TE* __restrict__ e1,
                                             const TE* __restrict__ g, const TS* __restrict__ h1,
@@ -429,6 +443,7 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
   static_assert(!DMA || (sizeof(TS) == 2 && sizeof(TE) == 2 && !EXT && !XE && GUIDE == DPM_GUIDE_NONE && SPEC == SPEC_NOISE_X0 &&
                          U == 1 && (FORM == DPM_FORM_LIN1 || FORM == DPM_FORM_TWO)),
                 "the LDS-DMA variant exists for the lone-launch north-star kernels only");
+  static_assert(!BASE || NOISE, "a block-index base belongs to a noise record");
   constexpr bool SPLIT = sizeof(TS) == 4;  // see load_tile
   const bool need_xe = spec_need_xe<SPEC>(p);
   const bool store_m = p.flags & DPM_F_STORE_M;
@@ -510,8 +525,14 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
       const bool split = can_split && (t0 + u) * 256 + 256 <= ngroups;
       const uint64_t ga = split ? (uint64_t)(t0 + u) * 512u + tile_lane() : 2u * (uint64_t)((t0 + u) * 256 + tile_lane());
       const uint64_t gb = split ? ga + 256u : ga + 1u;
-      noise4(*nz, ga, zn[u]);
-      noise4(*nz, gb, zn[u] + 4);
+      if constexpr (BASE) {
+        const uint64_t g0 = noise_base(*static_cast<const KNoiseTab*>(nz));
+        noise4(*nz, g0 + ga, zn[u]);
+        noise4(*nz, g0 + gb, zn[u] + 4);
+      } else {
+        noise4(*nz, ga, zn[u]);
+        noise4(*nz, gb, zn[u] + 4);
+      }
 #pragma unroll
       for (int j = 0; j < EPT; ++j) asm volatile("" : "+v"(zn[u][j]));  // ahead of the first use of a loaded value
     }
@@ -569,8 +590,14 @@ __device__ __forceinline__ void stage_tiles(const TS* __restrict__ x, const TS* 
       const uint64_t ga = split ? (uint64_t)(t0 + u) * 512u + tile_lane() : 2u * (uint64_t)gi;
       const uint64_t gb = split ? ga + 256u : ga + 1u;
       float z[EPT];
-      noise4(*nz, ga, z);
-      noise4(*nz, gb, z + 4);
+      if constexpr (BASE) {
+        const uint64_t g0 = noise_base(*static_cast<const KNoiseTab*>(nz));
+        noise4(*nz, g0 + ga, z);
+        noise4(*nz, g0 + gb, z + 4);
+      } else {
+        noise4(*nz, ga, z);
+        noise4(*nz, gb, z + 4);
+      }
 #pragma unroll
       for (int j = 0; j < EPT; ++j) ox[j] = ox[j] + nz->scale * z[j];
     }

@@ -4,8 +4,8 @@
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
 //               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
-//   unit C (2): the table-driven heterogeneous launcher (stage_kernel_table, stage_kernel_table_unipc) and nothing else -- a
-//               unit of its own, so that units A and B compile to the code they compiled to before it existed
+//   unit C (2): the table-driven heterogeneous launchers (stage_kernel_table, stage_kernel_table_unipc,
+//               stage_kernel_table_noise) and nothing else -- a unit of its own, so that units A and B compile to the code they compiled to before it existed
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2>"
 #endif
@@ -83,4 +83,19 @@ int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, void
   return launch_table_typed<TS, TE>(st, bs, n_req, rows, s);
 }
 template int dpm_table_launch<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+
+template <typename TS, typename TE>
+int dpm_table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs) {
+  table_fill_rows(st, bs, n_req, rows);
+  table_fill_noise(st, bs, n_req, recs);
+  return DPM_OK;
+}
+template int dpm_table_fill_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+
+template <typename TS, typename TE>
+int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_noise_typed<TS, TE>(st, bs, n_req, rows, recs, s);
+}
+template int dpm_table_launch_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 #endif

@@ -1,6 +1,6 @@
 // dpm_table_kernel.hpp -- the table-driven heterogeneous fused stage (dpm_launch_opts.table_mode): stage_kernel_het /
-// stage_kernel_het_unipc with their per-request records in DEVICE memory instead of the kernel arguments, and their
-// launcher (part of dpm_device.hpp; include that)
+// stage_kernel_het_unipc / stage_kernel_het_noise with their per-request records in DEVICE memory instead of the kernel
+// arguments, and their launchers (part of dpm_device.hpp; include that)
 #pragma once
 
 namespace {
@@ -123,6 +123,52 @@ __global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_table_unipc(co
 #undef DPM_TABLE_TILES
 }
 
+// SDE rows (DPM_TABLE_NOISE): stage_kernel_table with the form set {LIN1, TWO} and stage_kernel_het_noise's epilogue.  The row
+// has no room for the request's KNoise, so the noise records are a second array in device memory, record i beside row i --
+// a second const __restrict__ kernel-argument pointer indexed by the same wave-uniform r: scalar loads, like the row.  The
+// record carries what no kernel-argument launch can: the base g0 of the row's Philox block indices (KNoiseTab), which makes
+// a row one SAMPLE of a request whose other samples sit in other, non-adjacent rows -- each with the z of its own elements.
+// g0 = 0 gives the bits of stage_kernel_het_noise.  Its own family, so that stage_kernel_table stays as it is.
+static_assert(sizeof(KNoiseTab) == DPM_TABLE_NOISE_BYTES, "include/dpm_hip.h publishes the noise record's size");
+template <typename TS, typename TE, int GUIDE, int SPEC, int U, int NT>
+__global__ __launch_bounds__(STAGE_MAX_THREADS) void stage_kernel_table_noise(const TableRow* __restrict__ rows,
+                                                                              const KNoiseTab* __restrict__ nzs, int64_t n,
+                                                                              uint32_t nreq, uint32_t spr, uint32_t xcd_span) {
+  static_assert(GUIDE != DPM_GUIDE_CLASSIFIER, "noise: no classifier guidance");
+  const int64_t ngroups = n / EPT;
+  const uint32_t total = nreq * spr;
+  const uint32_t per = blockDim.x >> 8;
+  const uint32_t sub = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+  const uint32_t b = blockIdx.x;
+  const uint32_t in_xcd = (b >> 3) * per + sub;
+  if (xcd_span && in_xcd >= xcd_span) return;
+  const uint32_t v = xcd_span ? (b & 7u) * xcd_span + in_xcd : b * per + sub;
+  if (v >= total) return;
+  const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v / spr));
+  const int64_t t0 = (int64_t)(v - r * spr) * U;
+  const TableRow& row = rows[r];
+  const KParams& p = row.p;
+  const KNoise* nz = &nzs[r];
+  constexpr bool DUP = GUIDE == DPM_GUIDE_CFG;
+  KExt ext = {};
+  if constexpr (DUP) ext.xo2 = (void*)row.xo2;
+  const TS* x = (const TS*)row.x;
+  const TE* e0 = (const TE*)row.e0;
+  const TE* e1 = (const TE*)row.e1;
+  const TS* h1 = (const TS*)row.h1;
+  TS* xo = (TS*)row.xo;
+  TS* mo = (TS*)row.mo;
+#define DPM_TABLE_TILES(F_)                                                                                                   \
+  stage_tiles<TS, TE, F_, GUIDE, false, SPEC, U, NT, DUP, false, true, true>(x, nullptr, e0, e1, nullptr, h1, nullptr, xo, mo, \
+                                                                             ngroups, t0, p, ext, nullptr, nz)
+  switch (p.form) {
+    case DPM_FORM_LIN1: DPM_TABLE_TILES(DPM_FORM_LIN1); break;
+    case DPM_FORM_TWO: DPM_TABLE_TILES(DPM_FORM_TWO); break;
+    default: break;  // (the host groups LIN1 / TWO only)
+  }
+#undef DPM_TABLE_TILES
+}
+
 // the most members a table group of n-element requests may have: the launch's super-tiles (and its workgroups, eight
 // XCD spans rounded up) stay below 2^31.  Counted at one tile per super-tile, whatever the pair's U: one rule for every dtype.
 inline int64_t table_group_cap(int64_t n) {
@@ -143,6 +189,48 @@ inline void table_fill_rows(const dpm_stage* st, const dpm_buffers* bs, int n_re
     row.p = make_params(&st[r]);
     std::memcpy(&out[r], &row, sizeof row);
   }
+}
+
+// ---- DPM_TABLE_FILL | DPM_TABLE_NOISE: the noise records of one group of SDE rows, beside its rows (same order).  The seed
+// from the request's own options, counter and scale from its stage (noise_of), the base from dpm_buffers.noise_sample0 --
+// checked by the caller: >= 0, a whole number of Philox blocks.
+inline void table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* recs) {
+  KNoiseTab* out = static_cast<KNoiseTab*>(recs);
+  for (int r = 0; r < n_req; ++r) {
+    KNoiseTab nz;
+    std::memset(&nz, 0, sizeof nz);
+    static_cast<KNoise&>(nz) = noise_of(st[r], bs[r]);
+    nz.g0 = (uint64_t)bs[r].noise_sample0 * (uint64_t)(bs[r].n / bs[r].batch) / 4u;
+    std::memcpy(&out[r], &nz, sizeof nz);
+  }
+}
+
+// ---- DPM_TABLE_LAUNCH | DPM_TABLE_NOISE: ONE launch over a group of SDE rows and their noise records (device memory), the
+// launch shape of launch_table_typed
+template <typename TS, typename TE>
+int launch_table_noise_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs,
+                             const LaunchCtx& c) {
+  if (n_req < 1 || (int64_t)n_req > table_group_cap(bs[0].n))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one table launch", n_req);
+  const Tuning tn = tuning_for(bs[0].opts);
+  bool x0 = !tn.force_generic;
+  for (int r = 0; r < n_req; ++r) {
+    if (!(st[r].flags & DPM_F_NOISE) || (st[r].form != DPM_FORM_LIN1 && st[r].form != DPM_FORM_TWO))
+      return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a stage that is no first- / second-order SDE stage in a table noise launch");
+    x0 = x0 && x0_prologue_ok(st[r]);
+  }
+  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
+  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  const TableRow* tab = static_cast<const TableRow*>(rows);
+  const KNoiseTab* nzs = static_cast<const KNoiseTab*>(recs);
+  const int64_t n = bs[0].n;
+  const uint32_t nreq = (uint32_t)n_req;
+  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
+  with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
+    launch(stage_kernel_table_noise<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, nzs, n, nreq,
+           sh.spr, sh.xcd_span);
+  });
+  return launch_status("table noise stage kernel launch failed");
 }
 
 // ---- DPM_TABLE_LAUNCH: ONE launch over the group's run of rows (device memory: a byte copy of what table_fill_rows wrote for

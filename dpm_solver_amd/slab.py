@@ -32,6 +32,19 @@ evaluates all S rows; compaction of a sparse slab is out of scope.
 
 Admitted: multistep ODE requests (`submit`) and UniPC requests (`submit_unipc`), unconditional or classifier-free (the guidance
 scale stays the wrapper's; conditions may be per request).  Everything else is refused with NotImplementedError: see `submit`.
+
+`request_pool(slots=S, sde=True)` also admits SDE-DPM-Solver++ requests: `submit(x, ..., sde=True, seed=...)`, with
+`RequestPool.submit`'s checks and seed rules.  The tick's two calls then carry DPM_TABLE_NOISE: every SDE row is a row of the
+table whatever their number -- one stage_kernel_table_noise launch beside the ODE / UniPC one -- with a noise record behind
+the rows (the staging is sized for that section).  The noise contract indexes z over the REQUEST's flat [b, C, H, W] tensor
+and a request's samples may sit in any rows, so sample k of a request travels with dpm_buffers.noise_sample0 = k: its row
+starts the generator's counter at k * per_sample / 4 blocks.  Every SDE request keeps a dpm_launch_opts of its own (the
+solver's + its seed) while it is active, and its rows point at it; row 0's options carry the call's flags and its own seed,
+as in a `RequestPool`.  A tick is one network call, one copy and one launch per family present (ODE, UniPC + ODE, SDE).
+An SDE pool refuses, at its first submit, a sample whose element count is not a multiple of 8 (its rows could not take the
+table, and the counter base would have nowhere to go).
+Guarantee: every SDE result is bit-identical to `sample_sde(x, seed=..., ...)` on the request alone, for any b, whichever
+rows it landed in.  A pool built without `sde=True` refuses SDE requests and runs exactly as before.
 """
 import ctypes as C
 
@@ -40,11 +53,12 @@ import torch
 
 from . import _device as DV
 from . import _lib as L
+from . import sde as _sde
 from . import unipc as _unipc
 
 _RING = 4
 _STAGE = np.dtype(L.Stage)
-_BUFS = np.dtype(dict(names=[n for n, _ in L.Buffers._fields_],
+_BUFS = np.dtype(dict(names=[{"_ns0": "noise_sample0"}.get(n, n) for n, _ in L.Buffers._fields_],
                       formats=[{4: np.int32, 8: np.uint64}[getattr(L.Buffers, n).size] for n, _ in L.Buffers._fields_],
                       offsets=[getattr(L.Buffers, n).offset for n, _ in L.Buffers._fields_], itemsize=C.sizeof(L.Buffers)))
 assert _STAGE.itemsize == C.sizeof(L.Stage)
@@ -62,17 +76,22 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed")
 
 
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots):
+    def __init__(self, solver, slots, sde=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
         self._s, self.S = solver, slots
+        self._sde = bool(sde)            # SDE requests admitted: the tick's calls carry DPM_TABLE_NOISE
+        self._ropts = {}                 # handle -> the dpm_launch_opts of an active SDE request (the solver's + its seed)
+        self._optp = np.zeros(slots, dtype=np.uint64)    # per row: its request's options (0: the solver's), the sample of
+        self._ns0 = np.zeros(slots, dtype=np.int32)      # its request it holds, its request's seed (SDE rows)
+        self._seed = np.zeros(slots, dtype=np.uint64)
         self._wait = []                  # FIFO of _Waiting: requests that found too few free rows
         self._rows = {}                  # handle -> (rows, memory format of x_T) of the admitted requests
         self._free = list(range(slots))  # sorted
@@ -105,7 +124,7 @@ class SlabPool:
             raise NotImplementedError("slab pool: method={!r} -- a singlestep or adaptive update evaluates the network on an "
                                       "intermediate state, and a slab row's evaluation state is its state; use "
                                       "request_pool() without slots".format(method))
-        if sde:
+        if sde and not self._sde:
             raise NotImplementedError("slab pool: sde=True -- SDE stages have no table kernel; use request_pool() without slots")
         if s._thresholding:
             raise NotImplementedError("slab pool: correcting_x0_fn='dynamic_thresholding' -- thresholded stages have no table "
@@ -128,6 +147,12 @@ class SlabPool:
         if sd in (torch.float16, torch.bfloat16) and s._state_dtype is None:
             raise NotImplementedError("slab pool: a half-precision slab needs a solver built with an explicit state_dtype -- "
                                       "the reference's type promotion would depend on the first network output")
+        if self._sde and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
+            per = x.numel() // x.shape[0]
+            if per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
+                raise NotImplementedError("slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is "
+                                          "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
+                                          % per)
         DV._require_gpu(x)
         if not torch.is_tensor(x) or x.dim() < 1 or x.numel() == 0:
             raise ValueError("slab pool: x must be a tensor [b, *sample_shape] with at least one element")
@@ -141,23 +166,32 @@ class SlabPool:
 
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
-               condition=None, unconditional_condition=None):
+               condition=None, unconditional_condition=None, seed=None, generator=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
-        adaptive methods, sde=True, a thresholding solver, classifier guidance, correcting_x0_fn / correcting_xt_fn,
+        adaptive methods, sde=True in a pool built without it, a thresholding solver, classifier guidance, correcting_x0_fn / correcting_xt_fn,
         return_intermediate, double states, and a half-precision slab on a solver without an explicit state_dtype.  A request
         that finds fewer than b free rows waits (first in, first out) and is admitted by a later step().  Returns the
-        request's handle."""
+        request's handle.
+        `sde=True` (a pool built with sde=True): an SDE-DPM-Solver++ request -- `sample_sde`'s arguments, checks and seed rules
+        (`seed`, or one draw from `generator` / torch's default CPU generator, made here), as `RequestPool.submit`."""
         s = self._s
+        if not sde and (seed is not None or generator is not None):
+            raise ValueError("slab pool: `seed` / `generator` belong to an SDE request (sde=True)")
         self._refuse(method, sde, return_intermediate)
+        if sde:
+            _sde.check_solver(s, order)
+            seed = _sde.resolve_seed(seed, generator)
+            if torch.is_tensor(x):
+                _sde.check_state(s, x)
         t_0 = 1. / s.noise_schedule.total_N if t_end is None else t_end
         t_T = s.noise_schedule.T if t_start is None else t_start
         assert t_0 > 0 and t_T > 0, "Time range needs to be greater than 0. For discrete-time DPMs, it needs to be in [1 / N, 1], where N is the length of betas array"
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
-                                  solver_type)
-        return self._enqueue(x, plan, condition, unconditional_condition)
+                                  solver_type, sde=bool(sde))
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
@@ -202,7 +236,7 @@ class SlabPool:
             raise ValueError("slab pool: condition and unconditional_condition differ in shape or dtype")
         return cond, uncond
 
-    def _enqueue(self, x, plan, cond, uncond):
+    def _enqueue(self, x, plan, cond, uncond, seed=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
@@ -213,7 +247,7 @@ class SlabPool:
             raise ValueError("slab pool: a condition of shape %s, dtype %s does not match the pool's %s, %s"
                              % (tuple(cond.shape[1:]), cond.dtype, tuple(self._cslab.shape[1:]), self._cslab.dtype))
         q = _Waiting()
-        q.h, q.x, q.plan, q.cond, q.uncond, q.mf = self._next, x, plan, cond, uncond, DV._mf_of(x)
+        q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -239,7 +273,7 @@ class SlabPool:
             self._cslab = torch.zeros((nS,) + tuple(cond.shape[1:]), dtype=cond.dtype, device=dev)
         # staging: per ring slot a pinned buffer [table | next tick's times | this tick's times | stage array | buffers array]
         # and a device buffer for its first two parts (and one for the third: the copy an admitting tick adds)
-        self._tabb = (L.TABLE_HEADER_BYTES + S * L.TABLE_ROW_BYTES + 15) // 16 * 16
+        self._tabb = (L.TABLE_HEADER_BYTES + S * (L.TABLE_ROW_BYTES + (L.TABLE_NOISE_BYTES if self._sde else 0)) + 15) // 16 * 16
         self._copyb = self._tabb + 4 * nS
         o_cur = (self._copyb + 15) // 16 * 16
         o_st = (o_cur + 4 * nS + 15) // 16 * 16
@@ -288,6 +322,10 @@ class SlabPool:
                 k += cnt
             ra = np.asarray(rows, dtype=np.int64)
             self._off[ra], self._pos[ra], self._len[ra], self._req[ra] = self._plan_offset(q.plan), 0, len(q.plan.stages), q.h
+            self._optp[ra], self._ns0[ra], self._seed[ra] = 0, 0, 0
+            if q.seed is not None:       # sample k of the request sits in rows[k]: its z starts at element k * per_sample
+                o = self._ropts[q.h] = _sde.request_opts(q.seed, self._s._opts_ptr())
+                self._optp[ra], self._ns0[ra], self._seed[ra] = C.addressof(o), np.arange(b, dtype=np.int32), np.uint64(q.seed)
             self._rows[q.h] = (rows, q.mf)
 
     def _network(self, x, t):
@@ -376,7 +414,14 @@ class SlabPool:
                 b["opts"] = C.addressof(o.contents)
             self._opts.per_request_stages, self._opts.fuse_shapes = 1, 0
             self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
+            if self._sde:
+                own = self._optp[rows]
+                b["opts"] = np.where(own != 0, own, b["opts"])
+                b["noise_sample0"] = np.where((rec["flags"] & L.F_NOISE) != 0, self._ns0[rows], 0)
+                seed0 = int(self._seed[rows[0]]) if own[0] else 0      # row 0's options are the call's: they carry its seed
+                self._opts.noise_seed_lo, self._opts.noise_seed_hi = seed0 & 0xffffffff, seed0 >> 32
             b["opts"][0] = C.addressof(self._opts)
+            flag = L.TABLE_NOISE if self._sde else 0
             # next tick's time vector rides with this tick's table
             go = ~last
             t_next = self._times_of(rows[go], idx[go] + 1)
@@ -386,13 +431,13 @@ class SlabPool:
             pin, dev = self._pin[j], self._dev[j]
 
             def tick():
-                self._opts.table_mode = L.TABLE_FILL
+                self._opts.table_mode = L.TABLE_FILL | flag
                 b["workspace"][0] = pin.data_ptr()
                 rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
                 if rc == 0:
                     self._ev[j] = DV._copy_to_device(dev, pin[:self._copyb])
                     self.copies += 1
-                    self._opts.table_mode = L.TABLE_LAUNCH
+                    self._opts.table_mode = L.TABLE_LAUNCH | flag
                     b["workspace"][0] = dev.data_ptr()
                     rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
                 self._opts.table_mode = 0
@@ -411,6 +456,7 @@ class SlabPool:
             # finished requests: their rows, cloned from the output slab, are free again
             for h in np.unique(self._req[rows[last]]).tolist():
                 rws, mf = self._rows.pop(h)
+                self._ropts.pop(h, None)
                 parts = [xout[r0:r0 + cnt] for r0, cnt in _runs(rws)]
                 out = parts[0].clone() if len(parts) == 1 else torch.cat(parts)
                 done[h] = out if mf is None else DV._conv(out, out.dtype, mf)

@@ -701,7 +701,7 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False, slots=None):
+    def request_pool(self, mixed_shapes=False, slots=None, sde=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -709,12 +709,16 @@ class DPM_Solver:
         size, images per prompt) and still share the tick's launch.
         `slots=S`: a `SlabPool` (dpm_solver_amd/slab.py) for MANY SMALL requests -- S rows of one sample each in slabs the
         pool owns; a tick is one network call on the whole slab, one host-to-device copy and one table-driven stage launch
-        (dpm_launch_opts.table_mode), and every request may bring its own condition."""
+        (dpm_launch_opts.table_mode), and every request may bring its own condition.  `slots=S, sde=True`: the slab pool
+        also admits SDE-DPM-Solver++ requests (`submit(x, ..., sde=True, seed=...)`), their stages in the table-driven launch
+        too (DPM_TABLE_NOISE)."""
+        if sde and slots is None:
+            raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
         if slots is not None:
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots)
+            return _slab.SlabPool(self, slots, sde=sde)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -69,11 +69,15 @@ extern "C" {
    dpm_stage_launch_multi with per-request stages launches a group of MORE than 16 requests as ONE kernel whose per-request
    records are rows of a table in device memory (hundreds of single-image requests per tick; see "Table mode" at
    dpm_stage_launch_multi; no entry point added, no struct changed size).
+   209 DPM_TABLE_NOISE (a flag on table_mode), dpm_buffers.noise_sample0 (was `reserved`), DPM_TABLE_NOISE_BYTES /
+   DPM_SIZEOF_TABLE_NOISE: SDE stages in the table -- every fusable DPM_F_NOISE request owns a row and a noise record behind
+   the rows, and a row may be ONE SAMPLE of a request whose noise the contract indexes over all of its samples (see "Table
+   mode"; no entry point added, no struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 208
+#define DPM_HIP_VERSION 209
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -239,7 +243,10 @@ typedef struct dpm_launch_opts {
                                mode" at dpm_stage_launch_multi                                                            */
 } dpm_launch_opts;
 enum { DPM_TABLE_FILL = 1, DPM_TABLE_LAUNCH = 2 };
+enum { DPM_TABLE_NOISE = 4 }; /* version 209: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH (table_mode 5 / 6): SDE stages
+                                 take rows too, each with a noise record behind the rows */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
+#define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -272,7 +279,11 @@ typedef struct dpm_buffers {
                           written, the streams come from HBM -> streaming loads.  1: the immediately preceding launch
                           wrote them (frozen-model loops; dpm_plan_run sets it when there is no model callback) ->
                           default cache policy, they are expected in the 256 MiB Infinity Cache                  */
-  int32_t reserved;
+  int32_t noise_sample0; /* version 209 (was `reserved`).  The buffers are samples [noise_sample0, noise_sample0 + batch) of the
+                          tensor the noise contract indexes: element i of the buffers takes the z of element
+                          noise_sample0 * (n / batch) + i.  Honoured by the rows of a DPM_TABLE_NOISE call's SDE stages only;
+                          non-zero anywhere else -- table_mode 0 / 1 / 2, a stage without DPM_F_NOISE, a request that fits no
+                          fused group --, negative, or with noise_sample0 * (n / batch) not a multiple of 4: DPM_ERR_ARG */
   float* thr_hint;     /* DPM_F_THRESH, optional (NULL = off): DPM_THR_HINT_WORDS floats per sample that persist from stage
                           to stage of ONE trajectory -- the kernel's private state (content undefined to the caller; no
                           initialisation needed: the stage with index 0 resets it).  [0], [1]: the selected order statistic
@@ -424,7 +435,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    theirs).  Two calls with the SAME st / bs arrays make a tick:
      DPM_TABLE_FILL    bs[0].workspace is HOST memory.  Checks every request as mode 0 does (same error texts, nothing written
                        when one fails), groups them by the rules above without the cap of 16, and writes
-                         header  4 x uint32: DPM_TABLE_MAGIC, 208, n_req, the number of groups with rows
+                         header  4 x uint32: DPM_TABLE_MAGIC, dpm_version(), n_req, the number of groups with rows
                          rows    from byte dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) on, dpm_sizeof(DPM_SIZEOF_TABLE_ROW) bytes
                                  each: for every group of more than 16 members a run of consecutive rows, members in call
                                  order, the runs in the order their groups open.  A row is 8 pointers -- x, e0, e1, h1, h2,
@@ -438,9 +449,24 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        function: the same row order); a group with rows is ONE launch over its run of rows, every other
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
-   SDE stages, mixed n (fuse_shapes), thresholding, mask blend, classifier guidance and DPM_F_STORE_XC are outside the table
-   kernels: in a table call such requests take exactly the path they take in mode 0.  Every request gets the bits of its own
-   dpm_stage_launch.  Any other table_mode, a non-zero one without per_request_stages, or with fuse_shapes == 1: DPM_ERR_ARG. */
+   SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding, mask blend, classifier guidance and
+   DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   Every request gets the bits of its own dpm_stage_launch.
+   SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
+   same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
+   LIN1 / TWO -- then owns a row, whatever the size of its group, down to a group of one; the groups are those of mode 0
+   without the cap of 16, one run of rows and one launch each.  ODE and UniPC groups keep the rules above (rows from 17
+   members).  Behind the rows the table holds one noise record per row: the record of table row i (counted over all runs) is
+   the DPM_TABLE_NOISE_BYTES bytes at dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * dpm_sizeof(DPM_SIZEOF_TABLE_ROW) +
+   DPM_TABLE_NOISE_BYTES * i, n_req the call's; the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req *
+   (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + DPM_TABLE_NOISE_BYTES) bytes.  A record is 8 x uint32: seed lo, seed hi (the request's
+   own bs[r].opts, NULL: 0), st[r].index, the bits of st[r].c2, g0 lo, g0 hi, 0, 0.  g0 = bs[r].noise_sample0 * (n / batch) / 4
+   is added to the index of every Philox block of the row (64-bit), so the row's element i takes the z of element
+   noise_sample0 * (n / batch) + i of the noise contract: with noise_sample0 = k, a row that holds sample k of a larger
+   request gets the bits that sample has in the request's own launch; 0 gives the bits of the row's own dpm_stage_launch.
+   FILL writes the records of SDE rows only and leaves every other byte of the record section untouched.  Without the flag
+   (table_mode 1 / 2) SDE requests take their mode-0 path and write no rows, as in version 208.
+   Any other table_mode, a non-zero one without per_request_stages, or with fuse_shapes == 1: DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
@@ -578,7 +604,8 @@ DPM_API int dpm_version(void);
 /* sizeof() of the ABI structs as compiled, so a binding can verify its own layout at load time */
 enum { DPM_SIZEOF_STAGE = 0, DPM_SIZEOF_BUFFERS = 1, DPM_SIZEOF_PLAN_DESC = 2, DPM_SIZEOF_RUN_BUFFERS = 3,
        DPM_SIZEOF_ADAPTIVE_DESC = 4, DPM_SIZEOF_LAUNCH_OPTS = 5, DPM_SIZEOF_STAGE_F64 = 6,
-       DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */ };
+       DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */,
+       DPM_SIZEOF_TABLE_NOISE = 10 /* version 209: a noise record of a DPM_TABLE_NOISE table (9 is unassigned: 0) */ };
 DPM_API size_t dpm_sizeof(int which);
 DPM_API const char* dpm_last_error(void); /* thread-local text of the last non-zero return */
 DPM_API int dpm_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len);
