@@ -12,6 +12,8 @@ from . import _lib as L
 from .launch_list import _bind_outputs
 
 _F32 = np.float32
+_NAN_ESTIMATE = ("adaptive solver: the error estimate is NaN at t = %r (the state or the network output "
+                 "is not finite); the reference's loop would not terminate here")
 
 class _AdaptiveHandle:
     """a dpm_adaptive handle (device-resident controller state + schedule tables); created outside stream capture"""
@@ -101,7 +103,11 @@ def adaptive_device(self, x, order, t_T, t_0, h_init, atol, rtol, theta, t_err, 
     the decisions up to iteration i - 1 - lookahead and reads the host-mapped `done` word.  Iterations enqueued after
     the device reached t_0 are no-ops in the solver kernels (the network calls in them are the price of the
     look-ahead: at most `lookahead` iterations).  Under stream capture exactly `adaptive_max_iterations` are
-    recorded."""
+    recorded.
+    A NaN error estimate ends the run on the device (done == 2, include/dpm_hip.h): the step is rejected, the time
+    vectors keep their last finite values and the iterations already enqueued are no-ops; the host raises the host
+    loop's FloatingPointError at the run's end.  Under capture nothing can be raised: the recorded iterations after the
+    NaN are no-ops and the replay returns the last accepted state."""
     device = x.device
     sd = self._sdtype(x)
     mt, gd, sc = self._model_codes()
@@ -186,6 +192,8 @@ def adaptive_device(self, x, order, t_T, t_0, h_init, atol, rtol, theta, t_err, 
             torch.cuda.current_stream(device).synchronize()  # the one wait of the run: its end
             nfe = C.c_int(0)
             L.lib.dpm_adaptive_poll(h, C.byref(done), C.byref(nfe), None, None)
+            if done.value == 2:      # the time vectors keep their last finite values: tv[0, 0] is s of the failed iteration
+                raise FloatingPointError(_NAN_ESTIMATE % float(tv[0, 0, 0]))
             if not done.value:
                 raise RuntimeError("adaptive solver: t_end not reached within %d iterations" % max_it)
             print('adaptive solver nfe', nfe.value)
@@ -259,8 +267,7 @@ def solve(self, x, order, t_T, t_0, h_init=0.05, atol=0.0078, rtol=0.05, theta=0
         E = FT(E_dev.item())                     # the one host sync per iteration, as in the reference (ref :1002)
         if E != E:
             # a NaN estimate is never accepted and turns h into NaN: the reference's loop then spins forever (ref :1002-1008)
-            raise FloatingPointError("adaptive solver: the error estimate is NaN at t = %r (the state or the network output "
-                                     "is not finite); the reference's loop would not terminate here" % float(s))
+            raise FloatingPointError(_NAN_ESTIMATE % float(s))
         if E <= 1.:
             x = x_higher
             s = t

@@ -618,8 +618,13 @@ __global__ __launch_bounds__(256) void adaptive_begin_kernel(AdaptiveDev* S, dpm
   __shared__ int live;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (threadIdx.x == 0) {
-    if (S->iters > 0 && !S->done) {
-      const float E = *e_dev;
+    const float E = *e_dev;
+    if (S->iters > 0 && !S->done && E != E) {
+      // a NaN estimate is never accepted and would turn h, t and the time vectors into NaN without ever ending the run
+      // (ref :1002-1008 spins): reject and end the run with the verdict 2; s, h, nfe and the time vectors keep their values
+      S->accept = 0;
+      S->done = 2;
+    } else if (S->iters > 0 && !S->done) {
       const int acc = E <= 1.f;  // ref :1002
       if (acc) {
         S->s = S->t;

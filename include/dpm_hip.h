@@ -545,7 +545,10 @@ DPM_API int dpm_adaptive_stage_launch(dpm_adaptive* a, int which, const dpm_stag
 /* *e_dev <- max(*e_dev, max_b E_b) (ref :999-1001); several workgroups per sample, fp32 / fp16 / bf16 */
 DPM_API int dpm_adaptive_error(dpm_adaptive* a, const void* x_lower, const void* x_higher, const void* x_prev, int64_t batch,
                        int64_t per_sample, int dtype, float* e_dev, void* stream);
-/* host-mapped status as of the last dpm_adaptive_begin the device has executed: no synchronisation */
+/* host-mapped status as of the last dpm_adaptive_begin the device has executed: no synchronisation.
+   done: 0 running, 1 t_end reached, 2 the run was ended by a NaN error estimate -- the begin that read it rejected the
+   step, left s, h, nfe and the time vectors at their last (finite) values, and every later kernel of the handle is a
+   no-op as after 1.  dpm_adaptive_done_at reports the same three values. */
 DPM_API int dpm_adaptive_poll(const dpm_adaptive* a, int* done, int* nfe, int* iterations, int* accepted);
 /* `done` as recorded by the begin_index-th dpm_adaptive_begin since the last reset (a ring of the last 32): the value to
    look at after waiting for THAT launch -- identical on every rank of a batch-sharded run, whatever has run since */

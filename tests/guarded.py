@@ -71,6 +71,22 @@ class Arena:
         """the payload as a CPU tensor of the arena's dtype"""
         return self.payload_bits().cpu().view(self.dtype) if self.dtype.is_floating_point else self.payload_bits().cpu()
 
+    def verify(self, what, want_bits=None):
+        """an arena outside a GuardedLaunch: both guards as they were, and the payload -- bit for bit -- `want_bits`
+        (None: as it was at construction, i.e. nothing wrote it)"""
+        now, end = self.raw.cpu(), self.lead + self.extent
+        for lo, hi in ((0, self.lead), (end, now.numel())):
+            d = now[lo:hi] != self.before[lo:hi]
+            if bool(d.any()):
+                raise GuardError("%s offset=%d: guard element overwritten" % (what, lo + _first(d) - self.lead))
+        want = self.before[self.lead:end] if want_bits is None else want_bits.cpu().reshape(-1)
+        d = now[self.lead:end] != want
+        if bool(d.any()):
+            i = _first(d)
+            raise GuardError("%s offset=%d: payload holds bits %#x, want %#x%s" % (
+                what, i, int(now[self.lead + i]) & (2 ** (8 * self.es) - 1), int(want[i]) & (2 ** (8 * self.es) - 1),
+                " (nothing may write it)" if want_bits is None else ""))
+
 
 def _first(mask):
     return int(torch.nonzero(mask.reshape(-1))[0])
@@ -157,16 +173,17 @@ class GuardedLaunch:
         raise GuardError("family=%s pair=%s/%s n=%d request=%d buffer=%s offset=%d: %s" % (
             self.family, _name(self.sd), _name(self.ed), self.n, self.req, buffer, off, what))
 
-    def verify(self, want=None, rc=0):
-        """the checks of the module docstring; `want`: the GuardedLaunch the double ran on (None: structure only)"""
+    def verify(self, want=None, rc=0, noop=False):
+        """the checks of the module docstring; `want`: the GuardedLaunch the double ran on (None: structure only); `noop`: the
+        launch had to leave every arena alone although it returned 0 (a launch of a finished adaptive run)"""
         now = {k: a.raw.cpu() for k, a in self.arenas.items()}
         for k, a in self.arenas.items():                                          # 2 (and 6: outputs after an error)
-            if k in INPUTS or rc != 0:
+            if k in INPUTS or rc != 0 or noop:
                 d = now[k] != a.before
                 if bool(d.any()):
                     self._fail(k, _first(d) - a.lead, "changed by a launch that %s" % (
-                        "returned the error code %d" % rc if rc != 0 else "may only read it"))
-        if rc != 0:
+                        "returned the error code %d" % rc if rc != 0 else "had to be a no-op" if noop else "may only read it"))
+        if rc != 0 or noop:
             return
         for k in OUTPUTS + ("workspace",):
             a, v = self.arenas[k], now[k]
