@@ -55,6 +55,10 @@ int dpm_table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, 
 // DPM_TABLE_LAUNCH | DPM_TABLE_NOISE: one launch over the group's rows and records in DEVICE memory
 template <typename TS, typename TE>
 int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream);
+// DPM_TABLE_LAUNCH | DPM_TABLE_THRESH: one launch over a group's thresholded rows in DEVICE memory (filled by dpm_table_fill:
+// a thresholded row is a row like any other), one workgroup per sample
+template <typename TS, typename TE>
+int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -37,6 +37,7 @@ using TableFillFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 using TableFillNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 using TableLaunchNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+using TableLaunchThreshFn = TableLaunchFn;
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
@@ -47,11 +48,12 @@ struct PairUnits {
   TableLaunchFn table_launch;  // ... and the one launch over them
   TableFillNoiseFn table_fill_noise;      // (DPM_TABLE_NOISE) rows and noise records of a group of SDE stages
   TableLaunchNoiseFn table_launch_noise;  // ... and the one launch over them
+  TableLaunchThreshFn table_launch_thresh;  // (DPM_TABLE_THRESH) the one launch over a group of thresholded rows (table_fill's)
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>,      \
-   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>},
+   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -266,6 +268,12 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
   return DPM_OK;
 }
 
+// does request r own a row of stage_thresh_kernel_table in a DPM_TABLE_THRESH call?  (thresh_row_ok, dpm_table_thresh.hpp)
+bool thresh_row(const dpm_stage* st, const dpm_buffers* bs, int r) {
+  return bs[r].batch >= 1 && bs[r].n > 0 && bs[r].n % bs[r].batch == 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) &&
+         thresh_row_ok(st[r], bs[r]);
+}
+
 // table_mode (DPM_TABLE_FILL / DPM_TABLE_LAUNCH; `table` = bs[0].workspace, checked by the caller): the same walk without
 // the cap of HET_MAX -- a group is bounded by its launch's 2^31 super-tiles only.  A group of TABLE_MIN members or more owns
 // a run of consecutive table rows, members in call order, the runs in the order the groups open: FILL writes them (host
@@ -274,9 +282,15 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
 // their row order is the same.
 // With DPM_TABLE_NOISE on the mode, SDE groups own rows too, from ONE member on -- a row's noise_sample0 has no other way to
 // the kernel -- and a noise record each behind the n_req rows the table has room for, record i beside row i.
+// With DPM_TABLE_THRESH on the mode, thresholded requests that pass thresh_row_ok own rows too, from ONE member on (a lone
+// launch of a small batch is a cluster with a workspace; a row is one workgroup per sample): a group of them agrees on
+// het_same_group's keys and on the bit patterns of thr_ratio / thr_max, takes any of LIN1 / TWO / MS3 / DENOISE and is
+// one stage_thresh_kernel_table launch.  fusable_request refuses DPM_F_THRESH, so such a request never joins another group;
+// one that does not qualify goes as in mode 0.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
   const bool noise_rows = (table_mode & DPM_TABLE_NOISE) != 0;
-  table_mode &= ~DPM_TABLE_NOISE;
+  const bool thresh_rows = (table_mode & DPM_TABLE_THRESH) != 0;
+  table_mode &= ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH);
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
@@ -300,33 +314,45 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
   for (int r0 = 0; r0 < n_req; ++r0) {
     if (done[r0]) continue;
     int cnt = 0, third = 0;
-    if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
+    auto join = [&](int r) {
+      if ((size_t)cnt == gs.size()) {
+        gs.resize(2 * gs.size());
+        gb.resize(gs.size());
+        gi.resize(gs.size());
+      }
+      gs[cnt] = st[r];
+      gb[cnt] = bs[r];
+      gi[cnt++] = r;
+    };
+    const bool thr = thresh_rows && fuse && thresh_row(st, bs, r0);
+    if (thr) {
+      const int64_t cap = std::min<int64_t>(table_group_cap(bs[r0].n), 0x7fffffff / bs[r0].batch);
+      for (int r = r0; r < n_req && cnt < cap; ++r)
+        if (!done[r] && thresh_row(st, bs, r) && het_same_group(st[r0], bs[r0], st[r], bs[r], false) &&
+            thresh_same_group(st[r0], st[r]))
+          join(r);
+    } else if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
       const int64_t cap = table_mode ? table_group_cap(bs[r0].n) : HET_MAX;
       for (int r = r0; r < n_req && cnt < cap; ++r)
         if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r], shapes)) {
           const int f = het_third_form(st[r]);
           if (f && third && f != third) continue;
           if (f) third = f;
-          if ((size_t)cnt == gs.size()) {
-            gs.resize(2 * gs.size());
-            gb.resize(gs.size());
-            gi.resize(gs.size());
-          }
-          gs[cnt] = st[r];
-          gb[cnt] = bs[r];
-          gi[cnt++] = r;
+          join(r);
         }
     }
     // SDE groups take the table with DPM_TABLE_NOISE only (stage_kernel_table_noise, from one member on); without the flag
     // they go as in mode 0, beyond HET_MAX members in launches of HET_MAX
     const bool sde = (st[r0].flags & DPM_F_NOISE) != 0;
-    const bool tabled = table_mode && (sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
+    const bool tabled = table_mode && (thr ? cnt >= 1 : sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
     if (tabled) {
       const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
       void* run = rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
       void* nzs = recs + n_rows * (int64_t)DPM_TABLE_NOISE_BYTES;
       int rc;
-      if (sde)
+      if (thr)
+        rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch_thresh(gs.data(), gb.data(), cnt, run, stream);
+      else if (sde)
         rc = fill ? p.table_fill_noise(gs.data(), gb.data(), cnt, run, nzs)
                   : p.table_launch_noise(gs.data(), gb.data(), cnt, run, nzs, stream);
       else
@@ -367,17 +393,19 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  const int mode = o->table_mode & ~DPM_TABLE_NOISE;
+  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
-                         "without DPM_TABLE_NOISE)", o->table_mode);
+                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH)", o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");
   if (o->fuse_shapes == 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with fuse_shapes (the table kernels take one n per launch)");
   if (!bs[0].workspace || reinterpret_cast<uintptr_t>(bs[0].workspace) % 16 != 0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs the table in bs[0].workspace, 16-byte aligned");
-  if (st[0].flags & DPM_F_THRESH)
+  // (a thresholded request 0 that owns a row of a DPM_TABLE_THRESH call needs no workspace of its own)
+  const bool row0 = (o->table_mode & DPM_TABLE_THRESH) && tuning_for(o).multi_fuse != 0 && thresh_row(st, bs, 0);
+  if ((st[0].flags & DPM_F_THRESH) && !row0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with DPM_F_THRESH in st[0] (bs[0].workspace is the table)");
   return DPM_OK;
 }

@@ -5,7 +5,7 @@
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
 //               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
 //   unit C (2): the table-driven heterogeneous launchers (stage_kernel_table, stage_kernel_table_unipc,
-//               stage_kernel_table_noise) and nothing else -- a unit of its own, so that units A and B compile to the code they compiled to before it existed
+//               stage_kernel_table_noise, stage_thresh_kernel_table) and nothing else -- a unit of its own, so that units A and B compile to the code they compiled to before it existed
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2>"
 #endif
@@ -98,4 +98,11 @@ int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req
   return launch_table_noise_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
 template int dpm_table_launch_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+
+template <typename TS, typename TE>
+int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_thresh_typed<TS, TE>(st, bs, n_req, rows, s);
+}
+template int dpm_table_launch_thresh<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 #endif

@@ -113,9 +113,10 @@ struct ThrLaunchPlan {
 
 // The plan of one thresholded launch of `batch` samples of `per_sample` elements: cluster shape, quantile rank, select
 // route (top-K front end, single-exchange quota and slot geometry), workspace stride.  `vec`: 4-element accesses are
-// legal for every tensor; `fastdiv`: x0_prologue_ok of the stage.
+// legal for every tensor; `fastdiv`: x0_prologue_ok of the stage.  `one_wg`: the caller's kernel has no clusters (the table
+// rows of DPM_TABLE_THRESH) -- one workgroup per sample whatever the batch; per_sample beyond THR_CHUNK_MAX is out of range.
 inline ThrLaunchPlan thr_launch_plan(const dpm_stage& st, int64_t batch, int64_t per_sample, int n_cu, ThrKnobs tn,
-                                     bool capturing, bool vec, bool fastdiv) {
+                                     bool capturing, bool vec, bool fastdiv, bool one_wg = false) {
   ThrLaunchPlan lp;
   std::memset(&lp, 0, sizeof lp);
   if (batch > 0x7fffffff || per_sample > ((int64_t)1 << 40)) {
@@ -128,9 +129,13 @@ inline ThrLaunchPlan thr_launch_plan(const dpm_stage& st, int64_t batch, int64_t
   // replayed outside that chain, possibly next to another graph on another stream.  Under capture a sample that fits
   // one workgroup's LDS therefore takes the cluster-free shape (one workgroup per sample) unless the caller opts in
   // (dpm_launch_opts.cluster_in_graph); larger samples have no such shape and keep their clusters, with bounded waits.
-  if (capturing && pl.k > 1 && per_sample <= THR_CHUNK_MAX && !tn.cluster_in_graph) {
+  if (((capturing && !tn.cluster_in_graph) || one_wg) && pl.k > 1 && per_sample <= THR_CHUNK_MAX) {
     pl.k = 1;
     pl.chunk = (per_sample + 3) / 4 * 4;
+  }
+  if (one_wg && pl.k > 1) {
+    lp.err = 1;
+    return lp;
   }
   ThrParams& tp = lp.tp;
   tp.per_sample = per_sample;

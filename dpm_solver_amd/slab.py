@@ -45,6 +45,18 @@ An SDE pool refuses, at its first submit, a sample whose element count is not a 
 table, and the counter base would have nowhere to go).
 Guarantee: every SDE result is bit-identical to `sample_sde(x, seed=..., ...)` on the request alone, for any b, whichever
 rows it landed in.  A pool built without `sde=True` refuses SDE requests and runs exactly as before.
+
+`request_pool(slots=S, thresholding=True)` is the slab pool of a solver built with correcting_x0_fn="dynamic_thresholding"
+(pixel-space models: many requests of one or a few 64x64 images).  A row is one sample, and a sample of at most 12288 elements
+-- [3,64,64] exactly -- fits the LDS of one workgroup: the tick's two calls carry DPM_TABLE_THRESH, every thresholded row is a
+row of the table whatever their number -- ONE stage_thresh_kernel_table launch, one workgroup per row, no cluster, no
+workspace -- and a tick stays one network call, one copy and one launch.  Admitted: multistep ODE requests (`submit`),
+unconditional or classifier-free, with per-request conditions; UniPC and SDE requests are refused by their own checks of a
+thresholding solver.  At its first submit such a pool refuses a sample of more than 12288 elements, one whose element count
+is no multiple of 8, and one whose row is no multiple of 16 bytes (the row could not take the table, and its lone launch
+would need a workspace the pool does not hold).
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, for any b, whichever rows it landed in.
+Without `thresholding=True` a slab pool refuses a thresholding solver as before.
 """
 import ctypes as C
 
@@ -82,12 +94,13 @@ class _Waiting:
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots, sde=False):
+    def __init__(self, solver, slots, sde=False, thresholding=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
         self._s, self.S = solver, slots
         self._sde = bool(sde)            # SDE requests admitted: the tick's calls carry DPM_TABLE_NOISE
+        self._thr = bool(thresholding)   # a thresholding solver's pool: the tick's calls carry DPM_TABLE_THRESH
         self._ropts = {}                 # handle -> the dpm_launch_opts of an active SDE request (the solver's + its seed)
         self._optp = np.zeros(slots, dtype=np.uint64)    # per row: its request's options (0: the solver's), the sample of
         self._ns0 = np.zeros(slots, dtype=np.int32)      # its request it holds, its request's seed (SDE rows)
@@ -126,7 +139,7 @@ class SlabPool:
                                       "request_pool() without slots".format(method))
         if sde and not self._sde:
             raise NotImplementedError("slab pool: sde=True -- SDE stages have no table kernel; use request_pool() without slots")
-        if s._thresholding:
+        if s._thresholding and not self._thr:
             raise NotImplementedError("slab pool: correcting_x0_fn='dynamic_thresholding' -- thresholded stages have no table "
                                       "kernel; use request_pool() without slots")
         if s._wrapped is not None and s._wrapped.effective_guidance == "classifier":
@@ -153,6 +166,12 @@ class SlabPool:
                 raise NotImplementedError("slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is "
                                           "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
                                           % per)
+        if self._thr and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
+            per = x.numel() // x.shape[0]
+            if per > L.THR_ROW_MAX or per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
+                raise NotImplementedError("slab pool: thresholding=True with a sample of %d elements -- a thresholded row of the "
+                                          "table is at most %d elements (one workgroup's LDS), whole 8-element groups of "
+                                          "16-byte aligned buffers; use request_pool() without slots" % (per, L.THR_ROW_MAX))
         DV._require_gpu(x)
         if not torch.is_tensor(x) or x.dim() < 1 or x.numel() == 0:
             raise ValueError("slab pool: x must be a tensor [b, *sample_shape] with at least one element")
@@ -170,7 +189,7 @@ class SlabPool:
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
-        adaptive methods, sde=True in a pool built without it, a thresholding solver, classifier guidance, correcting_x0_fn / correcting_xt_fn,
+        adaptive methods, sde=True in a pool built without it, a thresholding solver in a pool built without thresholding=True, classifier guidance, correcting_x0_fn / correcting_xt_fn,
         return_intermediate, double states, and a half-precision slab on a solver without an explicit state_dtype.  A request
         that finds fewer than b free rows waits (first in, first out) and is admitted by a later step().  Returns the
         request's handle.
@@ -421,7 +440,7 @@ class SlabPool:
                 seed0 = int(self._seed[rows[0]]) if own[0] else 0      # row 0's options are the call's: they carry its seed
                 self._opts.noise_seed_lo, self._opts.noise_seed_hi = seed0 & 0xffffffff, seed0 >> 32
             b["opts"][0] = C.addressof(self._opts)
-            flag = L.TABLE_NOISE if self._sde else 0
+            flag = (L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
             # next tick's time vector rides with this tick's table
             go = ~last
             t_next = self._times_of(rows[go], idx[go] + 1)

@@ -701,7 +701,7 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False, slots=None, sde=False):
+    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -711,14 +711,22 @@ class DPM_Solver:
         pool owns; a tick is one network call on the whole slab, one host-to-device copy and one table-driven stage launch
         (dpm_launch_opts.table_mode), and every request may bring its own condition.  `slots=S, sde=True`: the slab pool
         also admits SDE-DPM-Solver++ requests (`submit(x, ..., sde=True, seed=...)`), their stages in the table-driven launch
-        too (DPM_TABLE_NOISE)."""
+        too (DPM_TABLE_NOISE).  `slots=S, thresholding=True`: the slab pool of a solver built with
+        correcting_x0_fn="dynamic_thresholding" -- samples of at most 12288 elements, their thresholded stages in the
+        table-driven launch too (DPM_TABLE_THRESH); without the flag a slab pool refuses such a solver."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
+        if thresholding and slots is None:
+            raise ValueError("request_pool: thresholding=True belongs to a slab pool (slots=...); a RequestPool takes a "
+                             "thresholding solver as it is")
+        if thresholding and not self._thresholding:
+            raise ValueError("request_pool: thresholding=True on a solver built without "
+                             "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots, sde=sde)
+            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

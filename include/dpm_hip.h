@@ -73,11 +73,14 @@ extern "C" {
    DPM_SIZEOF_TABLE_NOISE: SDE stages in the table -- every fusable DPM_F_NOISE request owns a row and a noise record behind
    the rows, and a row may be ONE SAMPLE of a request whose noise the contract indexes over all of its samples (see "Table
    mode"; no entry point added, no struct changed size).
+   210 DPM_TABLE_THRESH (a flag on table_mode): thresholded stages in the table -- every DPM_F_THRESH request whose sample fits
+   one workgroup's LDS owns a row, a group of them is ONE cluster-free launch without a workspace (see "Table mode"; no entry
+   point added, no struct changed, rows and records as in version 209).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 209
+#define DPM_HIP_VERSION 210
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -245,6 +248,8 @@ typedef struct dpm_launch_opts {
 enum { DPM_TABLE_FILL = 1, DPM_TABLE_LAUNCH = 2 };
 enum { DPM_TABLE_NOISE = 4 }; /* version 209: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH (table_mode 5 / 6): SDE stages
                                  take rows too, each with a noise record behind the rows */
+enum { DPM_TABLE_THRESH = 8 }; /* version 210: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without DPM_TABLE_NOISE
+                                  (table_mode 9 / 10 / 13 / 14): thresholded stages of small samples take rows too */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 
@@ -449,8 +454,8 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        function: the same row order); a group with rows is ONE launch over its run of rows, every other
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
-   SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding, mask blend, classifier guidance and
-   DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend, classifier
+   guidance and DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -466,7 +471,27 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    request gets the bits that sample has in the request's own launch; 0 gives the bits of the row's own dpm_stage_launch.
    FILL writes the records of SDE rows only and leaves every other byte of the record section untouched.  Without the flag
    (table_mode 1 / 2) SDE requests take their mode-0 path and write no rows, as in version 208.
-   Any other table_mode, a non-zero one without per_request_stages, or with fuse_shapes == 1: DPM_ERR_ARG. */
+   Thresholded rows (version 210): DPM_TABLE_THRESH OR-ed onto either mode, alone or with DPM_TABLE_NOISE (table_mode 9 / 10,
+   13 / 14), makes the same tick with thresholded stages in the table (stage_thresh_kernel_table: one workgroup of 512 threads
+   per sample, the sample's x0 in its LDS, no cluster, no workspace, no wait on another workgroup).  A DPM_F_THRESH request
+   owns a row when it passes every rule of the fused groups above apart from the DPM_F_THRESH bit -- form LIN1 / TWO / MS3, or
+   DPM_FORM_DENOISE (the thresholded last stage of denoise_to_zero, its buffers checked as LIN1's), guidance none or CFG,
+   evaluation state = state, dense buffers of whole 8-element groups, 16-byte aligned, x_out2 only under CFG, a 2- or 4-byte
+   dtype pair --, has neither DPM_F_BLEND nor DPM_F_NOISE, and its SAMPLE, n / batch elements, is a multiple of 4 and
+   at most 12288 (the kernel works per sample, in 4-element accesses, and a sample has to fit one workgroup's LDS; n being a
+   multiple of 8 is not enough: 4 samples of 10 elements own no row).  Such requests form groups of their own -- never with an un-thresholded request -- that agree on
+   dtypes, n, batch, model type, guidance kind, DPM_F_TO_X0 and on the bit patterns of thr_ratio and thr_max; the forms
+   share a group.  Every group, from ONE member on, is one run of rows and ONE launch (below 2^31 samples), the runs in the
+   order the groups open, among those of the other families.  A thresholded row is a row like any other -- the 8 pointers and
+   the 20 words of stage scalars, which already say which prologue the stage takes; rows of other requests, the row size and
+   the record section are byte for byte those of version 209, and there is no further section (dpm_sizeof(11), like
+   dpm_sizeof(9), is 0).  Such a request reads no dpm_buffers.workspace and no thr_hint, so st[0] may be one: bs[0].workspace
+   is the table.  A thresholded request that does not qualify (a larger sample, a mask blend, unaligned buffers ...) takes its
+   mode-0 path in the same call, with the workspace that path needs; as st[0] it is DPM_ERR_ARG as before.  Without the flag
+   every call is version 209's, the refusal of DPM_F_THRESH in st[0] included.  FILL still makes no HIP call; LAUNCH copies,
+   allocates and synchronises nothing.  Every sample gets the bits of its request's own dpm_stage_launch.
+   Any other table_mode (valid: 1, 2, 5, 6, 9, 10, 13, 14), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
 /* scratch needed by stages with DPM_F_THRESH on the current device: 0 when one workgroup per sample is the plan (the
