@@ -54,6 +54,8 @@ def _launch_ctx(dev):
 # can put its numpy double of the kernel behind the very same records)
 _stage_launch_raw = L.lib.dpm_stage_launch
 _stage_launch_multi_raw = L.lib.dpm_stage_launch_multi
+# ... and the stand-alone mask blend an inpainting slab pool runs on a request's rows before its first update (slab.py)
+_blend_launch_raw = L.lib.dpm_blend_launch
 
 
 # ---- the slab pool's staging (dpm_solver_amd/slab.py): pinned host memory and the one host-to-device copy of a tick.  Names of

@@ -143,3 +143,4 @@ const void* dpm_catchall_scalar_unipc();  // the UniPC stages' one-element-per-l
 #include "dpm_shapes_kernel.hpp"
 #include "dpm_table_kernel.hpp"
 #include "dpm_table_thresh.hpp"
+#include "dpm_table_blend.hpp"

@@ -19,7 +19,8 @@
 
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
-// pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones.
+// pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones, unit D (3) the
+// table-driven launch's mask-blend rows.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -59,6 +60,13 @@ int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req
 // a thresholded row is a row like any other), one workgroup per sample
 template <typename TS, typename TE>
 int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream);
+// (unit D) DPM_TABLE_FILL | DPM_TABLE_BLEND: rows and blend records (DPM_TABLE_BLEND_BYTES each: KBlendTab,
+// dpm_table_blend.hpp) of one group of DPM_F_BLEND stages, into HOST memory
+template <typename TS, typename TE>
+int dpm_table_fill_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs);
+// DPM_TABLE_LAUNCH | DPM_TABLE_BLEND: one launch over the group's rows and records in DEVICE memory
+template <typename TS, typename TE>
+int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

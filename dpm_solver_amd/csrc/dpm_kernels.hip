@@ -38,6 +38,8 @@ using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, 
 using TableFillNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
 using TableLaunchNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 using TableLaunchThreshFn = TableLaunchFn;
+using TableFillBlendFn = TableFillNoiseFn;
+using TableLaunchBlendFn = TableLaunchNoiseFn;
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
@@ -49,11 +51,14 @@ struct PairUnits {
   TableFillNoiseFn table_fill_noise;      // (DPM_TABLE_NOISE) rows and noise records of a group of SDE stages
   TableLaunchNoiseFn table_launch_noise;  // ... and the one launch over them
   TableLaunchThreshFn table_launch_thresh;  // (DPM_TABLE_THRESH) the one launch over a group of thresholded rows (table_fill's)
+  TableFillBlendFn table_fill_blend;        // unit D's (DPM_TABLE_BLEND): rows and blend records of a group of DPM_F_BLEND stages
+  TableLaunchBlendFn table_launch_blend;    // ... and the one launch over them
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>,      \
-   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>},
+   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>,                \
+   dpm_table_fill_blend<TS, TE>, dpm_table_launch_blend<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -287,10 +292,16 @@ bool thresh_row(const dpm_stage* st, const dpm_buffers* bs, int r) {
 // het_same_group's keys and on the bit patterns of thr_ratio / thr_max, takes any of LIN1 / TWO / MS3 / DENOISE and is
 // one stage_thresh_kernel_table launch.  fusable_request refuses DPM_F_THRESH, so such a request never joins another group;
 // one that does not qualify goes as in mode 0.
+// With DPM_TABLE_BLEND on the mode, DPM_F_BLEND requests that pass blend_row_ok (dpm_table_blend.hpp) own rows too, from ONE member
+// on, and a blend record each in a section of its own behind the noise records' (record i beside row i): a group of them
+// agrees on het_same_group's keys, takes any of LIN1 / TWO / MS3 and is one stage_kernel_table_blend launch.  fusable_request
+// refuses DPM_F_BLEND, so such a request never joins a plain group; one that does not qualify goes as in mode 0, where its
+// own launch blends.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
   const bool noise_rows = (table_mode & DPM_TABLE_NOISE) != 0;
   const bool thresh_rows = (table_mode & DPM_TABLE_THRESH) != 0;
-  table_mode &= ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH);
+  const bool blend_rows = (table_mode & DPM_TABLE_BLEND) != 0;
+  table_mode &= ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
@@ -305,6 +316,12 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
     if (const int rc = check_noise_base(st[r], bs[r], noise_row(r))) return rc;
   char* const rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
   char* const recs = rows + (int64_t)n_req * (int64_t)DPM_TABLE_ROW_BYTES;
+  // the blend records: a section of their own, behind the n_req noise records a DPM_TABLE_NOISE call has room for
+  char* const brecs = recs + (noise_rows ? (int64_t)n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
+  // does request r own a row of stage_kernel_table_blend?
+  auto blend_row = [&](int r) {
+    return blend_rows && fuse && bs[r].n > 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) && blend_row_ok(st[r], bs[r]);
+  };
   int64_t n_rows = 0;
   uint32_t n_runs = 0;
   std::vector<char> done((size_t)n_req, 0);
@@ -325,12 +342,17 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
       gi[cnt++] = r;
     };
     const bool thr = thresh_rows && fuse && thresh_row(st, bs, r0);
+    const bool bl = !thr && blend_row(r0);
     if (thr) {
       const int64_t cap = std::min<int64_t>(table_group_cap(bs[r0].n), 0x7fffffff / bs[r0].batch);
       for (int r = r0; r < n_req && cnt < cap; ++r)
         if (!done[r] && thresh_row(st, bs, r) && het_same_group(st[r0], bs[r0], st[r], bs[r], false) &&
             thresh_same_group(st[r0], st[r]))
           join(r);
+    } else if (bl) {
+      const int64_t cap = table_group_cap(bs[r0].n);
+      for (int r = r0; r < n_req && cnt < cap; ++r)
+        if (!done[r] && blend_row(r) && het_same_group(st[r0], bs[r0], st[r], bs[r], false)) join(r);
     } else if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
       const int64_t cap = table_mode ? table_group_cap(bs[r0].n) : HET_MAX;
       for (int r = r0; r < n_req && cnt < cap; ++r)
@@ -344,14 +366,18 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
     // SDE groups take the table with DPM_TABLE_NOISE only (stage_kernel_table_noise, from one member on); without the flag
     // they go as in mode 0, beyond HET_MAX members in launches of HET_MAX
     const bool sde = (st[r0].flags & DPM_F_NOISE) != 0;
-    const bool tabled = table_mode && (thr ? cnt >= 1 : sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
+    const bool tabled = table_mode && (thr || bl ? cnt >= 1 : sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
     if (tabled) {
       const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
       void* run = rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
       void* nzs = recs + n_rows * (int64_t)DPM_TABLE_NOISE_BYTES;
+      void* bls = brecs + n_rows * (int64_t)DPM_TABLE_BLEND_BYTES;
       int rc;
       if (thr)
         rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch_thresh(gs.data(), gb.data(), cnt, run, stream);
+      else if (bl)
+        rc = fill ? p.table_fill_blend(gs.data(), gb.data(), cnt, run, bls)
+                  : p.table_launch_blend(gs.data(), gb.data(), cnt, run, bls, stream);
       else if (sde)
         rc = fill ? p.table_fill_noise(gs.data(), gb.data(), cnt, run, nzs)
                   : p.table_launch_noise(gs.data(), gb.data(), cnt, run, nzs, stream);
@@ -393,10 +419,10 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH);
+  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
-                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH)", o->table_mode);
+                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND)", o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");
   if (o->fuse_shapes == 1)

@@ -1,13 +1,15 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled fifteen times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2> (__graft_entry__.py).
+// translation unit: compiled twenty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
 //               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
 //   unit C (2): the table-driven heterogeneous launchers (stage_kernel_table, stage_kernel_table_unipc,
 //               stage_kernel_table_noise, stage_thresh_kernel_table) and nothing else -- a unit of its own, so that units A and B compile to the code they compiled to before it existed
+//   unit D (3): the mask-blend rows of the table-driven launch (stage_kernel_table_blend, DPM_TABLE_BLEND) and nothing else --
+//               again a unit of its own: units A, B and C compile to the code they compiled to before it existed
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -31,7 +33,7 @@ template const void* dpm_catchall_scalar_noise<State, Eps>();
 template const void* dpm_catchall_scalar_unipc<State, Eps>();
 #endif
 
-#if DPM_UNIT != 2
+#if DPM_UNIT < 2
 template <typename TS, typename TE, unsigned FORMS>
 int dpm_launch_unit(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop,
                     const dpm_stage* dyn, const int32_t* skip, const dpm_buffers* multi, int n_multi) {
@@ -105,4 +107,21 @@ int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_re
   return launch_table_thresh_typed<TS, TE>(st, bs, n_req, rows, s);
 }
 template int dpm_table_launch_thresh<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+#endif
+
+#if DPM_UNIT == 3
+template <typename TS, typename TE>
+int dpm_table_fill_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs) {
+  table_fill_rows(st, bs, n_req, rows);
+  table_fill_blend(st, bs, n_req, recs);
+  return DPM_OK;
+}
+template int dpm_table_fill_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+
+template <typename TS, typename TE>
+int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_blend_typed<TS, TE>(st, bs, n_req, rows, recs, s);
+}
+template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 #endif

@@ -57,6 +57,27 @@ is no multiple of 8, and one whose row is no multiple of 16 bytes (the row could
 would need a workspace the pool does not hold).
 Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, for any b, whichever rows it landed in.
 Without `thresholding=True` a slab pool refuses a thresholding solver as before.
+
+`request_pool(slots=S, inpaint=True)` also admits inpainting / DiffEdit requests: `submit(x, ..., blend=mb)`, `mb` a
+`MaskBlend` that is a pure function of (stage, element) -- `x0=` with `noise=` given (the fixed-noise re-noising of the known
+image), or `intermediates=` (DiffEdit); `time_fn` is honoured, evaluated once per stage of the plan at submit.  The tick's two
+calls then carry DPM_TABLE_BLEND: every blend row is a row of the table whatever their number -- one
+stage_kernel_table_blend launch beside the plain family's -- with a blend record behind the rows (and behind the noise
+records of an `sde=True` pool; the staging is sized for that section).  Admission materialises, once per request, in the state
+dtype and contiguous: the mask at its own period (a `[H,W]` mask stays H*W elements; a period that is no multiple of 8 is
+expanded to the full sample), the known image, the noise, one tensor per step for `intermediates`, and per-stage arrays of
+(alpha, sigma) from the host schedule; the pool keeps them alive while the request is active or waiting.  A steady tick stays
+vectorised: DPM_F_BLEND is or-ed into the flags of every blend row's record, blend_alpha / blend_sigma and the three
+pointers are gathered by (request, position) and computed as base + sample * stride, mask_period is per row.  On the tick
+that admits such a request its rows of the current state slab are blended after the network call and before the stage launch,
+as `sample()` blends x_T after the first evaluation (dpm_blend_launch through a temporary -- the kernel's operands are
+__restrict__ --, once per run of consecutive rows; both halves under guidance): launches on admitting ticks only.  A row
+the table kernel does not take (the DENOISE stage of denoise_to_zero) goes as its own launch in the same call, which blends.
+Guarantee: the result is bit-identical to `sample(x, ...)` of a solver built with `correcting_xt_fn=mb` on the request alone,
+for any b, whichever rows it landed in.  Refused with NotImplementedError: `blend=` in a pool built without `inpaint=True`;
+`MaskBlend(x0=..., noise=None)` (it draws torch.randn per call: pass `noise=`); `blend=` with `sde=True` (the table has no
+blend behind the noise epilogue); `inpaint=True` with `thresholding=True` (the thresholded rows have no blend); `submit_unipc`
+takes no blend.  Without `inpaint=True` every pool behaves and refuses as before.
 """
 import ctypes as C
 
@@ -67,9 +88,12 @@ from . import _device as DV
 from . import _lib as L
 from . import sde as _sde
 from . import unipc as _unipc
+from .correctors import MaskBlend
 
 _RING = 4
 _STAGE = np.dtype(L.Stage)
+# an inpainting request's blend at one position of its plan: DPM_F_BLEND or 0, the scalars, the known image / noise of sample 0
+_BLEND = np.dtype([("flag", np.uint32), ("alpha", np.float32), ("sigma", np.float32), ("a", np.uint64), ("b", np.uint64)])
 _BUFS = np.dtype(dict(names=[{"_ns0": "noise_sample0"}.get(n, n) for n, _ in L.Buffers._fields_],
                       formats=[{4: np.int32, 8: np.uint64}[getattr(L.Buffers, n).size] for n, _ in L.Buffers._fields_],
                       offsets=[getattr(L.Buffers, n).offset for n, _ in L.Buffers._fields_], itemsize=C.sizeof(L.Buffers)))
@@ -88,19 +112,30 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend")
+
+
+class _Blend:
+    """what an inpainting request keeps alive: its tensors, its per-stage records, and the blend of x_T (`first`)"""
+    __slots__ = ("keep", "rec", "mask", "mstep", "period", "first")
 
 
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots, sde=False, thresholding=False):
+    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
         self._s, self.S = solver, slots
         self._sde = bool(sde)            # SDE requests admitted: the tick's calls carry DPM_TABLE_NOISE
         self._thr = bool(thresholding)   # a thresholding solver's pool: the tick's calls carry DPM_TABLE_THRESH
+        self._inp = bool(inpaint)        # inpainting requests admitted: the tick's calls carry DPM_TABLE_BLEND
+        self._blends = {}                # handle -> the _Blend of an active inpainting request
+        self._brec = np.zeros((slots, 0), dtype=_BLEND)  # [first row of the request, position]: its blend records
+        self._bslot = np.full(slots, -1, dtype=np.int64) # per row: the first row of its inpainting request (-1: none), the
+        self._bmask = np.zeros(slots, dtype=np.uint64)   # mask of its sample, its mask period
+        self._bper = np.zeros(slots, dtype=np.int64)
         self._ropts = {}                 # handle -> the dpm_launch_opts of an active SDE request (the solver's + its seed)
         self._optp = np.zeros(slots, dtype=np.uint64)    # per row: its request's options (0: the solver's), the sample of
         self._ns0 = np.zeros(slots, dtype=np.int32)      # its request it holds, its request's seed (SDE rows)
@@ -185,7 +220,7 @@ class SlabPool:
 
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
-               condition=None, unconditional_condition=None, seed=None, generator=None):
+               condition=None, unconditional_condition=None, seed=None, generator=None, blend=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -194,8 +229,23 @@ class SlabPool:
         that finds fewer than b free rows waits (first in, first out) and is admitted by a later step().  Returns the
         request's handle.
         `sde=True` (a pool built with sde=True): an SDE-DPM-Solver++ request -- `sample_sde`'s arguments, checks and seed rules
-        (`seed`, or one draw from `generator` / torch's default CPU generator, made here), as `RequestPool.submit`."""
+        (`seed`, or one draw from `generator` / torch's default CPU generator, made here), as `RequestPool.submit`.
+        `blend=mb` (a pool built with inpaint=True): an inpainting / DiffEdit request -- the result of `sample()` on a solver
+        built with correcting_xt_fn=mb; see the module docstring for the forms of `MaskBlend` admitted."""
         s = self._s
+        if blend is not None:
+            if not self._inp:
+                raise NotImplementedError("slab pool: blend= -- mask-blend stages take the table in a pool built with "
+                                          "request_pool(slots=..., inpaint=True) only")
+            if not isinstance(blend, MaskBlend):
+                raise NotImplementedError("slab pool: blend= takes a dpm_solver_amd.MaskBlend (any other correcting_xt_fn runs "
+                                          "Python between stages; sample with sample())")
+            if sde:
+                raise NotImplementedError("slab pool: blend= with sde=True -- the table has no blend behind the noise epilogue; "
+                                          "sample it with sample_sde()")
+            if blend.intermediates is None and blend.noise is None:
+                raise NotImplementedError("slab pool: MaskBlend(x0=..., noise=None) draws torch.randn per call, which a pool "
+                                          "cannot reproduce; pass noise= (the fixed-noise re-noising of the known image)")
         if not sde and (seed is not None or generator is not None):
             raise ValueError("slab pool: `seed` / `generator` belong to an SDE request (sde=True)")
         self._refuse(method, sde, return_intermediate)
@@ -210,7 +260,7 @@ class SlabPool:
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   solver_type, sde=bool(sde))
-        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None)
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
@@ -255,7 +305,55 @@ class SlabPool:
             raise ValueError("slab pool: condition and unconditional_condition differ in shape or dtype")
         return cond, uncond
 
-    def _enqueue(self, x, plan, cond, uncond, seed=None):
+    def _blend_of(self, mb, x, plan, sd):
+        """the request's `_Blend`: everything a tick must not compute per request, once, in the state dtype and contiguous"""
+        shape, dev, es = tuple(x.shape), x.device, torch.empty((), dtype=sd).element_size()
+        b, per = int(shape[0]), self._per
+        q = _Blend()
+        m, period = mb._mask_for(shape, sd, dev)
+        if period > per:                 # a full-size mask: sample k has its own `per` elements
+            q.mstep, q.period = per * es, per
+        else:
+            if period % 8 != 0:          # a period the vector path cannot take: the full sample
+                m, period = m.reshape(-1).repeat(per // period), per
+            q.mstep, q.period = 0, period
+        q.mask, q.keep = m, [m]
+        n = len(plan.stages)
+        q.rec = np.zeros(n, dtype=_BLEND)
+        ops = {}
+
+        def dense(t):                    # as MaskBlend.operands brings its tensors to the state
+            t = t.to(device=dev, dtype=sd)
+            return (t.expand(shape) if tuple(t.shape) != shape else t).contiguous()
+
+        # where the blends are looked up: every stage that emits a state, at its (t_out, outer_step), then x_T at (stage 0's
+        # t_eval, 0) -- run_plan at i == 0: blend.apply(state, t_eval, 0)
+        emit = [i for i, ps in enumerate(plan.stages) if ps.emits_state]
+        r = np.zeros(len(emit) + 1, dtype=_BLEND)
+        r["flag"] = L.F_BLEND
+        if mb.intermediates is not None:         # DiffEdit: the tensor of the step, as it is
+            steps = [plan.stages[i].outer_step for i in emit] + [0]
+            for step in steps:
+                if step not in ops:
+                    ops[step] = mb.intermediates[step].to(device=dev, dtype=sd).contiguous()
+                    if tuple(ops[step].shape) != shape:
+                        raise ValueError("slab pool: intermediates[%d] of shape %s for a state of %s"
+                                         % (step, tuple(ops[step].shape), shape))
+            r["alpha"], r["a"] = 1.0, [ops[step].data_ptr() for step in steps]
+            q.first = (ops[0], None, 1.0, 0.0)
+        else:                                    # the known image at the level of time_fn(t): MaskBlend._alpha_sigma, with
+            ops["a"], ops["b"] = dense(mb.x0), dense(mb.noise)     # time_fn once per entry and ONE schedule evaluation each
+            ts = [float(plan.stages[i].t_out) for i in emit] + [float(plan.stages[0].t_eval)]
+            tt = np.array(ts if mb.time_fn is None else [float(mb.time_fn(t)) for t in ts], dtype=np.float32)
+            r["alpha"] = mb.noise_schedule._eval_np(L.EVAL_ALPHA, tt)
+            r["sigma"] = mb.noise_schedule._eval_np(L.EVAL_STD, tt)
+            r["a"], r["b"] = ops["a"].data_ptr(), ops["b"].data_ptr()
+            q.first = (ops["a"], ops["b"], float(r["alpha"][-1]), float(r["sigma"][-1]))
+        q.rec[emit] = r[:-1]
+        q.keep += list(ops.values())
+        return q
+
+    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
@@ -267,6 +365,7 @@ class SlabPool:
                              % (tuple(cond.shape[1:]), cond.dtype, tuple(self._cslab.shape[1:]), self._cslab.dtype))
         q = _Waiting()
         q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
+        q.blend = None if blend is None else self._blend_of(blend, x, plan, sd)
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -292,7 +391,8 @@ class SlabPool:
             self._cslab = torch.zeros((nS,) + tuple(cond.shape[1:]), dtype=cond.dtype, device=dev)
         # staging: per ring slot a pinned buffer [table | next tick's times | this tick's times | stage array | buffers array]
         # and a device buffer for its first two parts (and one for the third: the copy an admitting tick adds)
-        self._tabb = (L.TABLE_HEADER_BYTES + S * (L.TABLE_ROW_BYTES + (L.TABLE_NOISE_BYTES if self._sde else 0)) + 15) // 16 * 16
+        self._tabb = (L.TABLE_HEADER_BYTES + S * (L.TABLE_ROW_BYTES + (L.TABLE_NOISE_BYTES if self._sde else 0)
+                                                  + (L.TABLE_BLEND_BYTES if self._inp else 0)) + 15) // 16 * 16
         self._copyb = self._tabb + 4 * nS
         o_cur = (self._copyb + 15) // 16 * 16
         o_st = (o_cur + 4 * nS + 15) // 16 * 16
@@ -319,8 +419,10 @@ class SlabPool:
         return hit[0]
 
     def _admit(self):
-        """waiting requests, first in first out, into free rows: their x_T (both halves under guidance) and conditions"""
+        """waiting requests, first in first out, into free rows: their x_T (both halves under guidance) and conditions.
+        Returns the inpainting requests among them as (rows, _Blend): their x_T is blended after the tick's network call."""
         S, cur = self.S, self._x[self._cur]
+        blends = []
         while self._wait and int(self._wait[0].x.shape[0]) <= len(self._free):
             q = self._wait.pop(0)
             b = int(q.x.shape[0])
@@ -345,7 +447,40 @@ class SlabPool:
             if q.seed is not None:       # sample k of the request sits in rows[k]: its z starts at element k * per_sample
                 o = self._ropts[q.h] = _sde.request_opts(q.seed, self._s._opts_ptr())
                 self._optp[ra], self._ns0[ra], self._seed[ra] = C.addressof(o), np.arange(b, dtype=np.int32), np.uint64(q.seed)
+            self._bslot[ra] = -1
+            if q.blend is not None:      # sample k of the request sits in rows[k]: its tensors start at element k * per_sample
+                bl = self._blends[q.h] = q.blend
+                if self._brec.shape[1] < len(bl.rec):
+                    grown = np.zeros((S, len(bl.rec)), dtype=_BLEND)
+                    grown[:, :self._brec.shape[1]] = self._brec
+                    self._brec = grown
+                self._brec[rows[0], :len(bl.rec)] = bl.rec
+                self._bslot[ra], self._bper[ra] = rows[0], bl.period
+                self._bmask[ra] = np.uint64(bl.mask.data_ptr()) + np.arange(b, dtype=np.uint64) * np.uint64(bl.mstep)
+                self._ns0[ra] = np.arange(b, dtype=np.int32)
+                blends.append((rows, bl))
             self._rows[q.h] = (rows, q.mf)
+        return blends
+
+    def _blend_first(self, blends, xin, stream):
+        """x_T of the inpainting requests admitted on this tick, blended in the current state slab as run_plan blends it at
+        i == 0 -- after the network has seen it.  One dpm_blend_launch per run of consecutive rows, through a temporary (the
+        kernel's x and out are __restrict__: not in place); both halves under guidance."""
+        S, per, rowb, code = self.S, self._per, self._rowb, DV._DT[self._sd]
+        for rows, bl in blends:
+            a, bb, alpha, sigma = bl.first
+            k = 0
+            for r0, cnt in _runs(rows):
+                tmp = torch.empty_like(xin[r0:r0 + cnt])
+                full = bl.mstep != 0
+                L.check(DV._blend_launch_raw(xin[r0:r0 + cnt].data_ptr(), bl.mask.data_ptr() + k * bl.mstep,
+                                             a.data_ptr() + k * rowb, None if bb is None else bb.data_ptr() + k * rowb,
+                                             alpha, sigma, tmp.data_ptr(), cnt * per, cnt * per if full else bl.period, code,
+                                             stream))
+                xin[r0:r0 + cnt].copy_(tmp)
+                if self._cfg:
+                    xin[S + r0:S + r0 + cnt].copy_(tmp)
+                k += cnt
 
     def _network(self, x, t):
         """ONE call on the whole slab: the raw output(s) as (e0, e1), e1 the unconditional half under guidance"""
@@ -386,7 +521,7 @@ class SlabPool:
         if capturing:
             raise RuntimeError("slab pool: ticks are not captured into graphs")
         with torch.no_grad():
-            self._admit()
+            admitted = self._admit()
             rows = np.flatnonzero(self._req >= 0)
             R = len(rows)
             if R == 0:
@@ -409,6 +544,12 @@ class SlabPool:
             xin, xout = self._x[self._cur], self._x[1 - self._cur]
             e0, e1 = self._network(xin if self._cfg else xin[:S], t_dev)
             e0, e1, ed = self._bind(e0, e1)
+            if admitted:
+                if other:
+                    with torch.cuda.device(idx_dev):
+                        self._blend_first(admitted, xin, stream)
+                else:
+                    self._blend_first(admitted, xin, stream)
             # the tick's records, vectorised: stage r = the record of row rows[r] at its position, pointers = base + row * stride
             st_v[:R] = rec
             b = b_v[:R]
@@ -439,8 +580,24 @@ class SlabPool:
                 b["noise_sample0"] = np.where((rec["flags"] & L.F_NOISE) != 0, self._ns0[rows], 0)
                 seed0 = int(self._seed[rows[0]]) if own[0] else 0      # row 0's options are the call's: they carry its seed
                 self._opts.noise_seed_lo, self._opts.noise_seed_hi = seed0 & 0xffffffff, seed0 >> 32
+            if self._inp:
+                # blend rows: DPM_F_BLEND, the scalars and the pointers of (request, position), sample k at base + k * stride
+                slot = self._bslot[rows]
+                width = self._brec.shape[1]
+                br = (self._brec[np.clip(slot, 0, None), np.minimum(self._pos[rows], width - 1)] if width
+                      else np.zeros(R, dtype=_BLEND))
+                on = (slot >= 0) & (br["flag"] != 0)
+                kb = self._ns0[rows].astype(np.uint64) * np.uint64(self._rowb)
+                st_v["flags"][:R] |= np.where(on, br["flag"], 0).astype(np.uint32)
+                st_v["blend_alpha"][:R] = np.where(on, br["alpha"], np.float32(0))
+                st_v["blend_sigma"][:R] = np.where(on, br["sigma"], np.float32(0))
+                b["mask"] = np.where(on, self._bmask[rows], np.uint64(0))
+                b["blend_a"] = np.where(on, br["a"] + kb, np.uint64(0))
+                b["blend_b"] = np.where(on & (br["b"] != 0), br["b"] + kb, np.uint64(0))
+                b["mask_period"] = np.where(on, self._bper[rows], 0)
             b["opts"][0] = C.addressof(self._opts)
-            flag = (L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
+            flag = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
+                    | (L.TABLE_BLEND if self._inp else 0))
             # next tick's time vector rides with this tick's table
             go = ~last
             t_next = self._times_of(rows[go], idx[go] + 1)
@@ -476,6 +633,7 @@ class SlabPool:
             for h in np.unique(self._req[rows[last]]).tolist():
                 rws, mf = self._rows.pop(h)
                 self._ropts.pop(h, None)
+                self._blends.pop(h, None)
                 parts = [xout[r0:r0 + cnt] for r0, cnt in _runs(rws)]
                 out = parts[0].clone() if len(parts) == 1 else torch.cat(parts)
                 done[h] = out if mf is None else DV._conv(out, out.dtype, mf)

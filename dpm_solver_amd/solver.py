@@ -701,7 +701,7 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False):
+    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -713,12 +713,21 @@ class DPM_Solver:
         also admits SDE-DPM-Solver++ requests (`submit(x, ..., sde=True, seed=...)`), their stages in the table-driven launch
         too (DPM_TABLE_NOISE).  `slots=S, thresholding=True`: the slab pool of a solver built with
         correcting_x0_fn="dynamic_thresholding" -- samples of at most 12288 elements, their thresholded stages in the
-        table-driven launch too (DPM_TABLE_THRESH); without the flag a slab pool refuses such a solver."""
+        table-driven launch too (DPM_TABLE_THRESH); without the flag a slab pool refuses such a solver.
+        `slots=S, inpaint=True` (alone or with sde=True): the slab pool also admits inpainting / DiffEdit requests
+        (`submit(x, ..., blend=MaskBlend(...))`, the result of sample() with correcting_xt_fn=blend), their mask-blend stages
+        in the table-driven launch too (DPM_TABLE_BLEND)."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
         if thresholding and slots is None:
             raise ValueError("request_pool: thresholding=True belongs to a slab pool (slots=...); a RequestPool takes a "
                              "thresholding solver as it is")
+        if inpaint and slots is None:
+            raise ValueError("request_pool: inpaint=True belongs to a slab pool (slots=...); a RequestPool takes no "
+                             "correcting_xt_fn")
+        if inpaint and thresholding:
+            raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
+                                      "no mask blend")
         if thresholding and not self._thresholding:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
@@ -726,7 +735,7 @@ class DPM_Solver:
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding)
+            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -129,6 +129,13 @@ def main():
         y = edit.sample(x_T, steps=20, order=2)
     err = ((y - known) * (1 - mask)).abs().max().item()
     print("inpaint: max |y - known| outside the mask at t_end = %.3g (the known image, noised to t = 1e-3)" % err)
+    # ... and as a request of a slab pool: its mask-blend stages ride the table-driven tick (one network call, one launch)
+    with torch.no_grad():
+        pool, done = DPM_Solver(model_fn, ns).request_pool(slots=B, inpaint=True), {}
+        h = pool.submit(x_T, steps=20, order=2, blend=edit.correcting_xt_fn)
+        while pool:
+            done.update(pool.step())
+    print("request_pool(slots=%d, inpaint=True): max |pool - sample()| = %.3g" % (B, (done[h] - y).abs().max().item()))
 
 
 if __name__ == "__main__":

@@ -76,11 +76,14 @@ extern "C" {
    210 DPM_TABLE_THRESH (a flag on table_mode): thresholded stages in the table -- every DPM_F_THRESH request whose sample fits
    one workgroup's LDS owns a row, a group of them is ONE cluster-free launch without a workspace (see "Table mode"; no entry
    point added, no struct changed, rows and records as in version 209).
+   211 DPM_TABLE_BLEND (a flag on table_mode), DPM_TABLE_BLEND_BYTES / DPM_SIZEOF_TABLE_BLEND: mask-blend stages (DPM_F_BLEND,
+   inpainting / DiffEdit) in the table -- every qualifying DPM_F_BLEND request owns a row and a blend record behind the rows,
+   a group of them is ONE stage_kernel_table_blend launch (see "Table mode"; no entry point added, no struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 210
+#define DPM_HIP_VERSION 211
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -250,8 +253,12 @@ enum { DPM_TABLE_NOISE = 4 }; /* version 209: a flag OR-ed onto DPM_TABLE_FILL /
                                  take rows too, each with a noise record behind the rows */
 enum { DPM_TABLE_THRESH = 8 }; /* version 210: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without DPM_TABLE_NOISE
                                   (table_mode 9 / 10 / 13 / 14): thresholded stages of small samples take rows too */
+enum { DPM_TABLE_BLEND = 32 }; /* version 211: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the two flags
+                                   above: DPM_F_BLEND stages take rows too, each with a blend record behind the rows.  (Bit 16
+                                   is unassigned: table_mode 16 .. 31 stay DPM_ERR_ARG, as in version 210.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
+#define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -454,8 +461,8 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        function: the same row order); a group with rows is ONE launch over its run of rows, every other
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
-   SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend, classifier
-   guidance and DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
+   DPM_TABLE_BLEND), classifier guidance and DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -490,7 +497,33 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    mode-0 path in the same call, with the workspace that path needs; as st[0] it is DPM_ERR_ARG as before.  Without the flag
    every call is version 209's, the refusal of DPM_F_THRESH in st[0] included.  FILL still makes no HIP call; LAUNCH copies,
    allocates and synchronises nothing.  Every sample gets the bits of its request's own dpm_stage_launch.
-   Any other table_mode (valid: 1, 2, 5, 6, 9, 10, 13, 14), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   Blend rows (version 211): DPM_TABLE_BLEND OR-ed onto either mode, alone or with DPM_TABLE_NOISE / DPM_TABLE_THRESH, makes the
+   same tick with mask-blend stages (DPM_F_BLEND: inpainting, DiffEdit) in the table (stage_kernel_table_blend: stage_kernel_table
+   over the forms LIN1 / TWO / MS3 with the blend epilogue of dpm_stage_launch).  A DPM_F_BLEND request owns a row when it
+   passes every rule of the fused groups above apart from the DPM_F_BLEND bit -- guidance none or CFG, evaluation state =
+   state, dense buffers of whole 8-element groups, aligned as there, x_out2 only under CFG, a 2- or 4-byte dtype pair --, its
+   form is LIN1, TWO or MS3, it has neither DPM_F_NOISE nor DPM_F_THRESH, mask, blend_a and blend_b (which may be NULL: blend_a
+   is blended in as it is) are 16-byte aligned, mask_period is a multiple of 8 and n a multiple of mask_period.  Such requests
+   form groups of their own -- never with a request without the blend -- that agree on dtypes, n, batch, model type, guidance
+   kind and DPM_F_TO_X0; the three forms, blend_b NULL and not NULL, and every mask_period share a group (a row whose period is a
+   multiple of 2048 takes the split tile layout of a 4-byte state, a row next to it with period 8 does not: per row,
+   wave-uniform).  Every group, from ONE member on, is one run of rows and ONE launch, the runs in the order the groups open,
+   among those of the other families.  Behind the rows -- and behind the n_req noise records a DPM_TABLE_NOISE call has room
+   for -- the table holds one blend record per row: the record of table row i (counted over all runs) is the
+   DPM_TABLE_BLEND_BYTES bytes at
+     dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * dpm_sizeof(DPM_SIZEOF_TABLE_ROW)
+       + (DPM_TABLE_NOISE set ? n_req * DPM_TABLE_NOISE_BYTES : 0) + DPM_TABLE_BLEND_BYTES * i
+   so the two record sections never overlap and each keeps its own index; the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) +
+   n_req * (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + [DPM_TABLE_NOISE_BYTES] + [DPM_TABLE_BLEND_BYTES]) bytes.  A record is three
+   device pointers -- mask, blend_a, blend_b of the request's dpm_buffers --, the 64-bit mask_period, the bits of
+   st[r].blend_alpha and st[r].blend_sigma, and two zero words.  FILL writes the records of blend rows only and leaves every
+   other byte of the section untouched; LAUNCH reads them in place (scalar loads) and writes nothing to the table.  A
+   DPM_F_BLEND request that does not qualify (a DPM_FORM_DENOISE stage, a period that is no multiple of 8, a misaligned mask,
+   DPM_F_NOISE or DPM_F_THRESH next to the blend ...) goes, in the same call, as its own dpm_stage_launch, which blends too:
+   the same bits, one more launch.  Without the flag every call is version 210's.  Every request gets the bits of its own
+   dpm_stage_launch.
+   Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND:
+   1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46), a non-zero one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
@@ -633,7 +666,8 @@ DPM_API int dpm_version(void);
 enum { DPM_SIZEOF_STAGE = 0, DPM_SIZEOF_BUFFERS = 1, DPM_SIZEOF_PLAN_DESC = 2, DPM_SIZEOF_RUN_BUFFERS = 3,
        DPM_SIZEOF_ADAPTIVE_DESC = 4, DPM_SIZEOF_LAUNCH_OPTS = 5, DPM_SIZEOF_STAGE_F64 = 6,
        DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */,
-       DPM_SIZEOF_TABLE_NOISE = 10 /* version 209: a noise record of a DPM_TABLE_NOISE table (9 is unassigned: 0) */ };
+       DPM_SIZEOF_TABLE_NOISE = 10 /* version 209: a noise record of a DPM_TABLE_NOISE table (9 is unassigned: 0) */,
+       DPM_SIZEOF_TABLE_BLEND = 12 /* version 211: a blend record of a DPM_TABLE_BLEND table (11 is unassigned: 0) */ };
 DPM_API size_t dpm_sizeof(int which);
 DPM_API const char* dpm_last_error(void); /* thread-local text of the last non-zero return */
 DPM_API int dpm_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len);
