@@ -306,6 +306,14 @@ TABLE_NOISE_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_NOISE))        # (TABLE_NOIS
 TABLE_BLEND_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_BLEND))        # (TABLE_BLEND) behind those, one blend record per row
 
 
+def table_bytes(n_req, flags=0):
+    """The bytes of the table of a table-mode call of n_req requests whose table_mode carries `flags` (TABLE_NOISE / TABLE_THRESH /
+    TABLE_BLEND; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
+    Not rounded."""
+    return (TABLE_HEADER_BYTES + n_req * (TABLE_ROW_BYTES + (TABLE_NOISE_BYTES if flags & TABLE_NOISE else 0)
+                                          + (TABLE_BLEND_BYTES if flags & TABLE_BLEND else 0)))
+
+
 if IS_LAB and os.environ.get("DPM_LAB_TUNE"):
     # lab build only: knobs for a whole tool run, e.g. DPM_LAB_TUNE="thr_elect=1,thr_predict=0" (A/B runs under rocprofv3)
     for _kv in os.environ["DPM_LAB_TUNE"].split(","):

@@ -43,30 +43,23 @@ int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req,
 // (unit C) the table of dpm_launch_opts.table_mode (include/dpm_hip.h): a 16-byte header, then rows of 8 pointers and the
 // kernels' 80-byte stage scalars (TableRow, dpm_table_kernel.hpp)
 constexpr size_t DPM_TABLE_HEADER_BYTES = 16, DPM_TABLE_ROW_BYTES = 8 * 8 + 80;
-// (DPM_TABLE_NOISE) the noise record of a row behind the rows: DPM_TABLE_NOISE_BYTES each (KNoiseTab, dpm_stage_kernel.hpp)
-// DPM_TABLE_FILL: the rows of one group, members in call order, into HOST memory (no HIP call)
+// Behind the rows: the noise records of a DPM_TABLE_NOISE call (DPM_TABLE_NOISE_BYTES each: KNoiseTab, dpm_stage_kernel.hpp),
+// behind those the blend records of a DPM_TABLE_BLEND call (DPM_TABLE_BLEND_BYTES each: KBlendTab, dpm_table_blend.hpp).
+// DPM_TABLE_FILL is host code without a dtype (table_fill_rows and
+// the record fills, called by dpm_kernels.hip itself); DPM_TABLE_LAUNCH is ONE launch per group, one launcher per row kind, all of
+// one signature: the group's run of rows and its records (null for a kind without records) in DEVICE memory.
+// plain and UniPC rows
 template <typename TS, typename TE>
-int dpm_table_fill(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows);
-// DPM_TABLE_LAUNCH: one launch over the group's run of rows in DEVICE memory
+int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (DPM_TABLE_NOISE) SDE rows and their noise records
 template <typename TS, typename TE>
-int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream);
-// DPM_TABLE_FILL | DPM_TABLE_NOISE: rows and noise records of one group of SDE stages, into HOST memory
+int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (DPM_TABLE_THRESH) thresholded rows -- rows like any other, no records --, one workgroup per sample
 template <typename TS, typename TE>
-int dpm_table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs);
-// DPM_TABLE_LAUNCH | DPM_TABLE_NOISE: one launch over the group's rows and records in DEVICE memory
+int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (unit D, DPM_TABLE_BLEND) DPM_F_BLEND rows and their blend records
 template <typename TS, typename TE>
-int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream);
-// DPM_TABLE_LAUNCH | DPM_TABLE_THRESH: one launch over a group's thresholded rows in DEVICE memory (filled by dpm_table_fill:
-// a thresholded row is a row like any other), one workgroup per sample
-template <typename TS, typename TE>
-int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream);
-// (unit D) DPM_TABLE_FILL | DPM_TABLE_BLEND: rows and blend records (DPM_TABLE_BLEND_BYTES each: KBlendTab,
-// dpm_table_blend.hpp) of one group of DPM_F_BLEND stages, into HOST memory
-template <typename TS, typename TE>
-int dpm_table_fill_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs);
-// DPM_TABLE_LAUNCH | DPM_TABLE_BLEND: one launch over the group's rows and records in DEVICE memory
-template <typename TS, typename TE>
-int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream);
+int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -33,32 +33,22 @@ using UnitFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*
                        const dpm_buffers*, int);
 using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
 using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
-using TableFillFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
-using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
-using TableFillNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*);
-using TableLaunchNoiseFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
-using TableLaunchThreshFn = TableLaunchFn;
-using TableFillBlendFn = TableFillNoiseFn;
-using TableLaunchBlendFn = TableLaunchNoiseFn;
+// the one launch over a group's run of table rows and its records (null: the kind has none), both in device memory
+using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
   FusedFn fused;
   HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
-  TableFillFn table_fill;      // unit C's table-driven launcher (dpm_launch_opts.table_mode): the rows of a group, on the host,
-  TableLaunchFn table_launch;  // ... and the one launch over them
-  TableFillNoiseFn table_fill_noise;      // (DPM_TABLE_NOISE) rows and noise records of a group of SDE stages
-  TableLaunchNoiseFn table_launch_noise;  // ... and the one launch over them
-  TableLaunchThreshFn table_launch_thresh;  // (DPM_TABLE_THRESH) the one launch over a group of thresholded rows (table_fill's)
-  TableFillBlendFn table_fill_blend;        // unit D's (DPM_TABLE_BLEND): rows and blend records of a group of DPM_F_BLEND stages
-  TableLaunchBlendFn table_launch_blend;    // ... and the one launch over them
+  // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
+  // thresholded rows, unit D's mask-blend rows
+  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend;
 };
-#define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                        \
-  {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>, \
-   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_fill<TS, TE>, dpm_table_launch<TS, TE>,      \
-   dpm_table_fill_noise<TS, TE>, dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>,                \
-   dpm_table_fill_blend<TS, TE>, dpm_table_launch_blend<TS, TE>},
+#define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
+  {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
+   dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
+   dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -248,11 +238,6 @@ bool het_same_group(const dpm_stage& s0, const dpm_buffers& b0, const dpm_stage&
 // UNIPC}: the form of the two a record brings, 0 for the forms every group takes
 int het_third_form(const dpm_stage& s) { return s.form == DPM_FORM_MS3 || s.form == DPM_FORM_UNIPC ? s.form : 0; }
 
-// dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
-// HET_MAX (first come, first grouped; the first MS3 or UNIPC record to join a group closes it to the other form, whose
-// records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
-// all share one n still takes the kernels it always took, one with at least two takes the mixed-shape family -- or, should
-// its tile space not fit that family's 32-bit index, single launches.
 // dpm_buffers.noise_sample0 of one request of a DPM_TABLE_NOISE call: honoured by a request that will own a noise row (`row`),
 // an error on every other; non-negative, a whole number of Philox blocks
 int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
@@ -273,55 +258,90 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
   return DPM_OK;
 }
 
-// does request r own a row of stage_thresh_kernel_table in a DPM_TABLE_THRESH call?  (thresh_row_ok, dpm_table_thresh.hpp)
-bool thresh_row(const dpm_stage* st, const dpm_buffers* bs, int r) {
-  return bs[r].batch >= 1 && bs[r].n > 0 && bs[r].n % bs[r].batch == 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) &&
-         thresh_row_ok(st[r], bs[r]);
+// The table of a table-mode call (include/dpm_hip.h, "Table mode"): the header, n_req rows, then n_req noise records if and only
+// if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND) -- record i of either section beside row i.
+struct TableSections {
+  char *rows, *noise, *blend;
+};
+TableSections table_sections(void* table, int64_t n_req, int flags) {
+  TableSections t;
+  t.rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
+  t.noise = t.rows + n_req * (int64_t)DPM_TABLE_ROW_BYTES;
+  t.blend = t.noise + ((flags & DPM_TABLE_NOISE) ? n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
+  return t;
 }
 
+// ---- The kinds of request that may own table rows, in the walk's order of precedence: a request is of the first kind whose
+// flag the call carries and whose `row_ok` it passes (row_kind).  A group of one kind agrees on het_same_group's keys and on
+// `same_group`; from `min_group` members on it owns a run of rows, and a record each in `section`, in a table-mode call.
+bool sde_row_ok(const dpm_stage& st, const dpm_buffers& b) { return (st.flags & DPM_F_NOISE) && fusable_request(st, b); }
+struct RowKind {
+  int flag;                                                // the DPM_TABLE_* flag a call needs for it (0: none)
+  bool (*row_ok)(const dpm_stage&, const dpm_buffers&);    // may the request own such a row?  (row_kind's guards come first)
+  bool (*same_group)(const dpm_stage&, const dpm_stage&);  // what a group shares besides het_same_group's keys (null: nothing)
+  bool third_form;  // ... and MS3 and UNIPC records never share a group (het_third_form)
+  bool per_sample;  // one workgroup per SAMPLE, not per super-tile: members x batch stay below 2^31, too
+  int min_group;    // the smallest group that takes the table
+  char* TableSections::*section;  // its records' section (null: a row is all there is) ...
+  size_t rec_bytes;
+  void (*fill_recs)(const dpm_stage*, const dpm_buffers*, int, void*);  // ... and what DPM_TABLE_FILL writes there
+  TableLaunchFn PairUnits::*launch;                                     // ONE launch over the group (DPM_TABLE_LAUNCH)
+};
+const RowKind kRowKinds[] = {
+    // thresholded requests whose sample fits one workgroup (dpm_table_thresh.hpp), from ONE member on: a lone launch of a small
+    // batch is a cluster with a workspace, a row is one workgroup per sample.  Any of LIN1 / TWO / MS3 / DENOISE in one group.
+    {DPM_TABLE_THRESH, thresh_row_ok, thresh_same_group, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_thresh},
+    // DPM_F_BLEND requests (dpm_table_blend.hpp), from ONE member on -- fusable_request refuses the blend, so the alternative is
+    // a launch per request.  Any of LIN1 / TWO / MS3 in one group.
+    {DPM_TABLE_BLEND, blend_row_ok, nullptr, false, false, 1, &TableSections::blend, DPM_TABLE_BLEND_BYTES, table_fill_blend,
+     &PairUnits::table_launch_blend},
+    // SDE requests, from ONE member on: a row's noise_sample0 has no other way to the kernel
+    {DPM_TABLE_NOISE, sde_row_ok, nullptr, false, false, 1, &TableSections::noise, DPM_TABLE_NOISE_BYTES, table_fill_noise,
+     &PairUnits::table_launch_noise},
+    // every other fusable request, in every call: groups of 2..HET_MAX keep the kernarg records (stage_kernel_het needs no
+    // dependent load in front of its tile's own), larger ones take the table.  An SDE group of a call without DPM_TABLE_NOISE
+    // is gathered here too -- het_same_group keeps it apart from the ODE groups -- and owns no rows (stage_launch_multi_het).
+    {0, fusable_request, nullptr, true, false, TABLE_MIN, nullptr, 0, nullptr, &PairUnits::table_launch},
+};
+
+// the kind of one request in a call that carries `flags`, or nullptr: it is launched on its own.  `fuse`: Tuning::multi_fuse.
+// For a request that has passed check_stage_buffers: thresh_row_ok divides by b.batch.
+const RowKind* row_kind(const dpm_stage& st, const dpm_buffers& b, int flags, bool fuse) {
+  if (!fuse || b.n <= 0 || !pair_of(b.state_dtype, b.eps_dtype)) return nullptr;
+  for (const RowKind& k : kRowKinds)
+    if ((k.flag & ~flags) == 0 && k.row_ok(st, b)) return &k;
+  return nullptr;
+}
+// does the request own a row of the kind that needs `flag`?
+bool owns_row(int flag, const dpm_stage& st, const dpm_buffers& b, int flags, bool fuse) {
+  const RowKind* const k = row_kind(st, b, flags, fuse);
+  return k && k->flag == flag;
+}
+
+// dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
+// HET_MAX (first come, first grouped; the first MS3 or UNIPC record to join a group closes it to the other form, whose
+// records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
+// all share one n still takes the kernels it always took, one with at least two takes the mixed-shape family -- or, should
+// its tile space not fit that family's 32-bit index, single launches.
 // table_mode (DPM_TABLE_FILL / DPM_TABLE_LAUNCH; `table` = bs[0].workspace, checked by the caller): the same walk without
-// the cap of HET_MAX -- a group is bounded by its launch's 2^31 super-tiles only.  A group of TABLE_MIN members or more owns
-// a run of consecutive table rows, members in call order, the runs in the order the groups open: FILL writes them (host
-// memory, no HIP call, nothing launched) and the header, LAUNCH launches one table kernel per run; every smaller group and
-// every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this one function, so
-// their row order is the same.
-// With DPM_TABLE_NOISE on the mode, SDE groups own rows too, from ONE member on -- a row's noise_sample0 has no other way to
-// the kernel -- and a noise record each behind the n_req rows the table has room for, record i beside row i.
-// With DPM_TABLE_THRESH on the mode, thresholded requests that pass thresh_row_ok own rows too, from ONE member on (a lone
-// launch of a small batch is a cluster with a workspace; a row is one workgroup per sample): a group of them agrees on
-// het_same_group's keys and on the bit patterns of thr_ratio / thr_max, takes any of LIN1 / TWO / MS3 / DENOISE and is
-// one stage_thresh_kernel_table launch.  fusable_request refuses DPM_F_THRESH, so such a request never joins another group;
-// one that does not qualify goes as in mode 0.
-// With DPM_TABLE_BLEND on the mode, DPM_F_BLEND requests that pass blend_row_ok (dpm_table_blend.hpp) own rows too, from ONE member
-// on, and a blend record each in a section of its own behind the noise records' (record i beside row i): a group of them
-// agrees on het_same_group's keys, takes any of LIN1 / TWO / MS3 and is one stage_kernel_table_blend launch.  fusable_request
-// refuses DPM_F_BLEND, so such a request never joins a plain group; one that does not qualify goes as in mode 0, where its
-// own launch blends.
+// the cap of HET_MAX -- a group is bounded by its launch's 2^31 super-tiles only.  A group of its kind's min_group members or
+// more owns a run of consecutive table rows (table_sections), members in call order, the runs in the order the groups open,
+// ONE row counter across the kinds: FILL writes the rows, the kind's records beside them (host memory, no HIP call, nothing
+// launched; the record slots of other rows are not touched) and the header, LAUNCH launches one table kernel per run; every
+// smaller group and every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this
+// one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
-  const bool noise_rows = (table_mode & DPM_TABLE_NOISE) != 0;
-  const bool thresh_rows = (table_mode & DPM_TABLE_THRESH) != 0;
-  const bool blend_rows = (table_mode & DPM_TABLE_BLEND) != 0;
-  table_mode &= ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
+  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
+  const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0;
+  table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
     if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;
-  // does request r own a row of stage_kernel_table_noise?  (a group's first member decides for the group: het_same_group)
-  auto noise_row = [&](int r) {
-    return noise_rows && fuse && (st[r].flags & DPM_F_NOISE) && bs[r].n > 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) &&
-           fusable_request(st[r], bs[r]);
-  };
   for (int r = 0; noise_rows && r < n_req; ++r)
-    if (const int rc = check_noise_base(st[r], bs[r], noise_row(r))) return rc;
-  char* const rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
-  char* const recs = rows + (int64_t)n_req * (int64_t)DPM_TABLE_ROW_BYTES;
-  // the blend records: a section of their own, behind the n_req noise records a DPM_TABLE_NOISE call has room for
-  char* const brecs = recs + (noise_rows ? (int64_t)n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
-  // does request r own a row of stage_kernel_table_blend?
-  auto blend_row = [&](int r) {
-    return blend_rows && fuse && bs[r].n > 0 && pair_of(bs[r].state_dtype, bs[r].eps_dtype) && blend_row_ok(st[r], bs[r]);
-  };
+    if (const int rc = check_noise_base(st[r], bs[r], owns_row(DPM_TABLE_NOISE, st[r], bs[r], flags, fuse))) return rc;
+  const TableSections sec = table_mode ? table_sections(table, n_req, flags) : TableSections{};
   int64_t n_rows = 0;
   uint32_t n_runs = 0;
   std::vector<char> done((size_t)n_req, 0);
@@ -341,49 +361,35 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
       gb[cnt] = bs[r];
       gi[cnt++] = r;
     };
-    const bool thr = thresh_rows && fuse && thresh_row(st, bs, r0);
-    const bool bl = !thr && blend_row(r0);
-    if (thr) {
-      const int64_t cap = std::min<int64_t>(table_group_cap(bs[r0].n), 0x7fffffff / bs[r0].batch);
-      for (int r = r0; r < n_req && cnt < cap; ++r)
-        if (!done[r] && thresh_row(st, bs, r) && het_same_group(st[r0], bs[r0], st[r], bs[r], false) &&
-            thresh_same_group(st[r0], st[r]))
-          join(r);
-    } else if (bl) {
-      const int64_t cap = table_group_cap(bs[r0].n);
-      for (int r = r0; r < n_req && cnt < cap; ++r)
-        if (!done[r] && blend_row(r) && het_same_group(st[r0], bs[r0], st[r], bs[r], false)) join(r);
-    } else if (fuse && pair_of(bs[r0].state_dtype, bs[r0].eps_dtype) && fusable_request(st[r0], bs[r0])) {
-      const int64_t cap = table_mode ? table_group_cap(bs[r0].n) : HET_MAX;
-      for (int r = r0; r < n_req && cnt < cap; ++r)
-        if (!done[r] && fusable_request(st[r], bs[r]) && het_same_group(st[r0], bs[r0], st[r], bs[r], shapes)) {
-          const int f = het_third_form(st[r]);
-          if (f && third && f != third) continue;
-          if (f) third = f;
-          join(r);
+    // the group r0 opens: every later request of its kind that agrees with it, in call order
+    const RowKind* const kind = row_kind(st[r0], bs[r0], flags, fuse);
+    if (kind) {
+      int64_t cap = table_mode ? table_group_cap(bs[r0].n) : HET_MAX;
+      if (kind->per_sample) cap = std::min<int64_t>(cap, 0x7fffffff / bs[r0].batch);
+      for (int r = r0; r < n_req && cnt < cap; ++r) {
+        if (done[r] || !kind->row_ok(st[r], bs[r]) || !het_same_group(st[r0], bs[r0], st[r], bs[r], shapes) ||
+            (kind->same_group && !kind->same_group(st[r0], st[r])))
+          continue;
+        if (const int f = kind->third_form ? het_third_form(st[r]) : 0) {
+          if (third && f != third) continue;
+          third = f;
         }
+        join(r);
+      }
     }
-    // SDE groups take the table with DPM_TABLE_NOISE only (stage_kernel_table_noise, from one member on); without the flag
-    // they go as in mode 0, beyond HET_MAX members in launches of HET_MAX
+    // (an SDE group of a call without DPM_TABLE_NOISE owns no rows: it goes as in mode 0, beyond HET_MAX members in launches
+    // of HET_MAX)
     const bool sde = (st[r0].flags & DPM_F_NOISE) != 0;
-    const bool tabled = table_mode && (thr || bl ? cnt >= 1 : sde ? noise_rows && cnt >= 1 : cnt >= TABLE_MIN);
-    if (tabled) {
+    if (kind && table_mode && cnt >= kind->min_group && (!sde || noise_rows)) {
       const PairUnits& p = *pair_of(bs[r0].state_dtype, bs[r0].eps_dtype);
-      void* run = rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
-      void* nzs = recs + n_rows * (int64_t)DPM_TABLE_NOISE_BYTES;
-      void* bls = brecs + n_rows * (int64_t)DPM_TABLE_BLEND_BYTES;
-      int rc;
-      if (thr)
-        rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch_thresh(gs.data(), gb.data(), cnt, run, stream);
-      else if (bl)
-        rc = fill ? p.table_fill_blend(gs.data(), gb.data(), cnt, run, bls)
-                  : p.table_launch_blend(gs.data(), gb.data(), cnt, run, bls, stream);
-      else if (sde)
-        rc = fill ? p.table_fill_noise(gs.data(), gb.data(), cnt, run, nzs)
-                  : p.table_launch_noise(gs.data(), gb.data(), cnt, run, nzs, stream);
-      else
-        rc = fill ? p.table_fill(gs.data(), gb.data(), cnt, run) : p.table_launch(gs.data(), gb.data(), cnt, run, stream);
-      if (rc) return rc;
+      void* const run = sec.rows + n_rows * (int64_t)DPM_TABLE_ROW_BYTES;
+      void* const recs = kind->section ? sec.*(kind->section) + n_rows * (int64_t)kind->rec_bytes : nullptr;
+      if (fill) {
+        table_fill_rows(gs.data(), gb.data(), cnt, run);
+        if (kind->fill_recs) kind->fill_recs(gs.data(), gb.data(), cnt, recs);
+      } else if (const int rc = (p.*(kind->launch))(gs.data(), gb.data(), cnt, run, recs, stream)) {
+        return rc;
+      }
       n_rows += cnt;
       n_runs += 1;
       for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
@@ -430,7 +436,9 @@ int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_bu
   if (!bs[0].workspace || reinterpret_cast<uintptr_t>(bs[0].workspace) % 16 != 0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs the table in bs[0].workspace, 16-byte aligned");
   // (a thresholded request 0 that owns a row of a DPM_TABLE_THRESH call needs no workspace of its own)
-  const bool row0 = (o->table_mode & DPM_TABLE_THRESH) && tuning_for(o).multi_fuse != 0 && thresh_row(st, bs, 0);
+  // (st[0] has not passed check_stage_buffers yet: its batch is checked here)
+  const bool row0 = bs[0].batch >= 1 && bs[0].n % bs[0].batch == 0 &&
+                    owns_row(DPM_TABLE_THRESH, st[0], bs[0], o->table_mode, tuning_for(o).multi_fuse != 0);
   if ((st[0].flags & DPM_F_THRESH) && !row0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with DPM_F_THRESH in st[0] (bs[0].workspace is the table)");
   return DPM_OK;

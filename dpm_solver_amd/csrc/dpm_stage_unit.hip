@@ -4,10 +4,12 @@
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
 //               stage_kernel_shapes_noise, stage_kernel_shapes_unipc)
-//   unit C (2): the table-driven heterogeneous launchers (stage_kernel_table, stage_kernel_table_unipc,
-//               stage_kernel_table_noise, stage_thresh_kernel_table) and nothing else -- a unit of its own, so that units A and B compile to the code they compiled to before it existed
-//   unit D (3): the mask-blend rows of the table-driven launch (stage_kernel_table_blend, DPM_TABLE_BLEND) and nothing else --
+//   unit C (2): the launches of the table's plain / UniPC, SDE and thresholded rows (stage_kernel_table, stage_kernel_table_unipc,
+//               stage_kernel_table_noise, stage_thresh_kernel_table) and nothing else -- a unit of its own, so that units A and
+//               B compile to the code they compiled to before it existed
+//   unit D (3): the launch of the table's mask-blend rows (stage_kernel_table_blend, DPM_TABLE_BLEND) and nothing else --
 //               again a unit of its own: units A, B and C compile to the code they compiled to before it existed
+// Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3>"
 #endif
@@ -71,57 +73,37 @@ int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req,
 template int dpm_launch_het_shapes<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
 #endif
 
+// The launches of the table's row kinds (dpm_kernels.hip: kRowKinds), all of one signature: the group's run of rows and, for a
+// kind that has them, its records, both in DEVICE memory.  (DPM_TABLE_FILL needs no dtype: the walk calls table_fill_rows and the
+// kind's record fill itself.)
 #if DPM_UNIT == 2
 template <typename TS, typename TE>
-int dpm_table_fill(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows) {
-  table_fill_rows(st, bs, n_req, rows);
-  return DPM_OK;
-}
-template int dpm_table_fill<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*);
-
-template <typename TS, typename TE>
-int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream) {
+int dpm_table_launch(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void*, void* stream) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
   return launch_table_typed<TS, TE>(st, bs, n_req, rows, s);
 }
-template int dpm_table_launch<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+template int dpm_table_launch<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 
 template <typename TS, typename TE>
-int dpm_table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs) {
-  table_fill_rows(st, bs, n_req, rows);
-  table_fill_noise(st, bs, n_req, recs);
-  return DPM_OK;
-}
-template int dpm_table_fill_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
-
-template <typename TS, typename TE>
-int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream) {
+int dpm_table_launch_noise(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
   return launch_table_noise_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
-template int dpm_table_launch_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+template int dpm_table_launch_noise<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 
 template <typename TS, typename TE>
-int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* stream) {
+int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void*, void* stream) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
   return launch_table_thresh_typed<TS, TE>(st, bs, n_req, rows, s);
 }
-template int dpm_table_launch_thresh<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
+template int dpm_table_launch_thresh<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif
 
 #if DPM_UNIT == 3
 template <typename TS, typename TE>
-int dpm_table_fill_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs) {
-  table_fill_rows(st, bs, n_req, rows);
-  table_fill_blend(st, bs, n_req, recs);
-  return DPM_OK;
-}
-template int dpm_table_fill_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*);
-
-template <typename TS, typename TE>
-int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* rows, void* recs, void* stream) {
+int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
   return launch_table_blend_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
-template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, void*, void*, void*);
+template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

@@ -107,32 +107,22 @@ inline void table_fill_blend(const dpm_stage* st, const dpm_buffers* bs, int n_r
   }
 }
 
-// ---- DPM_TABLE_LAUNCH | DPM_TABLE_BLEND: ONE launch over a group of blend rows and their records (device memory), the launch
-// shape of launch_table_typed
+// ---- DPM_TABLE_LAUNCH | DPM_TABLE_BLEND: ONE launch over a group of blend rows and their records (device memory)
 template <typename TS, typename TE>
 int launch_table_blend_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs,
                              const LaunchCtx& c) {
-  if (n_req < 1 || (int64_t)n_req > table_group_cap(bs[0].n))
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one table launch", n_req);
-  const Tuning tn = tuning_for(bs[0].opts);
-  bool x0 = !tn.force_generic;
-  for (int r = 0; r < n_req; ++r) {
-    if (!blend_row_ok(st[r], bs[r]) || bs[r].n != bs[0].n)
-      return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a stage that is no blend row of this group in a table blend launch");
-    x0 = x0 && x0_prologue_ok(st[r]);
-  }
-  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
-  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  constexpr int U = TableShape<TS, TE>::U, NT = TableShape<TS, TE>::NT;
   const TableRow* tab = static_cast<const TableRow*>(rows);
   const KBlendTab* bls = static_cast<const KBlendTab*>(recs);
   const int64_t n = bs[0].n;
   const uint32_t nreq = (uint32_t)n_req;
-  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
-  with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
-    launch(stage_kernel_table_blend<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, bls, n, nreq,
-           sh.spr, sh.xcd_span);
-  });
-  return launch_status("table blend stage kernel launch failed");
+  return launch_table_rows<TS, TE>(
+      st, bs, n_req, "stage_launch_multi: a stage that is no blend row of this group in a table blend launch",
+      "table blend stage kernel launch failed", [&](int r) { return blend_row_ok(st[r], bs[r]) && bs[r].n == bs[0].n; },
+      [&](auto x0_, auto cfg_, const FusedShape& sh) {
+        launch(stage_kernel_table_blend<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, bls, n, nreq,
+               sh.spr, sh.xcd_span);
+      });
 }
 
 }  // namespace

@@ -205,74 +205,77 @@ inline void table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_r
   }
 }
 
-// ---- DPM_TABLE_LAUNCH | DPM_TABLE_NOISE: ONE launch over a group of SDE rows and their noise records (device memory), the
-// launch shape of launch_table_typed
+// ---- DPM_TABLE_LAUNCH: the skeleton of the streaming table launchers (plain / UniPC, noise and blend rows; the thresholded
+// rows' launch has another shape, dpm_table_thresh.hpp).  The group's size against table_group_cap, the tuning, `row_ok(r)` for
+// every member -- the kind's own argument check: `bad_row` is its error --, the prologue every member allows, the het kernels'
+// launch shape (fused_grid), and ONE launch: `go(x0_, cfg_, shape)` names the kind's kernel for the two compile-time flags.
 template <typename TS, typename TE>
-int launch_table_noise_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs,
-                             const LaunchCtx& c) {
+struct TableShape {
+  static constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
+};
+template <typename TS, typename TE, typename RowOk, typename Go>
+int launch_table_rows(const dpm_stage* st, const dpm_buffers* bs, int n_req, const char* bad_row, const char* failed, RowOk row_ok,
+                      Go go) {
   if (n_req < 1 || (int64_t)n_req > table_group_cap(bs[0].n))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one table launch", n_req);
   const Tuning tn = tuning_for(bs[0].opts);
   bool x0 = !tn.force_generic;
   for (int r = 0; r < n_req; ++r) {
-    if (!(st[r].flags & DPM_F_NOISE) || (st[r].form != DPM_FORM_LIN1 && st[r].form != DPM_FORM_TWO))
-      return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a stage that is no first- / second-order SDE stage in a table noise launch");
+    if (!row_ok(r)) return dpm_set_error(DPM_ERR_ARG, "%s", bad_row);
     x0 = x0 && x0_prologue_ok(st[r]);
   }
-  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
-  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, TableShape<TS, TE>::U, tn, false);
+  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
+  with_flags(x0, cfg, [&](auto x0_, auto cfg_) { go(x0_, cfg_, sh); });
+  return launch_status(failed);
+}
+
+// ---- DPM_TABLE_LAUNCH | DPM_TABLE_NOISE: ONE launch over a group of SDE rows and their noise records (device memory)
+template <typename TS, typename TE>
+int launch_table_noise_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs,
+                             const LaunchCtx& c) {
+  constexpr int U = TableShape<TS, TE>::U, NT = TableShape<TS, TE>::NT;
   const TableRow* tab = static_cast<const TableRow*>(rows);
   const KNoiseTab* nzs = static_cast<const KNoiseTab*>(recs);
   const int64_t n = bs[0].n;
   const uint32_t nreq = (uint32_t)n_req;
-  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
-  with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
-    launch(stage_kernel_table_noise<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, nzs, n, nreq,
-           sh.spr, sh.xcd_span);
-  });
-  return launch_status("table noise stage kernel launch failed");
+  return launch_table_rows<TS, TE>(
+      st, bs, n_req, "stage_launch_multi: a stage that is no first- / second-order SDE stage in a table noise launch",
+      "table noise stage kernel launch failed",
+      [&](int r) { return (st[r].flags & DPM_F_NOISE) && (st[r].form == DPM_FORM_LIN1 || st[r].form == DPM_FORM_TWO); },
+      [&](auto x0_, auto cfg_, const FusedShape& sh) {
+        launch(stage_kernel_table_noise<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, nzs, n, nreq,
+               sh.spr, sh.xcd_span);
+      });
 }
 
 // ---- DPM_TABLE_LAUNCH: ONE launch over the group's run of rows (device memory: a byte copy of what table_fill_rows wrote for
-// the same st / bs).  The prologue and the form set come from the host's records, as in launch_het_typed; the launch shape
-// is the het kernels' (fused_grid).
+// the same st / bs).  The prologue and the form set come from the host's records, as in launch_het_typed.  (The three
+// families are named inside one with_flags body, so unit C's code object lays them out flag pair by flag pair.)
 template <typename TS, typename TE>
 int launch_table_typed(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const LaunchCtx& c) {
-  if (n_req < 1 || (int64_t)n_req > table_group_cap(bs[0].n))
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: %d requests in one table launch", n_req);
-  const Tuning tn = tuning_for(bs[0].opts);
-  bool ms3 = false, unipc = false;
-  bool x0 = !tn.force_generic;
-  for (int r = 0; r < n_req; ++r) {
-    ms3 = ms3 || st[r].form == DPM_FORM_MS3;
-    unipc = unipc || st[r].form == DPM_FORM_UNIPC;
-    x0 = x0 && x0_prologue_ok(st[r]);
-  }
-  if ((st[0].flags & DPM_F_NOISE) || (unipc && ms3))
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: an SDE stage, or UniPC next to third-order stages, in a table launch");
-  constexpr int U = MultiShape<TS, TE>::U, NT = MultiShape<TS, TE>::NT | NT_TABLE;
-  const FusedShape sh = fused_grid<TS, TE>(bs[0].n, n_req, U, tn, false);
+  constexpr int U = TableShape<TS, TE>::U, NT = TableShape<TS, TE>::NT;
   const TableRow* tab = static_cast<const TableRow*>(rows);
   const int64_t n = bs[0].n;
   const uint32_t nreq = (uint32_t)n_req;
-  const bool cfg = st[0].guidance == DPM_GUIDE_CFG;
-  if (unipc) {
-    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
-      launch(stage_kernel_table_unipc<TS, TE, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq, sh.spr,
-             sh.xcd_span);
-    });
-  } else if (ms3) {
-    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
-      launch(stage_kernel_table<TS, TE, HET_FORMS_3, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq,
-             sh.spr, sh.xcd_span);
-    });
-  } else {
-    with_flags(x0, cfg, [&](auto x0_, auto cfg_) {
-      launch(stage_kernel_table<TS, TE, HET_FORMS_2, guide_of(cfg_), spec_of(x0_), U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq,
-             sh.spr, sh.xcd_span);
-    });
-  }
-  return launch_status("table stage kernel launch failed");
+  bool ms3 = false, unipc = false;
+  return launch_table_rows<TS, TE>(
+      st, bs, n_req, "stage_launch_multi: an SDE stage, or UniPC next to third-order stages, in a table launch",
+      "table stage kernel launch failed",
+      [&](int r) {
+        ms3 = ms3 || st[r].form == DPM_FORM_MS3;
+        unipc = unipc || st[r].form == DPM_FORM_UNIPC;
+        return !(st[0].flags & DPM_F_NOISE) && !(unipc && ms3);
+      },
+      [&](auto x0_, auto cfg_, const FusedShape& sh) {
+        constexpr int G = guide_of(cfg_), S = spec_of(x0_);
+        if (unipc)
+          launch(stage_kernel_table_unipc<TS, TE, G, S, U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq, sh.spr, sh.xcd_span);
+        else if (ms3)
+          launch(stage_kernel_table<TS, TE, HET_FORMS_3, G, S, U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq, sh.spr, sh.xcd_span);
+        else
+          launch(stage_kernel_table<TS, TE, HET_FORMS_2, G, S, U, NT>, sh.grid, sh.block, 0, c, tab, n, nreq, sh.spr, sh.xcd_span);
+      });
 }
 
 }  // namespace

@@ -131,6 +131,8 @@ class SlabPool:
         self._sde = bool(sde)            # SDE requests admitted: the tick's calls carry DPM_TABLE_NOISE
         self._thr = bool(thresholding)   # a thresholding solver's pool: the tick's calls carry DPM_TABLE_THRESH
         self._inp = bool(inpaint)        # inpainting requests admitted: the tick's calls carry DPM_TABLE_BLEND
+        self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
+                        | (L.TABLE_BLEND if self._inp else 0))      # ... the flags of every tick's two calls, and its table's size
         self._blends = {}                # handle -> the _Blend of an active inpainting request
         self._brec = np.zeros((slots, 0), dtype=_BLEND)  # [first row of the request, position]: its blend records
         self._bslot = np.full(slots, -1, dtype=np.int64) # per row: the first row of its inpainting request (-1: none), the
@@ -391,8 +393,7 @@ class SlabPool:
             self._cslab = torch.zeros((nS,) + tuple(cond.shape[1:]), dtype=cond.dtype, device=dev)
         # staging: per ring slot a pinned buffer [table | next tick's times | this tick's times | stage array | buffers array]
         # and a device buffer for its first two parts (and one for the third: the copy an admitting tick adds)
-        self._tabb = (L.TABLE_HEADER_BYTES + S * (L.TABLE_ROW_BYTES + (L.TABLE_NOISE_BYTES if self._sde else 0)
-                                                  + (L.TABLE_BLEND_BYTES if self._inp else 0)) + 15) // 16 * 16
+        self._tabb = (L.table_bytes(S, self._tflags) + 15) // 16 * 16
         self._copyb = self._tabb + 4 * nS
         o_cur = (self._copyb + 15) // 16 * 16
         o_st = (o_cur + 4 * nS + 15) // 16 * 16
@@ -596,8 +597,7 @@ class SlabPool:
                 b["blend_b"] = np.where(on & (br["b"] != 0), br["b"] + kb, np.uint64(0))
                 b["mask_period"] = np.where(on, self._bper[rows], 0)
             b["opts"][0] = C.addressof(self._opts)
-            flag = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
-                    | (L.TABLE_BLEND if self._inp else 0))
+            flag = self._tflags
             # next tick's time vector rides with this tick's table
             go = ~last
             t_next = self._times_of(rows[go], idx[go] + 1)

@@ -71,7 +71,7 @@ class BlendSlabs(T.Slabs):
             o = L.LaunchOpts()
             o.per_request_stages = 1
             bufs[0].opts = C.pointer(o)
-            nb = L.TABLE_HEADER_BYTES + R * (L.TABLE_ROW_BYTES + L.TABLE_BLEND_BYTES)
+            nb = L.table_bytes(R, BLEND)
             host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
             out.append((sts, bufs, o, host, torch.empty(nb, dtype=torch.uint8, device=self.dev), R))
         return out

@@ -60,7 +60,7 @@ class SdeSlabs(T.Slabs):
                 o.noise_seed_lo, o.noise_seed_hi = 1000 + r, 7 * r
                 bufs[r].opts = C.pointer(o)
             own[0].per_request_stages = 1
-            nb = L.TABLE_HEADER_BYTES + R * (L.TABLE_ROW_BYTES + L.TABLE_NOISE_BYTES)
+            nb = L.table_bytes(R, NOISE)
             host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
             out.append((sts, bufs, own[0], host, torch.empty(nb, dtype=torch.uint8, device=self.dev), R, own))
         return out

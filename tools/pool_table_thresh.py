@@ -93,7 +93,7 @@ class ThrSlabs:
             o = L.LaunchOpts()
             o.per_request_stages = 1
             bufs[0].opts = C.pointer(o)
-            nb = L.TABLE_HEADER_BYTES + R * L.TABLE_ROW_BYTES
+            nb = L.table_bytes(R, THRESH)
             host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
             out.append((sts, bufs, o, host, torch.empty(nb, dtype=torch.uint8, device=self.dev), R, self.ws.data_ptr()))
         return out
