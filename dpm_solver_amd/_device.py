@@ -124,6 +124,15 @@ def _in_layout_of(t, ref):
     return t if mf is None else _conv(t, t.dtype, mf)
 
 
+def _bind_rescale(st, phi):
+    """Guidance rescale (dpm_solver_amd.cfg_rescale) in a stage record: a classifier-free stage carries DPM_F_CFG_RESCALE and phi
+    in `cg_scale` -- a field the planner writes and no classifier-free kernel reads.  phi = 0 leaves the record as it is."""
+    if phi and st.guidance == L.GUIDE["classifier-free"]:
+        st.flags |= L.F_CFG_RESCALE
+        st.cg_scale = phi
+    return st
+
+
 def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=None, opts=None, coef64=None):
     """One `dpm_stage_launch` on the current stream.  Allocates x_out (and m_out when the stage stores
     its model value) through torch's caching allocator; returns (x_out, m_out).

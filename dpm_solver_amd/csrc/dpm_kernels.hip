@@ -35,6 +35,7 @@ using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*,
 using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 // the one launch over a group's run of table rows and its records (null: the kind has none), both in device memory
 using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+using RescaleFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
@@ -44,11 +45,13 @@ struct PairUnits {
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
   // thresholded rows, unit D's mask-blend rows
   TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend;
+  RescaleFn rescale;  // unit E's guidance-rescale stage (DPM_F_CFG_RESCALE)
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
-   dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>},
+   dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
+   dpm_launch_rescale<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -81,6 +84,25 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
   if (b->noise_sample0 != 0 && !base_ok)
     return fail(DPM_ERR_ARG, "stage_launch: noise_sample0=%d (honoured by the SDE rows of a DPM_TABLE_NOISE call only)",
                 b->noise_sample0);
+  if (st->flags & DPM_F_CFG_RESCALE) {  // guidance rescale (include/dpm_hip.h): one workgroup per sample, stage_rescale_kernel
+    const int64_t per = b->n / b->batch;
+    if (st->guidance != DPM_GUIDE_CFG)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE is valid under classifier-free guidance only (guidance %d)", st->guidance);
+    if (b->n > 0 && per < 2)  // (an empty batch is DPM_OK below, as for every stage; its record is still checked)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE needs samples of at least 2 elements (got %lld)", (long long)per);
+    if (!(st->cg_scale > 0.f && st->cg_scale <= 1.f))
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE with phi=%g (dpm_stage.cg_scale), which is not in (0, 1]", (double)st->cg_scale);
+    if (st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with thresholding, mask blend or noise (flags %u)", st->flags);
+    if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE on a DPM_FORM_UNIPC stage");
+    // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
+    if (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_DENOISE) return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
+    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with a double state (no double rescale kernel)");
+    if (b->eps_stride != 0 && b->eps_stride != per)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with eps_stride=%lld (a channel slice of a wider output)",
+                  (long long)b->eps_stride);
+  }
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -154,6 +176,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with device-resident coefficients");
   if (dyn && st->form == DPM_FORM_UNIPC)
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with device-resident coefficients");
+  if (dyn && (st->flags & DPM_F_CFG_RESCALE))
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with device-resident coefficients");
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -164,6 +188,7 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   }
   const PairUnits* p = pair_of(sd, ed);
   if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
+  if (st->flags & DPM_F_CFG_RESCALE) return p->rescale(st, &bb, stream, ev_start, ev_stop);
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused

@@ -1,5 +1,5 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled twenty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3> (__graft_entry__.py).
+// translation unit: compiled twenty-five times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
@@ -9,14 +9,19 @@
 //               B compile to the code they compiled to before it existed
 //   unit D (3): the launch of the table's mask-blend rows (stage_kernel_table_blend, DPM_TABLE_BLEND) and nothing else --
 //               again a unit of its own: units A, B and C compile to the code they compiled to before it existed
+//   unit E (4): the launch of a guidance-rescale stage (stage_rescale_kernel, DPM_F_CFG_RESCALE; dpm_rescale_kernel.hpp, which
+//               no other unit includes) and nothing else -- units A to D compile to the code they compiled to before it existed
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
 #endif
 #include "dpm_device.hpp"
+#if DPM_UNIT == 4
+#include "dpm_rescale_kernel.hpp"
+#endif
 
 #include <tuple>
 #include <utility>
@@ -106,4 +111,13 @@ int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req
   return launch_table_blend_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
 template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+#endif
+
+#if DPM_UNIT == 4
+template <typename TS, typename TE>
+int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
+  return launch_rescale_typed<TS, TE>(st, b, s);
+}
+template int dpm_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 #endif

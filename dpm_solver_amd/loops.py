@@ -46,7 +46,8 @@ def run_plan_group(self, plan, xs, sd, cfg):
     mf = DV._mf_of(first[0][0]) if first[0][0].shape == shape else None
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
-    key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit))
+    key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
+           self._rescale_phi())
     grp = None if capturing else self._fast_groups.get(key)
     if grp is None:
         runs = [_FastRun(self, plan, shape, sd, device, cfg, mf) for _ in range(R)]
@@ -141,7 +142,8 @@ def run_plan_fast(self, plan, x, sd, cfg):
     mf = DV._mf_of(first[0]) if first[0].shape == x.shape else None
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
-    key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit))
+    key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
+           self._rescale_phi())
     fr = None if capturing else self._fast.get(key)      # a captured graph bakes its buffers in: give it its own
     if fr is None:
         fr = _FastRun(self, plan, x.shape, sd, device, cfg, mf)
@@ -196,6 +198,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     device = x.device
     sd = self._sdtype(x)
     cfg = self._wrapped is not None and self._wrapped.effective_guidance == "classifier-free"
+    self._check_rescale(sd=sd, blend=isinstance(cxt, MaskBlend))    # the one check of a run (its loops do not repeat it)
     # denoise_to_zero evaluates the data prediction at a (1,)-shaped time (ref :1236: `torch.ones((1,)) * t_0`): on a
     # continuous schedule its alpha_t / sigma_t are then dimensioned fp32 tensors and the RESULT of a half-precision run
     # is fp32 (on a discrete schedule every run is fp32 anyway).  That last stage runs in fp32 in the general loop below.
@@ -239,7 +242,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     tmp, tmp2 = None, None
     hist = [None] * max(plan.slots, 1)
     for i, ps in enumerate(plan.stages):
-        st = ps.copy()                # launches may edit flags
+        st = self._prep_stage(ps.copy())                # (a copy: launches may edit flags)
         from_tmp = st.xe_src == L.SRC_TMP
         xe = tmp if from_tmp else state
         outs = self._network(xe, None, None, x_in2=tmp2 if from_tmp else state2,

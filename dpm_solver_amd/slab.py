@@ -187,6 +187,8 @@ class SlabPool:
                                       "sample()")
         if return_intermediate:
             raise NotImplementedError("slab pool: return_intermediate is not supported; sample it with sample()")
+        s._check_rescale("the slab pool (request_pool(slots=...)) -- the table has no row kind for rescale stages (a "
+                         "follow-up); use request_pool() without slots")
 
     def _check_state(self, x):
         """the refusals that depend on x's dtype, then the device requirement and the pool's own checks"""

@@ -165,6 +165,26 @@ class DPM_Solver:
             return L.MODEL[w.model_type], L.GUIDE[w.effective_guidance], float(w.guidance_scale)
         return L.MODEL["noise"], L.GUIDE["uncond"], 1.0
 
+    def _rescale_phi(self):
+        """phi of the wrapper's guidance rescale (dpm_solver_amd.cfg_rescale); 0.0: none, every launch as without it"""
+        return self._wrapped.rescale_phi if self._wrapped is not None else 0.0
+
+    def _check_rescale(self, what=None, sd=None, blend=False):
+        """the combinations guidance rescale is not built with: `what` names a sampler that has none; else
+        the run's corrector and state dtype.  Called where a run starts (run_plan, the pool's _admit, the samplers' own
+        checks) and by _run_stage, whose state dtype may have been promoted by the first evaluation; a thresholded stage is
+        refused where it is bound (_prep_stage)."""
+        if not self._rescale_phi():
+            return
+        if what is not None:
+            raise NotImplementedError("guidance rescale (cfg_rescale): %s" % what)
+        if blend:
+            raise NotImplementedError("guidance rescale (cfg_rescale): a MaskBlend corrector -- the rescale kernel has no "
+                                      "mask-blend epilogue (a follow-up)")
+        if sd is torch.float64:
+            raise NotImplementedError("guidance rescale (cfg_rescale): double-precision states (there is no double rescale "
+                                      "kernel)")
+
     def _sdtype(self, x):
         if self._state_dtype is not None:
             return self._state_dtype
@@ -343,16 +363,23 @@ class DPM_Solver:
                 st.flags |= L.F_THRESH
                 st.thr_ratio = float(self.dynamic_thresholding_ratio)
                 st.thr_max = float(self.thresholding_max_val)
+        phi = self._rescale_phi()
+        if phi:
+            if st.flags & L.F_THRESH:
+                raise NotImplementedError("guidance rescale (cfg_rescale): correcting_x0_fn='dynamic_thresholding' -- the "
+                                          "thresholding kernels have no rescale (a follow-up)")
+            DV._bind_rescale(st, phi)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
         """outs = (e0, e1, g) fresh network outputs.  Handles a *callable* correcting_x0_fn by splitting the
         stage: prologue kernel -> user function (opaque torch) -> combination kernel."""
+        self._check_rescale(sd=sd)          # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
         e0, e1, g = outs if sd is not torch.float64 else self._cfg_pre(outs, sd)
         if self._user_x0 is not None and (st.flags & L.F_TO_X0):
             s1 = st.copy()
             s1.form = L.FORM_DENOISE
-            s1.flags = L.F_TO_X0
+            s1.flags = L.F_TO_X0 | (st.flags & L.F_CFG_RESCALE)
             x0, _ = DV._launch_stage(s1, None, xe if xe is not None else x, e0, e1, g, None, None, sd, want_m=False,
                                   opts=self._opts_ptr(), coef64=coef64)
             x0 = self._call_x0(x0, t_eval_t)                                             # ref :440-441
@@ -732,6 +759,8 @@ class DPM_Solver:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
+            self._check_rescale("the slab pool (request_pool(slots=...)) -- the table has no row kind for rescale stages (a "
+                                "follow-up); use request_pool() without slots")
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")

@@ -7,10 +7,17 @@ blend (ref :326-330) and the classifier-guidance term (ref :315-321) into the pr
 kernel instead of running them as separate elementwise passes.  The network itself (and the autograd
 call through the classifier) stays an opaque PyTorch-ROCm call on the current stream.
 """
+import copy
+import numbers
+
 import torch
 
 
 class WrappedModel:
+    # guidance rescale (Lin et al. 2023, section 3.4; diffusers' `guidance_rescale`): phi in [0, 1], set through
+    # dpm_solver_amd.cfg_rescale -- model_wrapper's signature is the reference's.  0 = off: every bit as without it.
+    guidance_rescale = 0.0
+
     def __init__(self, model, noise_schedule, model_type, model_kwargs, guidance_type, condition,
                  unconditional_condition, guidance_scale, classifier_fn, classifier_kwargs):
         self.model = model
@@ -34,6 +41,12 @@ class WrappedModel:
                 self.guidance_scale == 1. or self.unconditional_condition is None):
             return "classifier-free"
         return "uncond"
+
+    @property
+    def rescale_phi(self):
+        """phi of the guidance rescale this wrapper asks the stage kernels for; 0.0 = none (phi 0, or no classifier-free blend)"""
+        phi = float(self.guidance_rescale)
+        return phi if phi != 0.0 and self.effective_guidance == "classifier-free" else 0.0
 
     def get_model_input_time(self, t_continuous):
         """ref :271-280"""
@@ -100,10 +113,39 @@ class WrappedModel:
         if eff == "classifier":                                   # ref :315-321
             _, sigma_t = self.noise_schedule.device_alpha_sigma(t_continuous)
             return to_noise(e0) - self.guidance_scale * expand_dims(sigma_t, dims) * g
+        if eff == "classifier-free" and self.rescale_phi != 0.0:
+            # guidance rescale: blend and statistics on the RAW outputs (the paper, diffusers), the conversion afterwards; the
+            # per-sample standard deviations in float64, their ratio rounded once to the outputs' dtype (include/dpm_hip.h)
+            phi = self.rescale_phi
+            half = e0.dtype in (torch.float16, torch.bfloat16)
+            if half and mt != "noise":                   # such outputs meet the fp32 schedule first without rescale (ref :290-298):
+                e0, e1 = e0.float(), e1.float()          # their blend is fp32 here too
+            g = e1 + self.guidance_scale * (e0 - e1)     # a noise network: in its own dtype, like the blend without rescale (ref :330)
+            if half:
+                g = g.float()                            # nothing after the blend is rounded to half (as in the stage kernel)
+            axes = list(range(1, dims))
+            f = (e0.double().std(dim=axes, keepdim=True) / g.double().std(dim=axes, keepdim=True)).to(g.dtype)
+            return to_noise(phi * (g * f) + (1. - phi) * g)
         if eff == "classifier-free":                              # ref :326-330
             nu, nc = to_noise(e1), to_noise(e0)
             return nu + self.guidance_scale * (nc - nu)
         return to_noise(e0)
+
+
+def cfg_rescale(model_fn, phi):
+    """(extension) A copy of the classifier-free wrapper `model_fn` with guidance rescale phi (Lin et al. 2023, "Common
+    Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4; the `guidance_rescale` of diffusers pipelines): the
+    guided output is rescaled so that its per-sample standard deviation matches the conditional output's, and blended with the
+    un-rescaled one -- phi * rescaled + (1 - phi) * guided.  What v-prediction / zero-terminal-SNR checkpoints need at the
+    usual guidance scales.  DPM_Solver runs it inside the stage kernel (DPM_F_CFG_RESCALE); phi = 0 changes nothing."""
+    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
+        raise ValueError("cfg_rescale: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
+                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
+    if isinstance(phi, bool) or not isinstance(phi, numbers.Real) or not (0.0 <= float(phi) <= 1.0):
+        raise ValueError("cfg_rescale: phi must be a real number in [0, 1], got %r" % (phi,))
+    out = copy.copy(model_fn)
+    out.guidance_rescale = float(phi)
+    return out
 
 
 def model_wrapper(model, noise_schedule, model_type="noise", model_kwargs={}, guidance_type="uncond",

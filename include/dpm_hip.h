@@ -79,11 +79,14 @@ extern "C" {
    211 DPM_TABLE_BLEND (a flag on table_mode), DPM_TABLE_BLEND_BYTES / DPM_SIZEOF_TABLE_BLEND: mask-blend stages (DPM_F_BLEND,
    inpainting / DiffEdit) in the table -- every qualifying DPM_F_BLEND request owns a row and a blend record behind the rows,
    a group of them is ONE stage_kernel_table_blend launch (see "Table mode"; no entry point added, no struct changed size).
+   212 DPM_F_CFG_RESCALE: classifier-free guidance with guidance rescale (Lin et al. 2023, section 3.4; diffusers'
+   guidance_rescale) in ONE stage launch -- a kernel that owns a whole sample, takes the two per-sample standard deviations,
+   then runs the usual prologue, update and stores (see DPM_F_CFG_RESCALE; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 211
+#define DPM_HIP_VERSION 212
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -177,6 +180,34 @@ enum {
                                 caller of return_intermediate wants) instead of a second copy of x_out; never set by the
                                 planner.  Such a stage runs on its own in a multi-request launch                          */
 
+#define DPM_F_CFG_RESCALE 1024u /* version 212, with guidance == DPM_GUIDE_CFG only (else DPM_ERR_ARG); never set by the planner.
+                                  Guidance rescale: the guided output is rescaled so that its per-sample standard deviation
+                                  matches the conditional output's, and blended with the un-rescaled one by phi.  With the flag
+                                  dpm_stage.cg_scale carries phi in (0, 1] (under CFG the planner writes that field and nothing
+                                  reads it; the caller overwrites it).  For each sample b of the launch, P = n / batch elements,
+                                  s = cfg_scale:
+                                    o_c, o_u = e0, e1 of the sample as fp32             (the RAW outputs: before any conversion)
+                                    g   = o_u + s * (o_c - o_u)      fp32, one rounding per operation; a 2-byte noise-prediction
+                                                                     network: each of the three operations rounded through the
+                                                                     network's dtype, as the flag-less blend is
+                                    d_c = (double)o_c - (double)o_c[0];  d_g = (double)g - (double)g[0]     (the sample's first element)
+                                    S1 = sum d, S2 = sum d * d       in double, no fused multiply-add, any summation order
+                                    var = max((S2 - S1 * S1 / P) / (P - 1), 0);  std = sqrt(var)     in double (unbiased: torch.std)
+                                    f   = (float)(std_c / std_g)     one double division, one rounding to fp32
+                                    r   = phi * (g * f) + (1.f - phi) * g               fp32, one rounding per operation
+                                    eps = noise prediction of the raw output r (x_start / v / score conversion), then
+                                          DPM_F_TO_X0, the update form and the stores as without the flag, all fp32: r is
+                                          an fp32 value whatever the network's dtype, nothing after the blend is rounded to it
+                                  The statistics are those of the raw outputs (the paper, diffusers): for an x_start / v / score
+                                  network the blend therefore precedes the conversion, which it follows without the flag.  A
+                                  sample with std_g == 0 gets what IEEE gives (inf or NaN in every element), like torch.
+                                  DPM_ERR_ARG: P < 2 (an empty batch, n == 0, is DPM_OK and launches nothing, as for every
+                                  stage); phi outside (0, 1] or NaN; the flag without DPM_GUIDE_CFG; an unknown form.
+                                  DPM_ERR_UNSUPPORTED (this version): DPM_F_THRESH, DPM_F_BLEND, DPM_F_NOISE; DPM_FORM_UNIPC; a
+                                  double state; eps_stride other than 0 or P; device-resident coefficients.  No output byte is
+                                  written in any error case.  One workgroup per sample (stage_rescale_kernel); such a stage runs
+                                  on its own in a multi-request launch, in every mode of dpm_stage_launch_multi */
+
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
 
@@ -200,7 +231,7 @@ typedef struct dpm_stage {
   float alpha_e;       /* alpha(t_eval)                                                          */
   float sigma_e;       /* sigma(t_eval)                                                          */
   float cfg_scale;     /* guidance_scale as fp32 (ref :330)                                      */
-  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321)                         */
+  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi */
   float cx, c0, c1, c2; /* update coefficients, reference association (see kernels)              */
   float k[5];          /* difference-quotient scalars: 1/r0, 1/r1, ...                           */
   float thr_ratio;     /* dynamic_thresholding_ratio                                             */
@@ -462,7 +493,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance and DPM_F_STORE_XC are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC and DPM_F_CFG_RESCALE are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
