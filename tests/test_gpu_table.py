@@ -44,14 +44,17 @@ def _stream():
 
 
 class TableCall:
-    """the arrays of one per-request-stage call on guarded GPU operands, and its table: a host tensor and a guarded device one"""
+    """the arrays of one per-request-stage call on guarded GPU operands, and its table: a host tensor and a guarded device one.
+    `flags` (DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND) is the section layout -- the table is sized for the record
+    sections those flags put behind the rows -- and the flag word tick() puts on both of its calls"""
 
-    def __init__(self, devs):
-        self.devs, self.R = devs, len(devs)
+    def __init__(self, devs, flags=0):
+        self.devs, self.R, self.flags = devs, len(devs), flags
         self.st = (L.Stage * self.R)(*[d.st for d in devs])
         self.bs = (L.Buffers * self.R)(*[d.b for d in devs])
         self.opts = devs[0].opts
-        nbytes = L.TABLE_HEADER_BYTES + self.R * L.TABLE_ROW_BYTES
+        self.ws0 = devs[0].b.workspace                          # request 0's own workspace: what a mode-0 call hands it
+        nbytes = L.table_bytes(self.R, flags)
         self.host = torch.full((nbytes,), 0x5A, dtype=torch.uint8)
         self.arena = torch.full((nbytes + 2 * TABLE_GUARD,), 0xC3, dtype=torch.uint8, device=DEV)
         self.dev = self.arena[TABLE_GUARD:TABLE_GUARD + nbytes]
@@ -59,16 +62,17 @@ class TableCall:
 
     def call(self, mode, table=None):
         self.opts.table_mode = mode
-        self.bs[0].workspace = None if table is None else table.data_ptr()
+        self.bs[0].workspace = self.ws0 if table is None else table.data_ptr()
         rc = L.lib.dpm_stage_launch_multi(self.st, self.bs, self.R, _stream())
         self.opts.table_mode = 0
         assert rc == 0, (rc, L.lib.dpm_last_error())
 
-    def tick(self):
-        """FILL into the host tensor, one copy to the device, LAUNCH"""
-        self.call(L.TABLE_FILL, self.host)
+    def tick(self, flags=None):
+        """FILL into the host tensor, one copy to the device, LAUNCH; both calls with `flags` (default: the layout's)"""
+        flags = self.flags if flags is None else flags
+        self.call(L.TABLE_FILL | flags, self.host)
         self.dev.copy_(self.host, non_blocking=True)
-        self.call(L.TABLE_LAUNCH, self.dev)
+        self.call(L.TABLE_LAUNCH | flags, self.dev)
         torch.cuda.synchronize()
 
     def mode0(self):
