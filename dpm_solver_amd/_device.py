@@ -124,12 +124,26 @@ def _in_layout_of(t, ref):
     return t if mf is None else _conv(t, t.dtype, mf)
 
 
+def _cfg_fields(scale, phi, sigma_e, flags):
+    """The guidance fields of a classifier-free stage record for a wrapper of guidance scale `scale` and guidance rescale `phi`
+    (scalars or numpy arrays, one entry per record; `sigma_e`, `flags`: the record's own): (cfg_scale, cg_scale, flags).
+    cfg_scale is the scale as fp32 and, without rescale, cg_scale its fp32 product with sigma_e (the planner: a field no
+    classifier-free kernel reads); with phi != 0 the record carries DPM_F_CFG_RESCALE and phi in `cg_scale`.  The one statement
+    of that conversion: _bind_rescale and the slab pool's per-request guidance both go through it."""
+    cs = np.asarray(scale, dtype=np.float64).astype(np.float32)
+    ph = np.asarray(phi, dtype=np.float64).astype(np.float32)
+    fl = np.asarray(flags, dtype=np.uint32)
+    on = ph != 0
+    cg = np.where(on, ph, cs * np.asarray(sigma_e, dtype=np.float32))
+    return cs, cg, np.where(on, fl | np.uint32(L.F_CFG_RESCALE), fl & ~np.uint32(L.F_CFG_RESCALE))
+
+
 def _bind_rescale(st, phi):
     """Guidance rescale (dpm_solver_amd.cfg_rescale) in a stage record: a classifier-free stage carries DPM_F_CFG_RESCALE and phi
     in `cg_scale` -- a field the planner writes and no classifier-free kernel reads.  phi = 0 leaves the record as it is."""
     if phi and st.guidance == L.GUIDE["classifier-free"]:
-        st.flags |= L.F_CFG_RESCALE
-        st.cg_scale = phi
+        _, cg, fl = _cfg_fields(st.cfg_scale, phi, st.sigma_e, st.flags)
+        st.cg_scale, st.flags = float(cg), int(fl)
     return st
 
 

@@ -51,6 +51,7 @@ TABLE_FILL, TABLE_LAUNCH = 1, 2           # dpm_launch_opts.table_mode (version 
 TABLE_NOISE = 4                           # ... a flag on either: SDE stages take rows and noise records too (version 209)
 TABLE_THRESH = 8                          # ... another: thresholded stages of small samples take rows too (version 210)
 TABLE_BLEND = 32                          # ... another: DPM_F_BLEND stages take rows and blend records too (version 211)
+TABLE_RESCALE = 128                       # ... another: DPM_F_CFG_RESCALE stages take rows too, no records (version 213)
 THR_ROW_MAX = 12288                       # elements of the largest sample a thresholded row holds (THR_CHUNK_MAX, csrc)
 TABLE_MAGIC = 0x4c425444
 SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
@@ -298,8 +299,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 212:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 212 -- stale library, rebuild"
+if lib.dpm_version() < 213:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 213 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16

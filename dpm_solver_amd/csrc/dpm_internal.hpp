@@ -64,6 +64,9 @@ int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req
 // (unit E, DPM_F_CFG_RESCALE) one classifier-free stage with guidance rescale: one workgroup per sample (stage_rescale_kernel)
 template <typename TS, typename TE>
 int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+// (unit E, DPM_TABLE_RESCALE) DPM_F_CFG_RESCALE rows -- rows like any other, no records --, one workgroup per sample
+template <typename TS, typename TE>
+int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

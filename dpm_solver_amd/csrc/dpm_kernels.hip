@@ -43,15 +43,15 @@ struct PairUnits {
   HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
-  // thresholded rows, unit D's mask-blend rows
-  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend;
+  // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows
+  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale;
   RescaleFn rescale;  // unit E's guidance-rescale stage (DPM_F_CFG_RESCALE)
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
-   dpm_launch_rescale<TS, TE>},
+   dpm_table_launch_rescale<TS, TE>, dpm_launch_rescale<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -323,6 +323,9 @@ const RowKind kRowKinds[] = {
     // SDE requests, from ONE member on: a row's noise_sample0 has no other way to the kernel
     {DPM_TABLE_NOISE, sde_row_ok, nullptr, false, false, 1, &TableSections::noise, DPM_TABLE_NOISE_BYTES, table_fill_noise,
      &PairUnits::table_launch_noise},
+    // guidance-rescale requests (DPM_F_CFG_RESCALE; dpm_table_rescale.hpp), from ONE member on: the alternative is a launch of
+    // one workgroup per sample per request.  Any of LIN1 / TWO / MS3 / DENOISE, any phi and guidance scale in one group.
+    {DPM_TABLE_RESCALE, rescale_row_ok, nullptr, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_rescale},
     // every other fusable request, in every call: groups of 2..HET_MAX keep the kernarg records (stage_kernel_het needs no
     // dependent load in front of its tile's own), larger ones take the table.  An SDE group of a call without DPM_TABLE_NOISE
     // is gathered here too -- het_same_group keeps it apart from the ODE groups -- and owns no rows (stage_launch_multi_het).
@@ -356,7 +359,7 @@ bool owns_row(int flag, const dpm_stage& st, const dpm_buffers& b, int flags, bo
 // smaller group and every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this
 // one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
-  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
+  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE);
   const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0;
   table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
@@ -450,7 +453,7 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND);
+  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
                          "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND)", o->table_mode);

@@ -10,7 +10,8 @@
 //   unit D (3): the launch of the table's mask-blend rows (stage_kernel_table_blend, DPM_TABLE_BLEND) and nothing else --
 //               again a unit of its own: units A, B and C compile to the code they compiled to before it existed
 //   unit E (4): the launch of a guidance-rescale stage (stage_rescale_kernel, DPM_F_CFG_RESCALE; dpm_rescale_kernel.hpp, which
-//               no other unit includes) and nothing else -- units A to D compile to the code they compiled to before it existed
+//               no other unit includes) and of the table's guidance-rescale rows (stage_rescale_kernel_table, DPM_TABLE_RESCALE;
+//               dpm_table_rescale.hpp) and nothing else -- units A to D compile to the code they compiled to before it existed
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4>"
@@ -21,6 +22,7 @@
 #include "dpm_device.hpp"
 #if DPM_UNIT == 4
 #include "dpm_rescale_kernel.hpp"
+#include "dpm_table_rescale.hpp"
 #endif
 
 #include <tuple>
@@ -120,4 +122,11 @@ int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, 
   return launch_rescale_typed<TS, TE>(st, b, s);
 }
 template int dpm_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
+
+template <typename TS, typename TE>
+int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void*, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_rescale_typed<TS, TE>(st, bs, n_req, rows, s);
+}
+template int dpm_table_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

@@ -30,8 +30,8 @@ whose output row depends only on its input row, its time and its condition row. 
 chosen by batch size, batch statistics) is outside this.  Occupancy below S wastes network work in proportion: every tick
 evaluates all S rows; compaction of a sparse slab is out of scope.
 
-Admitted: multistep ODE requests (`submit`) and UniPC requests (`submit_unipc`), unconditional or classifier-free (the guidance
-scale stays the wrapper's; conditions may be per request).  Everything else is refused with NotImplementedError: see `submit`.
+Admitted: multistep ODE requests (`submit`) and UniPC requests (`submit_unipc`), unconditional or classifier-free (conditions
+and the guidance scale may be per request: see "Per-request guidance" below).  Everything else is refused with NotImplementedError: see `submit`.
 
 `request_pool(slots=S, sde=True)` also admits SDE-DPM-Solver++ requests: `submit(x, ..., sde=True, seed=...)`, with
 `RequestPool.submit`'s checks and seed rules.  The tick's two calls then carry DPM_TABLE_NOISE: every SDE row is a row of the
@@ -78,8 +78,33 @@ for any b, whichever rows it landed in.  Refused with NotImplementedError: `blen
 `MaskBlend(x0=..., noise=None)` (it draws torch.randn per call: pass `noise=`); `blend=` with `sde=True` (the table has no
 blend behind the noise epilogue); `inpaint=True` with `thresholding=True` (the thresholded rows have no blend); `submit_unipc`
 takes no blend.  Without `inpaint=True` every pool behaves and refuses as before.
+
+`request_pool(slots=S, rescale=True)` is the slab pool that admits guidance-rescale requests (`dpm_solver_amd.cfg_rescale`;
+v-prediction / zero-terminal-SNR checkpoints at the usual guidance scales): an effectively classifier-free wrapper, with or
+without a phi of its own.  The tick's two calls carry DPM_TABLE_RESCALE: every row whose record carries DPM_F_CFG_RESCALE is a
+row of the table whatever their number -- ONE stage_rescale_kernel_table launch, one workgroup per row, the kernel of the
+request's own launch -- beside the plain family's, which rows with phi 0 take; a tick stays one network call, one copy and one
+launch per family present.  A rescale row is a row and nothing else: no record section.  The DENOISE stage of
+denoise_to_zero is a rescale row too.  At its first submit such a pool refuses a sample of fewer than 8 elements, one whose
+element count is no multiple of 8, and one whose row is no multiple of 16 bytes (the row could not take the table).  Refused
+with NotImplementedError: `rescale=True` with `sde=True`, `thresholding=True` or `inpaint=True` (the rescale kernel has none of
+those epilogues); `submit_unipc` on a solver whose wrapper carries phi.  Without `rescale=True` a slab pool refuses a
+`cfg_rescale` solver as before.
+
+Per-request guidance: the kernels read the guidance scale and phi from each row's own record and no grouping key compares
+them, so in ANY classifier-free slab pool `submit(..., guidance_scale=g)` / `submit_unipc(..., guidance_scale=g)` take the
+request's own scale, and in a `rescale=True` pool `submit(..., guidance_rescale=phi)` its own phi in [0, 1]; the default for
+both is the wrapper's.  The values are kept per row; every tick writes them over the gathered stage records, vectorised like
+the blend fields, as the planner and the binder write them for a wrapper of that scale and phi (`_device._cfg_fields`): fp32(g)
+in cfg_scale, DPM_F_CFG_RESCALE and phi in cg_scale -- phi 0 clears the flag: a plain row.  `guidance_scale=1.0` is refused
+(NotImplementedError): a wrapper of scale 1 evaluates the conditional branch alone, without a blend, which a row of a
+[2S, ...] slab cannot reproduce.  Either argument on a pool whose wrapper is not classifier-free, a g that is no real number
+and a phi outside [0, 1] are ValueError; `guidance_rescale=` outside a `rescale=True` pool is NotImplementedError.
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
+guidance scale and `cfg_rescale(..., phi)`, for any b, whichever rows it landed in.
 """
 import ctypes as C
+import numbers
 
 import numpy as np
 import torch
@@ -112,7 +137,7 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide")
 
 
 class _Blend:
@@ -123,7 +148,7 @@ class _Blend:
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False):
+    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
@@ -131,8 +156,13 @@ class SlabPool:
         self._sde = bool(sde)            # SDE requests admitted: the tick's calls carry DPM_TABLE_NOISE
         self._thr = bool(thresholding)   # a thresholding solver's pool: the tick's calls carry DPM_TABLE_THRESH
         self._inp = bool(inpaint)        # inpainting requests admitted: the tick's calls carry DPM_TABLE_BLEND
+        self._rsc = bool(rescale)        # guidance-rescale requests admitted: the tick's calls carry DPM_TABLE_RESCALE
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
-                        | (L.TABLE_BLEND if self._inp else 0))      # ... the flags of every tick's two calls, and its table's size
+                        | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
+                        | (L.TABLE_RESCALE if self._rsc else 0))
+        self._gon = np.zeros(slots, dtype=bool)          # per row: does its request bring its own guidance (submit's
+        self._gs = np.zeros(slots, dtype=np.float32)     # guidance_scale= / guidance_rescale=)?  its scale, its phi
+        self._gphi = np.zeros(slots, dtype=np.float32)
         self._blends = {}                # handle -> the _Blend of an active inpainting request
         self._brec = np.zeros((slots, 0), dtype=_BLEND)  # [first row of the request, position]: its blend records
         self._bslot = np.full(slots, -1, dtype=np.int64) # per row: the first row of its inpainting request (-1: none), the
@@ -187,8 +217,31 @@ class SlabPool:
                                       "sample()")
         if return_intermediate:
             raise NotImplementedError("slab pool: return_intermediate is not supported; sample it with sample()")
-        s._check_rescale("the slab pool (request_pool(slots=...)) -- the table has no row kind for rescale stages (a "
-                         "follow-up); use request_pool() without slots")
+        if not self._rsc:
+            s._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built with "
+                             "request_pool(slots=..., rescale=True) only")
+
+    def _guidance(self, scale, phi):
+        """the request's own (guidance scale, phi) of submit's guidance_scale= / guidance_rescale=, checked; None: the wrapper's"""
+        if scale is None and phi is None:
+            return None
+        w = self._s._wrapped
+        if w is None or w.effective_guidance != "classifier-free":
+            raise ValueError("slab pool: guidance_scale / guidance_rescale belong to a classifier-free wrapper (with an "
+                             "unconditional condition and a guidance scale other than 1)")
+        for name, v in (("guidance_scale", scale), ("guidance_rescale", phi)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real) or not np.isfinite(float(v))):
+                raise ValueError("slab pool: %s must be a real number, got %r" % (name, v))
+        if phi is not None and not (0.0 <= float(phi) <= 1.0):
+            raise ValueError("slab pool: guidance_rescale must be in [0, 1], got %r" % (phi,))
+        if scale is not None and float(scale) == 1.0:
+            raise NotImplementedError("slab pool: guidance_scale=1.0 -- a wrapper of scale 1 evaluates the conditional branch "
+                                      "alone, without a blend, which a row of a classifier-free slab cannot reproduce")
+        if phi is not None and not self._rsc:
+            raise NotImplementedError("slab pool: guidance_rescale= -- rescale stages take the table in a pool built with "
+                                      "request_pool(slots=..., rescale=True) only")
+        return (float(w.guidance_scale) if scale is None else float(scale),
+                float(self._s._rescale_phi()) if phi is None else float(phi))
 
     def _check_state(self, x):
         """the refusals that depend on x's dtype, then the device requirement and the pool's own checks"""
@@ -203,6 +256,12 @@ class SlabPool:
             per = x.numel() // x.shape[0]
             if per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
                 raise NotImplementedError("slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is "
+                                          "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
+                                          % per)
+        if self._rsc and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
+            per = x.numel() // x.shape[0]
+            if per < 8 or per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
+                raise NotImplementedError("slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is "
                                           "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
                                           % per)
         if self._thr and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
@@ -224,7 +283,8 @@ class SlabPool:
 
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
-               condition=None, unconditional_condition=None, seed=None, generator=None, blend=None):
+               condition=None, unconditional_condition=None, seed=None, generator=None, blend=None, guidance_scale=None,
+               guidance_rescale=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -235,8 +295,12 @@ class SlabPool:
         `sde=True` (a pool built with sde=True): an SDE-DPM-Solver++ request -- `sample_sde`'s arguments, checks and seed rules
         (`seed`, or one draw from `generator` / torch's default CPU generator, made here), as `RequestPool.submit`.
         `blend=mb` (a pool built with inpaint=True): an inpainting / DiffEdit request -- the result of `sample()` on a solver
-        built with correcting_xt_fn=mb; see the module docstring for the forms of `MaskBlend` admitted."""
+        built with correcting_xt_fn=mb; see the module docstring for the forms of `MaskBlend` admitted.
+        `guidance_scale=g` (a classifier-free pool): the request's own guidance scale -- the result of `sample()` on a solver
+        whose wrapper has that scale; g = 1.0 is refused.  `guidance_rescale=phi` (a pool built with rescale=True): the request's
+        own phi in [0, 1] -- the result of `sample()` under `cfg_rescale(model_fn, phi)`.  Default for both: the wrapper's."""
         s = self._s
+        guide = self._guidance(guidance_scale, guidance_rescale)
         if blend is not None:
             if not self._inp:
                 raise NotImplementedError("slab pool: blend= -- mask-blend stages take the table in a pool built with "
@@ -264,14 +328,16 @@ class SlabPool:
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   solver_type, sde=bool(sde))
-        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend)
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
-                     condition=None, unconditional_condition=None):
+                     condition=None, unconditional_condition=None, guidance_scale=None):
         """Admit a UniPC request: `sample_unipc()`'s arguments, checks and errors in its order, then the pool's; the two
-        condition arguments as for `submit`.  `corrector=False` (variant 'bh2') admits sample()'s multistep plan."""
+        condition arguments and `guidance_scale` as for `submit`.  `corrector=False` (variant 'bh2') admits sample()'s
+        multistep plan."""
         s = self._s
+        guide = self._guidance(guidance_scale, None)
         _unipc.check_solver(s, order, variant)
         t_0, t_T = _unipc._times(s, t_start, t_end)
         self._refuse(return_intermediate=return_intermediate)
@@ -284,11 +350,12 @@ class SlabPool:
                                           "'bh2', where it is DPM-Solver++ 2M)")
             return self.submit(x, steps=steps, t_start=t_start, t_end=t_end, order=order, skip_type=skip_type,
                                lower_order_final=lower_order_final, denoise_to_zero=denoise_to_zero, solver_type='dpmsolver',
-                               condition=condition, unconditional_condition=unconditional_condition)
+                               condition=condition, unconditional_condition=unconditional_condition,
+                               guidance_scale=guidance_scale)
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   'dpmsolver', unipc=variant)
-        return self._enqueue(x, plan, condition, unconditional_condition)
+        return self._enqueue(x, plan, condition, unconditional_condition, guide=guide)
 
     def _conditions(self, b, cond, uncond):
         """the request's condition tensors, checked against the wrapper's guidance kind (None where the network takes none)"""
@@ -357,7 +424,7 @@ class SlabPool:
         q.keep += list(ops.values())
         return q
 
-    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None):
+    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
@@ -370,6 +437,7 @@ class SlabPool:
         q = _Waiting()
         q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
         q.blend = None if blend is None else self._blend_of(blend, x, plan, sd)
+        q.guide = guide
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -450,6 +518,9 @@ class SlabPool:
             if q.seed is not None:       # sample k of the request sits in rows[k]: its z starts at element k * per_sample
                 o = self._ropts[q.h] = _sde.request_opts(q.seed, self._s._opts_ptr())
                 self._optp[ra], self._ns0[ra], self._seed[ra] = C.addressof(o), np.arange(b, dtype=np.int32), np.uint64(q.seed)
+            self._gon[ra] = q.guide is not None
+            if q.guide is not None:
+                self._gs[ra], self._gphi[ra] = q.guide
             self._bslot[ra] = -1
             if q.blend is not None:      # sample k of the request sits in rows[k]: its tensors start at element k * per_sample
                 bl = self._blends[q.h] = q.blend
@@ -555,6 +626,14 @@ class SlabPool:
                     self._blend_first(admitted, xin, stream)
             # the tick's records, vectorised: stage r = the record of row rows[r] at its position, pointers = base + row * stride
             st_v[:R] = rec
+            if self._cfg:
+                # rows whose request brought its own guidance: what the planner and _bind_rescale write for a wrapper of that
+                # scale and phi (phi 0: no flag, a plain row)
+                on = self._gon[rows] & (rec["guidance"] == L.GUIDE["classifier-free"])
+                cs, cg, fl = DV._cfg_fields(self._gs[rows], self._gphi[rows], rec["sigma_e"], rec["flags"])
+                st_v["cfg_scale"][:R] = np.where(on, cs, rec["cfg_scale"])
+                st_v["cg_scale"][:R] = np.where(on, cg, rec["cg_scale"])
+                st_v["flags"][:R] = np.where(on, fl, rec["flags"])
             b = b_v[:R]
             b_raw[:R * _BUFS.itemsize] = 0
             rb = rows.astype(np.uint64) * np.uint64(self._rowb)

@@ -728,7 +728,7 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False):
+    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -743,7 +743,13 @@ class DPM_Solver:
         table-driven launch too (DPM_TABLE_THRESH); without the flag a slab pool refuses such a solver.
         `slots=S, inpaint=True` (alone or with sde=True): the slab pool also admits inpainting / DiffEdit requests
         (`submit(x, ..., blend=MaskBlend(...))`, the result of sample() with correcting_xt_fn=blend), their mask-blend stages
-        in the table-driven launch too (DPM_TABLE_BLEND)."""
+        in the table-driven launch too (DPM_TABLE_BLEND).
+        `slots=S, rescale=True`: the slab pool of a classifier-free wrapper that admits guidance-rescale requests -- the
+        wrapper's own phi (`cfg_rescale`) or the request's (`submit(x, ..., guidance_rescale=phi)`), their stages in the
+        table-driven launch too (DPM_TABLE_RESCALE: one stage_rescale_kernel_table launch, one workgroup per row); samples of
+        whole 8-element groups.  Not together with sde / thresholding / inpaint (the rescale kernel has none of those
+        epilogues); without the flag a slab pool refuses a `cfg_rescale` solver.
+        Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
         if thresholding and slots is None:
@@ -755,16 +761,29 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
+        if rescale:
+            if slots is None:
+                raise ValueError("request_pool: rescale=True belongs to a slab pool (slots=...); a RequestPool takes a "
+                                 "cfg_rescale solver as it is")
+            for on, name, why in ((sde, "sde", "the SDE stage kernels have no rescale"),
+                                  (thresholding, "thresholding", "the thresholding kernels have no rescale"),
+                                  (inpaint, "inpaint", "the rescale kernel has no mask-blend epilogue")):
+                if on:
+                    raise NotImplementedError("request_pool: rescale=True with %s=True -- %s (a follow-up)" % (name, why))
+            if self._wrapped is None or self._wrapped.effective_guidance != "classifier-free":
+                raise ValueError("request_pool: rescale=True needs a classifier-free wrapper (an unconditional condition and a "
+                                 "guidance scale other than 1): guidance rescale rescales the guided output")
         if thresholding and not self._thresholding:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
-            self._check_rescale("the slab pool (request_pool(slots=...)) -- the table has no row kind for rescale stages (a "
-                                "follow-up); use request_pool() without slots")
+            if not rescale:
+                self._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built "
+                                    "with request_pool(slots=..., rescale=True) only")
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint)
+            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

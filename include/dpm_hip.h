@@ -82,11 +82,14 @@ extern "C" {
    212 DPM_F_CFG_RESCALE: classifier-free guidance with guidance rescale (Lin et al. 2023, section 3.4; diffusers'
    guidance_rescale) in ONE stage launch -- a kernel that owns a whole sample, takes the two per-sample standard deviations,
    then runs the usual prologue, update and stores (see DPM_F_CFG_RESCALE; no entry point added, no struct changed).
+   213 DPM_TABLE_RESCALE (a flag on table_mode): guidance-rescale stages in the table -- every qualifying DPM_F_CFG_RESCALE
+   request owns a row, a group of them is ONE stage_rescale_kernel_table launch, one workgroup per sample (see "Table mode"; no
+   entry point added, no struct changed, rows and records as in version 211).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 212
+#define DPM_HIP_VERSION 213
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -287,6 +290,9 @@ enum { DPM_TABLE_THRESH = 8 }; /* version 210: a flag OR-ed onto DPM_TABLE_FILL 
 enum { DPM_TABLE_BLEND = 32 }; /* version 211: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the two flags
                                    above: DPM_F_BLEND stages take rows too, each with a blend record behind the rows.  (Bit 16
                                    is unassigned: table_mode 16 .. 31 stay DPM_ERR_ARG, as in version 210.) */
+enum { DPM_TABLE_RESCALE = 128 }; /* version 213: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the three
+                                     flags above: DPM_F_CFG_RESCALE stages take rows too, rows like any other.  (Bits 16 and 64
+                                     are unassigned: table_mode 16 .. 31 and 64 .. 127 stay DPM_ERR_ARG.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 #define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
@@ -493,7 +499,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC and DPM_F_CFG_RESCALE are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC and DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -553,8 +559,26 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    DPM_F_NOISE or DPM_F_THRESH next to the blend ...) goes, in the same call, as its own dpm_stage_launch, which blends too:
    the same bits, one more launch.  Without the flag every call is version 210's.  Every request gets the bits of its own
    dpm_stage_launch.
-   Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND:
-   1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   Rescale rows (version 213): DPM_TABLE_RESCALE OR-ed onto either mode, alone or with any of the three flags above, makes the
+   same tick with guidance-rescale stages (DPM_F_CFG_RESCALE) in the table (stage_rescale_kernel_table: the kernel of the
+   request's own launch, one workgroup of 512 threads per sample, with pointers and stage scalars read from the sample's row;
+   no cluster, no workspace, no wait on another workgroup).  A DPM_F_CFG_RESCALE request owns a row when dpm_stage_launch
+   accepts the flag on it -- classifier-free guidance, samples of at least 2 elements, phi in (0, 1], no DPM_F_THRESH /
+   DPM_F_BLEND / DPM_F_NOISE, no DPM_FORM_UNIPC, a 2- or 4-byte dtype pair, a dense network output -- and its form is LIN1, TWO,
+   MS3 or DPM_FORM_DENOISE (the last stage of denoise_to_zero, its buffers checked as LIN1's), its evaluation state is its
+   state, its SAMPLE, n / batch elements, is whole 8-element groups (so a multiple of 16 bytes in either dtype: the kernel
+   works per sample, in 16-byte accesses), and every buffer, x_out2 included, is 16-byte aligned.  Such requests form groups of
+   their own that agree on dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the four forms, every phi
+   (dpm_stage.cg_scale) and guidance scale (cfg_scale), DPM_F_STORE_M and the duplicate store share a group: each is the row's
+   own.  Every group, from ONE member on, is one run of rows and ONE launch (below 2^31 samples), the runs in the order the
+   groups open, among those of the other families.  A rescale row is a row like any other -- the 8 pointers and the 20 words of
+   stage scalars; rows of other requests, the row size and the record sections are byte for byte those of version 211, and
+   there is no further section.  A DPM_F_CFG_RESCALE request that does not qualify (a sample of 12 elements, a misaligned
+   buffer, a separate evaluation state ...) goes, in the same call, as its own dpm_stage_launch, which rescales too: the same
+   bits, one more launch.  Without the flag every call is version 212's.  Every sample gets the bits of its request's own
+   dpm_stage_launch.
+   Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND,
+   DPM_TABLE_RESCALE: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, and each of those plus 128), a non-zero one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);

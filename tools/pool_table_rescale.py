@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""Many small guidance-rescale requests in flight: what a stage tick of R single-image requests under classifier-free guidance
+with guidance rescale costs as ONE table rescale launch.
+
+tools/pool_table_thresh.py's method on DPM-Solver++(2M) plans of a solver built on `cfg_rescale(model_fn, 0.7)` at guidance
+scale 7.5: R (default 256) requests `[1,4,64,64]` -- 16384 elements, the largest sample the kernel's register path holds --, 20
+steps, order 2, request r at stage (k + 20 r / R) mod 20 of tick k, frozen network outputs (conditional and unconditional); the
+rows live in slabs as a slab pool lays them out (the duplicate store of a stage goes to row R + r of the output slab), `--sets`
+(8) sets in rotation so that every tick's inputs come from HBM.  Modes:
+
+    H  DPM_TABLE_LAUNCH | DPM_TABLE_RESCALE alone, on device tables filled and copied beforehand: the one
+       stage_rescale_kernel_table launch
+    h  FILL + the pinned host-to-device copy + LAUNCH, both with DPM_TABLE_RESCALE: the whole stage side of a rescale slab pool's tick
+    a  the same arrays WITHOUT the flag (table_mode 0, per-request stages: what version 212 runs): R stage_rescale_kernel launches
+       of one workgroup each
+    b  ONE lockstep stage_rescale_kernel launch of `[R,4,64,64]`: the same grid and the same bytes at one stage -- what the rows
+       would cost if they marched in step
+    p  the plain ODE table tick of the same rows: the same arrays without DPM_F_CFG_RESCALE (classifier-free guidance alone),
+       one stage_kernel_table launch
+
+HIP events around `--ticks` back-to-back ticks after `--warmup` (mode a: a tenth of either, it is two orders slower),
+`--repeat` rounds over the modes, alternating.
+
+    python tools/pool_table_rescale.py --dtype fp16 --out DIR/events.jsonl
+"""
+import argparse
+import ctypes as C
+import json
+import sys
+
+import numpy as np
+import torch
+
+import pool_table as T
+import dpm_solver_amd as D
+from dpm_solver_amd import _lib as L
+
+STEPS, SHAPE, PER = T.STEPS, T.SHAPE, T.PER
+RESCALE = L.TABLE_RESCALE
+SCALE, PHI = 7.5, 0.7
+
+
+def solver(td, phi=PHI):
+    betas = np.linspace(0.00085 ** 0.5, 0.012 ** 0.5, 1000, dtype=np.float64) ** 2
+    ns = D.NoiseScheduleVP("discrete", alphas_cumprod=torch.from_numpy(np.cumprod(1.0 - betas).astype(np.float32)))
+    fn = D.model_wrapper(lambda x, t, c: x, ns, guidance_type="classifier-free", guidance_scale=SCALE, condition=torch.ones(1),
+                         unconditional_condition=torch.zeros(1))
+    return D.DPM_Solver(D.cfg_rescale(fn, phi), ns, algorithm_type="dpmsolver++", state_dtype=td)
+
+
+class RescaleSlabs:
+    """`sets` sets of slabs: state in [R, 4, 64, 64], state out [2R, ...] (the duplicate store's half behind the first), the
+    two frozen network outputs, three cached model values"""
+
+    def __init__(self, dev, dtype, R, sets):
+        self.td, self.code = T.DTYPES[dtype]
+        self.R, self.dev = R, dev
+        self.stages, self.plain = [], []
+        for phi, into in ((PHI, self.stages), (0.0, self.plain)):
+            dpm = solver(self.td, phi)
+            plan = dpm._get_plan(method="multistep", order=2, steps=STEPS, skip_type="time_uniform", solver_type="dpmsolver",
+                                 lower_order_final=True, denoise_to_zero=False, t_T=1.0, t_0=1.0 / dpm.noise_schedule.total_N)
+            into += [dpm._prep_stage(st.copy()) for st in plan.stages]
+        assert all(st.flags & L.F_CFG_RESCALE for st in self.stages) and not any(st.flags & L.F_CFG_RESCALE for st in self.plain)
+        g = torch.Generator(device=dev).manual_seed(0)
+        mk = lambda s=1.0: (s * torch.randn((R,) + SHAPE, generator=g, device=dev)).to(self.td)
+        self.sets = [dict(x=mk(), e0=mk(0.5), e1=mk(0.5), out=torch.empty((2 * R,) + SHAPE, dtype=self.td, device=dev),
+                          h=[mk(), mk(), mk()]) for _ in range(sets)]
+        self.rowb = PER * torch.empty((), dtype=self.td).element_size()
+
+    def buffers(self, S, r, st, n=PER, batch=1):
+        b = L.Buffers()
+        off = r * self.rowb
+        b.x, b.e0, b.e1 = S["x"].data_ptr() + off, S["e0"].data_ptr() + off, S["e1"].data_ptr() + off
+        b.x_out, b.x_out2 = S["out"].data_ptr() + off, S["out"].data_ptr() + self.R * self.rowb + off
+        if st.h1_slot >= 0:
+            b.h1 = S["h"][st.h1_slot].data_ptr() + off
+        if st.h2_slot >= 0:
+            b.h2 = S["h"][st.h2_slot].data_ptr() + off
+        if st.flags & L.F_STORE_M:
+            b.m_out = S["h"][st.m_slot].data_ptr() + off
+        b.n, b.batch, b.state_dtype, b.eps_dtype = n, batch, self.code, self.code
+        return b
+
+    def ticks(self, plain=False):
+        """the distinct ticks: (stages, buffers, options, host table, device table, R); plain: the same rows without the flag"""
+        R, stages = self.R, self.plain if plain else self.stages
+        out = []
+        for k in range(max(STEPS, len(self.sets))):
+            S = self.sets[k % len(self.sets)]
+            pos = [(k + (STEPS * r) // R) % STEPS for r in range(R)]
+            sts = (L.Stage * R)(*[stages[p] for p in pos])
+            bufs = (L.Buffers * R)(*[self.buffers(S, r, stages[pos[r]]) for r in range(R)])
+            o = L.LaunchOpts()
+            o.per_request_stages = 1
+            bufs[0].opts = C.pointer(o)
+            nb = L.table_bytes(R, RESCALE)
+            host = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+            out.append((sts, bufs, o, host, torch.empty(nb, dtype=torch.uint8, device=self.dev), R))
+        return out
+
+    def lone(self):
+        out = []
+        for k in range(max(STEPS, len(self.sets))):
+            st = self.stages[k % STEPS]
+            out.append((st, self.buffers(self.sets[k % len(self.sets)], 0, st, n=self.R * PER, batch=self.R)))
+        return out
+
+
+def prefill(ticks, stream, flag=RESCALE):
+    for sts, bufs, o, host, dev, R in ticks:
+        o.table_mode, bufs[0].workspace = L.TABLE_FILL | flag, host.data_ptr()
+        T._call(L.lib, sts, bufs, R, stream)
+        assert host[:16].view(torch.int32).tolist()[2:] == [R, 1], "the tick is not one run of rows"
+        dev.copy_(host)
+        o.table_mode, bufs[0].workspace = 0, None
+    torch.cuda.synchronize()
+
+
+def run(mode, ticks, lone, warmup, n_ticks, stream, plain=None):
+    """plain: the ticks of mode p (RescaleSlabs.ticks(plain=True), prefilled with flag 0)"""
+    if mode == "a":
+        warmup, n_ticks = max(2, warmup // 10), max(5, n_ticks // 10)
+    flag = 0 if mode == "p" else RESCALE
+
+    def tick(k):
+        if mode == "b":
+            st, b = lone[k % len(lone)]
+            L.check(L.lib.dpm_stage_launch(C.byref(st), C.byref(b), stream))
+            return
+        sts, bufs, o, host, dev, R = (plain if mode == "p" else ticks)[k % len(ticks)]
+        if mode == "a":
+            T._call(L.lib, sts, bufs, R, stream)
+            return
+        if mode == "h":
+            o.table_mode, bufs[0].workspace = L.TABLE_FILL | flag, host.data_ptr()
+            T._call(L.lib, sts, bufs, R, stream)
+            dev.copy_(host, non_blocking=True)
+        o.table_mode, bufs[0].workspace = L.TABLE_LAUNCH | flag, dev.data_ptr()
+        T._call(L.lib, sts, bufs, R, stream)
+        o.table_mode, bufs[0].workspace = 0, None
+    for k in range(warmup):
+        tick(k)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for k in range(warmup, warmup + n_ticks):
+        tick(k)
+    e1.record()
+    torch.cuda.synchronize()
+    sec = e0.elapsed_time(e1) / 1e3
+    return dict(ticks=n_ticks, region_s=sec, us_per_tick=sec * 1e6 / n_ticks)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--dtype", choices=sorted(T.DTYPES), default="fp16")
+    ap.add_argument("--requests", type=int, default=256)
+    ap.add_argument("--sets", type=int, default=8)
+    ap.add_argument("--modes", default="Hhabp")
+    ap.add_argument("--ticks", type=int, default=600)
+    ap.add_argument("--warmup", type=int, default=40)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("pool_table_rescale.py measures on the GPU; no device found")
+    dev = torch.device("cuda:0")
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    res = {"workload": "%d x [1,4,64,64] %s, 2M + CFG %.1f + guidance rescale %.1f, 20 steps, staggered, frozen outputs, %d slab sets"
+                       % (a.requests, a.dtype, SCALE, PHI, a.sets),
+           "label": a.label, "device": torch.cuda.get_device_name(0), "version": int(L.lib.dpm_version()), "ticks": a.ticks}
+    slabs = RescaleSlabs(dev, a.dtype, a.requests, a.sets)
+    ticks, lone, plain = slabs.ticks(), slabs.lone(), slabs.ticks(plain=True)
+    prefill(ticks, stream)
+    prefill(plain, stream, flag=0)
+    rows = []
+    for _ in range(a.repeat):
+        for m in a.modes:
+            rows.append(dict(mode=m, requests=a.requests, **run(m, ticks, lone, a.warmup, a.ticks, stream, plain)))
+    res["rows"] = rows
+    for m in sorted({r["mode"] for r in rows}):
+        v = [r["us_per_tick"] for r in rows if r["mode"] == m]
+        res["%s@%d" % (m, a.requests)] = dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()
