@@ -147,6 +147,16 @@ def _bind_rescale(st, phi):
     return st
 
 
+def _bind_apg(st, apg):
+    """Adaptive projected guidance (dpm_solver_amd.cfg_apg) in a stage record: a classifier-free stage carries DPM_F_CFG_APG, eta
+    in `cg_scale`, the norm threshold in `thr_ratio` and the momentum in `thr_max` -- fields nothing else reads under the flag.
+    apg = None leaves the record as it is.  (The running average travels in dpm_buffers.workspace: the caller binds it.)"""
+    if apg is not None and st.guidance == L.GUIDE["classifier-free"]:
+        st.cg_scale, st.thr_ratio, st.thr_max = float(apg[0]), float(apg[1]), float(apg[2])
+        st.flags |= L.F_CFG_APG
+    return st
+
+
 def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=None, opts=None, coef64=None):
     """One `dpm_stage_launch` on the current stream.  Allocates x_out (and m_out when the stage stores
     its model value) through torch's caching allocator; returns (x_out, m_out).
@@ -154,7 +164,8 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
     ext (optional dict): 'dup' -> write x_out twice into one [2B,...] buffer (returned as ext['x2'], x_out is its
     first half): the network input of classifier-free guidance; 'blend' -> (mask, period, a, b, alpha, sigma), the
     MaskBlend epilogue; 'xc' -> a DPM_FORM_UNIPC stage also stores its corrected state (DPM_F_STORE_XC), returned as
-    ext['xc_out'] (not together with 'dup': both use x_out2)."""
+    ext['xc_out'] (not together with 'dup': both use x_out2); 'apg_avg' -> the running average of a DPM_F_CFG_APG stage with a
+    momentum (an fp32 tensor of the state's shape, updated in place)."""
     ref_t = x if x is not None else xe
     dev = ref_t.device
     sd = state_dtype
@@ -230,6 +241,12 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
         if nb:
             ws = _cluster_workspace(dev, idx, stream, nb)
             b.workspace = ws.data_ptr()
+    if (st.flags & L.F_CFG_APG) and st.thr_max != 0.0:
+        # the run's running average (fp32, the state's shape); a launch outside a run (the public per-update calls) has no
+        # history: a first step, its average starts at zero
+        avg = ext.get("apg_avg") if ext is not None else None
+        ws = avg if avg is not None else torch.zeros(shape, dtype=torch.float32, device=dev)
+        b.workspace = ws.data_ptr()
     if ext is not None and ext.get("blend") is not None:
         mask, period, ba, bb, alpha, sigma = ext["blend"]
         st.flags |= L.F_BLEND

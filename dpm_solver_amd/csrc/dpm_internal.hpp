@@ -20,7 +20,7 @@
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
 // pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones, unit D (3) the
-// table-driven launch's mask-blend rows, unit E (4) the guidance-rescale stage.
+// table-driven launch's mask-blend rows, unit E (4) the guidance-rescale stage, unit F (5) the adaptive-projected-guidance stage.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -67,6 +67,9 @@ int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, 
 // (unit E, DPM_TABLE_RESCALE) DPM_F_CFG_RESCALE rows -- rows like any other, no records --, one workgroup per sample
 template <typename TS, typename TE>
 int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (unit F, DPM_F_CFG_APG) one classifier-free stage with adaptive projected guidance: one workgroup per sample (stage_apg_kernel)
+template <typename TS, typename TE>
+int dpm_launch_apg(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -46,12 +46,13 @@ struct PairUnits {
   // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows
   TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale;
   RescaleFn rescale;  // unit E's guidance-rescale stage (DPM_F_CFG_RESCALE)
+  RescaleFn apg;      // unit F's adaptive-projected-guidance stage (DPM_F_CFG_APG)
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
-   dpm_table_launch_rescale<TS, TE>, dpm_launch_rescale<TS, TE>},
+   dpm_table_launch_rescale<TS, TE>, dpm_launch_rescale<TS, TE>, dpm_launch_apg<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -84,7 +85,9 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
   if (b->noise_sample0 != 0 && !base_ok)
     return fail(DPM_ERR_ARG, "stage_launch: noise_sample0=%d (honoured by the SDE rows of a DPM_TABLE_NOISE call only)",
                 b->noise_sample0);
-  if (st->flags & DPM_F_CFG_RESCALE) {  // guidance rescale (include/dpm_hip.h): one workgroup per sample, stage_rescale_kernel
+  // guidance rescale (include/dpm_hip.h): one workgroup per sample, stage_rescale_kernel.  (Together with DPM_F_CFG_APG, whose
+  // eta shares cg_scale with phi, the pair is reported by that flag's checks below.)
+  if ((st->flags & DPM_F_CFG_RESCALE) && !(st->flags & DPM_F_CFG_APG)) {
     const int64_t per = b->n / b->batch;
     if (st->guidance != DPM_GUIDE_CFG)
       return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE is valid under classifier-free guidance only (guidance %d)", st->guidance);
@@ -101,6 +104,35 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
       return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with a double state (no double rescale kernel)");
     if (b->eps_stride != 0 && b->eps_stride != per)
       return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with eps_stride=%lld (a channel slice of a wider output)",
+                  (long long)b->eps_stride);
+  }
+  if (st->flags & DPM_F_CFG_APG) {  // adaptive projected guidance (include/dpm_hip.h): one workgroup per sample, stage_apg_kernel
+    const int64_t per = b->n / b->batch;
+    const float eta = st->cg_scale, r = st->thr_ratio, beta = st->thr_max;
+    if (st->guidance != DPM_GUIDE_CFG)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG is valid under classifier-free guidance only (guidance %d)", st->guidance);
+    if (b->n > 0 && per < 1)  // (an empty batch is DPM_OK below, as for every stage; its record is still checked)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG needs samples of at least 1 element (got %lld)", (long long)per);
+    if (!(eta >= 0.f && eta <= 1.f))
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with eta=%g (dpm_stage.cg_scale), which is not in [0, 1]", (double)eta);
+    if (!(r >= 0.f))
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a norm threshold of %g (dpm_stage.thr_ratio), which is not >= 0", (double)r);
+    if (!(beta > -1.f && beta < 1.f))
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum of %g (dpm_stage.thr_max), which is not in (-1, 1)", (double)beta);
+    if (beta != 0.f && !b->workspace)
+      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum needs the running average in dpm_buffers.workspace");
+    // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
+    if (st->form != DPM_FORM_UNIPC && (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_DENOISE))
+      return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
+    if (!(st->flags & DPM_F_TO_X0))
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG without DPM_F_TO_X0 (it is defined on the data prediction)");
+    if (st->flags & (DPM_F_CFG_RESCALE | DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with guidance rescale, thresholding, mask blend or noise (flags %u)", st->flags);
+    if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG on a DPM_FORM_UNIPC stage");
+    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with a double state (no double kernel)");
+    if (b->eps_stride != 0 && b->eps_stride != per)
+      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with eps_stride=%lld (a channel slice of a wider output)",
                   (long long)b->eps_stride);
   }
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
@@ -178,6 +210,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with device-resident coefficients");
   if (dyn && (st->flags & DPM_F_CFG_RESCALE))
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with device-resident coefficients");
+  if (dyn && (st->flags & DPM_F_CFG_APG))
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with device-resident coefficients");
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -188,6 +222,7 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   }
   const PairUnits* p = pair_of(sd, ed);
   if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
+  if (st->flags & DPM_F_CFG_APG) return p->apg(st, &bb, stream, ev_start, ev_stop);
   if (st->flags & DPM_F_CFG_RESCALE) return p->rescale(st, &bb, stream, ev_start, ev_stop);
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
@@ -469,6 +504,8 @@ int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_bu
                     owns_row(DPM_TABLE_THRESH, st[0], bs[0], o->table_mode, tuning_for(o).multi_fuse != 0);
   if ((st[0].flags & DPM_F_THRESH) && !row0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with DPM_F_THRESH in st[0] (bs[0].workspace is the table)");
+  if ((st[0].flags & DPM_F_CFG_APG) && st[0].thr_max != 0.f)  // (its running average would be that workspace)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with a DPM_F_CFG_APG momentum in st[0] (bs[0].workspace is the table)");
   return DPM_OK;
 }
 }  // namespace

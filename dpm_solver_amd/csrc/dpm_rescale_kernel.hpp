@@ -1,6 +1,7 @@
 // dpm_rescale_kernel.hpp -- classifier-free guidance with guidance rescale (DPM_F_CFG_RESCALE, include/dpm_hip.h; Lin et al.
 // 2023, section 3.4): stage_rescale_kernel, a stage kernel that owns a whole SAMPLE, and its launcher.  Included by unit E of
-// dpm_stage_unit.hip behind dpm_device.hpp and by nothing else, so that every other unit compiles to the code it compiled to.
+// dpm_stage_unit.hip behind dpm_device.hpp -- and by unit F for the frame alone (rescale_index / rescale_load / rescale_store,
+// dpm_apg_kernel.hpp; it instantiates no kernel of this file) -- so that every other unit compiles to the code it compiled to.
 //
 // The streaming kernels have no notion of a sample; the rescale needs the standard deviation of the guided and of the
 // conditional output over each one.  One workgroup of 512 threads per sample, grid = batch:

@@ -1,5 +1,5 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled twenty-five times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4> (__graft_entry__.py).
+// translation unit: compiled thirty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
@@ -12,9 +12,12 @@
 //   unit E (4): the launch of a guidance-rescale stage (stage_rescale_kernel, DPM_F_CFG_RESCALE; dpm_rescale_kernel.hpp, which
 //               no other unit includes) and of the table's guidance-rescale rows (stage_rescale_kernel_table, DPM_TABLE_RESCALE;
 //               dpm_table_rescale.hpp) and nothing else -- units A to D compile to the code they compiled to before it existed
+//   unit F (5): the launch of an adaptive-projected-guidance stage (stage_apg_kernel, DPM_F_CFG_APG; dpm_apg_kernel.hpp on the
+//               frame of dpm_rescale_kernel.hpp, none of whose kernels it instantiates) and nothing else -- units A to E compile
+//               to the code they compiled to before it existed
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -23,6 +26,10 @@
 #if DPM_UNIT == 4
 #include "dpm_rescale_kernel.hpp"
 #include "dpm_table_rescale.hpp"
+#endif
+#if DPM_UNIT == 5
+#include "dpm_rescale_kernel.hpp"
+#include "dpm_apg_kernel.hpp"
 #endif
 
 #include <tuple>
@@ -129,4 +136,13 @@ int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_r
   return launch_table_rescale_typed<TS, TE>(st, bs, n_req, rows, s);
 }
 template int dpm_table_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+#endif
+
+#if DPM_UNIT == 5
+template <typename TS, typename TE>
+int dpm_launch_apg(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
+  return launch_apg_typed<TS, TE>(st, b, s);
+}
+template int dpm_launch_apg<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 #endif

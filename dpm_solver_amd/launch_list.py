@@ -66,6 +66,9 @@ class _FastRun:
         self.hist = [DV._empty(shape, sd, device, mf) for _ in range(plan.slots)]
         self.ws = None
         self.thr_hint = None
+        # adaptive projected guidance with a momentum: the run's running average, bound to every flagged stage's workspace;
+        # whoever starts a run on these records zeroes it (run_plan_fast, run_plan_group, the pool's _start)
+        self.apg_avg = solver._apg_average(shape, device)
         nstg = len(plan.stages)
         self.stages, self.bufs, self.refs = [], [], []
         esz = torch.empty((), dtype=sd).element_size()
@@ -106,6 +109,8 @@ class _FastRun:
                         self.thr_hint = torch.zeros(L.THR_HINT_WORDS * max(B, 1), dtype=torch.float32, device=device)
                     b.workspace = self.ws.data_ptr()
                     b.thr_hint = self.thr_hint.data_ptr()
+            if (st.flags & L.F_CFG_APG) and self.apg_avg is not None:
+                b.workspace = self.apg_avg.data_ptr()
             self.stages.append(st)
             self.bufs.append(b)
             self.refs.append((C.byref(st), C.byref(b)))

@@ -47,7 +47,7 @@ def run_plan_group(self, plan, xs, sd, cfg):
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._rescale_phi())
+           self._rescale_phi(), self._apg_params())
     grp = None if capturing else self._fast_groups.get(key)
     if grp is None:
         runs = [_FastRun(self, plan, shape, sd, device, cfg, mf) for _ in range(R)]
@@ -63,6 +63,9 @@ def run_plan_group(self, plan, xs, sd, cfg):
                 self._fast_groups.pop(next(iter(self._fast_groups)))
             self._fast_groups[key] = grp
     runs, arrs = grp
+    for fr in runs:
+        if fr.apg_avg is not None:
+            fr.apg_avg.zero_()              # a run starts: its running average is zero
     if not plan.sde:
         return _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, idx, other)
     # sample_sde_requests: every request's seed in a dpm_launch_opts of its own, pointed to for the length of this call
@@ -143,7 +146,7 @@ def run_plan_fast(self, plan, x, sd, cfg):
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._rescale_phi())
+           self._rescale_phi(), self._apg_params())
     fr = None if capturing else self._fast.get(key)      # a captured graph bakes its buffers in: give it its own
     if fr is None:
         fr = _FastRun(self, plan, x.shape, sd, device, cfg, mf)
@@ -151,6 +154,8 @@ def run_plan_fast(self, plan, x, sd, cfg):
             if len(self._fast) >= 8:
                 self._fast.pop(next(iter(self._fast)))
             self._fast[key] = fr
+    if fr.apg_avg is not None:
+        fr.apg_avg.zero_()                  # a run starts: its running average is zero
     x0 = DV._conv(x, sd, mf)
     p0 = x0.data_ptr()
     out = DV._empty(x.shape, sd, device, mf)
@@ -199,6 +204,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     sd = self._sdtype(x)
     cfg = self._wrapped is not None and self._wrapped.effective_guidance == "classifier-free"
     self._check_rescale(sd=sd, blend=isinstance(cxt, MaskBlend))    # the one check of a run (its loops do not repeat it)
+    self._check_apg(sd=sd, blend=isinstance(cxt, MaskBlend))
     # denoise_to_zero evaluates the data prediction at a (1,)-shaped time (ref :1236: `torch.ones((1,)) * t_0`): on a
     # continuous schedule its alpha_t / sigma_t are then dimensioned fp32 tensors and the RESULT of a half-precision run
     # is fp32 (on a discrete schedule every run is fp32 anyway).  That last stage runs in fp32 in the general loop below.
@@ -241,6 +247,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     state, state2 = x, None
     tmp, tmp2 = None, None
     hist = [None] * max(plan.slots, 1)
+    apg_avg = self._apg_average(x.shape, device)        # zeroed here: every evaluation of THIS run updates it
     for i, ps in enumerate(plan.stages):
         st = self._prep_stage(ps.copy())                # (a copy: launches may edit flags)
         from_tmp = st.xe_src == L.SRC_TMP
@@ -266,6 +273,8 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
             ext["dup"] = True
         if blend is not None and st.emits_state:
             ext["blend"] = blend.operands(x.shape, sd, device, ps.t_out, st.outer_step)
+        if apg_avg is not None:
+            ext["apg_avg"] = apg_avg
         c64 = None
         if sd is torch.float64:
             c64 = self._stage64(st, plan.stages64[i] if plan.stages64 is not None else None)

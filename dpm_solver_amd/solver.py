@@ -185,6 +185,42 @@ class DPM_Solver:
             raise NotImplementedError("guidance rescale (cfg_rescale): double-precision states (there is no double rescale "
                                       "kernel)")
 
+    def _apg_params(self):
+        """(eta, norm threshold, momentum) of the wrapper's adaptive projected guidance (dpm_solver_amd.cfg_apg); None: none,
+        every launch as without it"""
+        return self._wrapped.apg if self._wrapped is not None else None
+
+    def _apg_average(self, shape, device):
+        """a zeroed running average for one run under adaptive projected guidance with a momentum (fp32, the state's shape);
+        None where the run carries none"""
+        apg = self._apg_params()
+        if apg is None or apg[2] == 0.0:
+            return None
+        return torch.zeros(tuple(shape), dtype=torch.float32, device=device)
+
+    def _check_apg(self, what=None, sd=None, blend=False):
+        """the combinations adaptive projected guidance is not built with, as _check_rescale: `what` names a
+        sampler or a mode that has none; else the solver's algorithm and correctors, the run's corrector and state dtype"""
+        if self._apg_params() is None:
+            return
+        if what is not None:
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): %s" % what)
+        if self._rescale_phi():
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): together with guidance rescale (cfg_rescale) -- "
+                                      "the two remedies are not built together")
+        if self.algorithm_type != "dpmsolver++":
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): algorithm_type='dpmsolver' -- it is defined on "
+                                      "the data prediction (algorithm_type='dpmsolver++')")
+        if self._thresholding:
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): correcting_x0_fn='dynamic_thresholding' -- the "
+                                      "thresholding kernels have no projected guidance (a follow-up)")
+        if blend:
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): a MaskBlend corrector -- its kernel has no "
+                                      "mask-blend epilogue (a follow-up)")
+        if sd is torch.float64:
+            raise NotImplementedError("adaptive projected guidance (cfg_apg): double-precision states (there is no double "
+                                      "kernel)")
+
     def _sdtype(self, x):
         if self._state_dtype is not None:
             return self._state_dtype
@@ -369,19 +405,25 @@ class DPM_Solver:
                 raise NotImplementedError("guidance rescale (cfg_rescale): correcting_x0_fn='dynamic_thresholding' -- the "
                                           "thresholding kernels have no rescale (a follow-up)")
             DV._bind_rescale(st, phi)
+        apg = self._apg_params()
+        if apg is not None:
+            self._check_apg()
+            DV._bind_apg(st, apg)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
         """outs = (e0, e1, g) fresh network outputs.  Handles a *callable* correcting_x0_fn by splitting the
         stage: prologue kernel -> user function (opaque torch) -> combination kernel."""
         self._check_rescale(sd=sd)          # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
+        self._check_apg(sd=sd)
         e0, e1, g = outs if sd is not torch.float64 else self._cfg_pre(outs, sd)
         if self._user_x0 is not None and (st.flags & L.F_TO_X0):
             s1 = st.copy()
             s1.form = L.FORM_DENOISE
-            s1.flags = L.F_TO_X0 | (st.flags & L.F_CFG_RESCALE)
+            s1.flags = L.F_TO_X0 | (st.flags & (L.F_CFG_RESCALE | L.F_CFG_APG))
+            avg = ext.get("apg_avg") if ext is not None else None
             x0, _ = DV._launch_stage(s1, None, xe if xe is not None else x, e0, e1, g, None, None, sd, want_m=False,
-                                  opts=self._opts_ptr(), coef64=coef64)
+                                  ext={"apg_avg": avg} if avg is not None else None, opts=self._opts_ptr(), coef64=coef64)
             x0 = self._call_x0(x0, t_eval_t)                                             # ref :440-441
             return self._run_given(st, x, x0, h1, h2, sd, want_m, ext=ext, coef64=coef64)
         return DV._launch_stage(st, x, xe, e0, e1, g, h1, h2, sd, want_m=want_m, ext=ext, opts=self._opts_ptr(), coef64=coef64)
@@ -777,6 +819,8 @@ class DPM_Solver:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
+            self._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance rows in the table are a follow-up; "
+                            "a RequestPool (no slots) takes a cfg_apg solver as it is")
             if not rescale:
                 self._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built "
                                     "with request_pool(slots=..., rescale=True) only")
@@ -799,6 +843,10 @@ class DPM_Solver:
         synchronisation, no data-dependent control flow), shapes are frozen, and the returned tensors are static
         buffers that the next replay overwrites.  method='adaptive' is captured with its device-side controller: exactly
         `adaptive_max_iterations` (default 64) iterations are recorded, those after t_end is reached do nothing."""
+        apg = self._apg_params()
+        if apg is not None and apg[2] != 0.0:
+            self._check_apg("capture with a momentum -- a replayed graph would carry the running average of one run into the "
+                            "next; capture with momentum=0, or sample() eagerly")
         if sample_kwargs.get("method", "multistep") == "adaptive" and not self._adaptive_runs_on_device(x):
             raise NotImplementedError("the host-side adaptive control loop synchronises every iteration; it cannot be "
                                       "captured into a graph (the device-side controller can: adaptive_on_device = True, no "

@@ -17,6 +17,9 @@ class WrappedModel:
     # guidance rescale (Lin et al. 2023, section 3.4; diffusers' `guidance_rescale`): phi in [0, 1], set through
     # dpm_solver_amd.cfg_rescale -- model_wrapper's signature is the reference's.  0 = off: every bit as without it.
     guidance_rescale = 0.0
+    # adaptive projected guidance (Sadat et al. 2024; diffusers' APG guider): (eta, norm threshold, momentum), set through
+    # dpm_solver_amd.cfg_apg.  None = off: every bit as without it.
+    guidance_apg = None
 
     def __init__(self, model, noise_schedule, model_type, model_kwargs, guidance_type, condition,
                  unconditional_condition, guidance_scale, classifier_fn, classifier_kwargs):
@@ -47,6 +50,58 @@ class WrappedModel:
         """phi of the guidance rescale this wrapper asks the stage kernels for; 0.0 = none (phi 0, or no classifier-free blend)"""
         phi = float(self.guidance_rescale)
         return phi if phi != 0.0 and self.effective_guidance == "classifier-free" else 0.0
+
+    @property
+    def apg(self):
+        """(eta, norm threshold, momentum) of the adaptive projected guidance this wrapper asks the stage kernels for; None =
+        none (never set, or no classifier-free blend)"""
+        return self.guidance_apg if self.guidance_apg is not None and self.effective_guidance == "classifier-free" else None
+
+    def apg_x0(self, x, t_continuous, average=None):
+        """The guided DATA prediction under adaptive projected guidance, in torch (include/dpm_hip.h, DPM_F_CFG_APG, in the
+        tensors' own precision -- half outputs are widened to fp32 first, as the stage kernel widens them --, the three
+        per-sample sums in float64).  `average`: the running average of the guidance direction, an fp32 tensor of x's shape
+        updated in place (momentum != 0); None: a first step, the average starts at zero."""
+        from .utils import expand_dims
+        eta, r, beta = self.apg
+        e0, e1, _ = self.raw_outputs(x, t_continuous)
+        dims = x.dim()
+        wide = torch.float64 if torch.float64 in (x.dtype, e0.dtype) else torch.float32
+        e0, e1, xw = e0.to(wide), e1.to(wide), x.to(wide)
+        alpha_t, sigma_t = self.noise_schedule.device_alpha_sigma(t_continuous)
+        al, sg = expand_dims(alpha_t, dims).to(wide), expand_dims(sigma_t, dims).to(wide)
+        mt = self.model_type
+
+        def x0_of(out):                                           # noise_pred_fn (ref :288-298), then ref :439
+            if mt == "x_start":
+                eps = (xw - al * out) / sg
+            elif mt == "v":
+                eps = al * out + sg * xw
+            elif mt == "score":
+                eps = -sg * out
+            else:
+                eps = out
+            return (xw - sg * eps) / al
+        c = x0_of(e0)
+        d = c - x0_of(e1)
+        if beta != 0.0:
+            if average is not None:
+                d = average.copy_(d + beta * average.to(wide)).to(wide)
+            # (no average: a first step -- d + beta * 0)
+        axes = list(range(1, dims))
+        d64, c64 = d.double(), c.double()
+        s_dd = (d64 * d64).sum(dim=axes, keepdim=True)
+        s_dc = (d64 * c64).sum(dim=axes, keepdim=True)
+        s_cc = (c64 * c64).sum(dim=axes, keepdim=True)
+        sc64 = torch.ones_like(s_dd)
+        if r > 0.0:
+            t = float(torch.tensor(r, dtype=torch.float32)) / s_dd.sqrt()
+            sc64 = torch.where(t < 1.0, t, sc64)
+        sc, q = sc64.to(wide), (sc64 * s_dc / s_cc).to(wide)
+        dn, par = sc * d, q * c
+        upd = (dn - par) + eta * par
+        s1 = float(torch.tensor(float(self.guidance_scale), dtype=torch.float32) - 1.0)   # (s - 1.f) as the kernel forms it
+        return c + s1 * upd
 
     def get_model_input_time(self, t_continuous):
         """ref :271-280"""
@@ -92,10 +147,18 @@ class WrappedModel:
         """The reference's model_fn(x, t_continuous) -> noise (ref :282-330) for callers OTHER than DPM_Solver (which fuses
         these conversions into its stage kernels and never comes here): the raw network call(s), then the reference's own
         tensor expressions in torch on x's device -- per-sample times (`t_continuous` of shape (B,) with distinct entries)
-        included, no host synchronisation (the schedule is evaluated on the device, NoiseScheduleVP.device_alpha_sigma)."""
+        included, no host synchronisation (the schedule is evaluated on the device, NoiseScheduleVP.device_alpha_sigma).
+        Under adaptive projected guidance (cfg_apg) the result is the noise prediction equivalent to the guided data
+        prediction, (x - alpha * x0) / sigma; a direct call has no history: it is a FIRST step, with a running average of
+        zero, whatever the momentum."""
         from .utils import expand_dims
         from ._device import _require_gpu
         _require_gpu(x)
+        if self.apg is not None:
+            x0 = self.apg_x0(x, t_continuous)
+            alpha_t, sigma_t = self.noise_schedule.device_alpha_sigma(t_continuous)
+            al, sg = expand_dims(alpha_t, x.dim()).to(x0.dtype), expand_dims(sigma_t, x.dim()).to(x0.dtype)
+            return (x.to(x0.dtype) - al * x0) / sg
         e0, e1, g = self.raw_outputs(x, t_continuous)
         mt = self.model_type
         dims = x.dim()
@@ -143,8 +206,38 @@ def cfg_rescale(model_fn, phi):
                          % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
     if isinstance(phi, bool) or not isinstance(phi, numbers.Real) or not (0.0 <= float(phi) <= 1.0):
         raise ValueError("cfg_rescale: phi must be a real number in [0, 1], got %r" % (phi,))
+    if phi and model_fn.guidance_apg is not None:
+        raise NotImplementedError("cfg_rescale on top of cfg_apg: the two remedies are not built together")
     out = copy.copy(model_fn)
     out.guidance_rescale = float(phi)
+    return out
+
+
+def cfg_apg(model_fn, eta=0.0, norm_threshold=0.0, momentum=0.0):
+    """(extension) A copy of the classifier-free wrapper `model_fn` with adaptive projected guidance (Sadat et al. 2024,
+    "Eliminating Oversaturation and Artifacts of High Guidance Scales in Diffusion Models"; the APG guider of diffusers): the
+    guidance direction -- conditional minus unconditional data prediction -- is capped at the per-sample norm `norm_threshold`
+    (0 = no cap), split into its components parallel and orthogonal to the conditional prediction, the parallel one scaled by
+    `eta` in [0, 1], and with `momentum` in (-1, 1) replaced by its running average over the network evaluations of a run
+    (a = d + momentum * a; the paper uses negative values).  DPM_Solver runs it inside the stage kernel (DPM_F_CFG_APG) of the
+    data-prediction samplers.  cfg_apg(fn, 1.0, 0.0, 0.0) is classifier-free guidance itself and changes nothing."""
+    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
+        raise ValueError("cfg_apg: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
+                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
+    for name, v in (("eta", eta), ("norm_threshold", norm_threshold), ("momentum", momentum)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
+            raise ValueError("cfg_apg: %s must be a real number, got %r" % (name, v))
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError("cfg_apg: eta must be in [0, 1], got %r" % (eta,))
+    if not (0.0 <= float(norm_threshold) < float("inf")):
+        raise ValueError("cfg_apg: norm_threshold must be a finite number >= 0 (0 = off), got %r" % (norm_threshold,))
+    if not -1.0 < float(momentum) < 1.0:
+        raise ValueError("cfg_apg: momentum must be in (-1, 1), got %r" % (momentum,))
+    params = (float(eta), float(norm_threshold), float(momentum))
+    if params != (1.0, 0.0, 0.0) and float(model_fn.guidance_rescale) != 0.0:
+        raise NotImplementedError("cfg_apg on top of cfg_rescale: the two remedies are not built together")
+    out = copy.copy(model_fn)
+    out.guidance_apg = None if params == (1.0, 0.0, 0.0) else params
     return out
 
 

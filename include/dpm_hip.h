@@ -85,11 +85,15 @@ extern "C" {
    213 DPM_TABLE_RESCALE (a flag on table_mode): guidance-rescale stages in the table -- every qualifying DPM_F_CFG_RESCALE
    request owns a row, a group of them is ONE stage_rescale_kernel_table launch, one workgroup per sample (see "Table mode"; no
    entry point added, no struct changed, rows and records as in version 211).
+   214 DPM_F_CFG_APG: classifier-free guidance with adaptive projected guidance (Sadat et al. 2024; diffusers' APG guider) in
+   ONE stage launch -- a kernel that owns a whole sample, splits the guidance direction of the two data predictions into its
+   components parallel and orthogonal to the conditional one, damps the parallel one, caps the direction's norm and optionally
+   carries a running average of it from stage to stage (see DPM_F_CFG_APG; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 213
+#define DPM_HIP_VERSION 214
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -211,6 +215,42 @@ enum {
                                   written in any error case.  One workgroup per sample (stage_rescale_kernel); such a stage runs
                                   on its own in a multi-request launch, in every mode of dpm_stage_launch_multi */
 
+#define DPM_F_CFG_APG 2048u /* version 214, with guidance == DPM_GUIDE_CFG only (else DPM_ERR_ARG); never set by the planner.
+                               Adaptive projected guidance (Sadat et al. 2024): the guidance direction -- the difference of the
+                               conditional and the unconditional DATA prediction -- is capped in norm per sample, split into its
+                               components parallel and orthogonal to the conditional prediction, the parallel one damped by eta,
+                               and optionally smoothed over the stages by a (negative) momentum.  The flag reuses fields nothing
+                               else reads under it: dpm_stage.cg_scale carries eta in [0, 1], dpm_stage.thr_ratio the norm
+                               threshold r >= 0 (0 = off), dpm_stage.thr_max the momentum beta in (-1, 1) (0 = off), and with
+                               beta != 0 dpm_buffers.workspace the RUNNING AVERAGE: n fp32 values in the state's flat order, read
+                               and written in place (the caller zero-fills it where a trajectory starts).  For each sample of
+                               the launch, P = n / batch elements, s = cfg_scale:
+                                 c = x0 of the conditional output e0, u = x0 of the unconditional output e1: the noise
+                                     prediction of the raw output on xe (x_start / v / score conversion), then
+                                     (xe - sigma_e * eps) / alpha_e -- operation for operation the model value of a flag-less
+                                     data-prediction stage; raw outputs are widened to fp32 on load, nothing after that is
+                                     rounded to the network's dtype
+                                 d = c - u                                               fp32
+                                 beta != 0:  a = d + beta * a  (fp32, one rounding per operation, no fused multiply-add);
+                                             a is stored;  d = a
+                                 S_dd = sum d*d, S_dc = sum d*c, S_cc = sum c*c          products and sums in double, any order
+                                 sc64 = r > 0 ? (t < 1 ? t : 1) : 1,  t = (double)r / sqrt(S_dd)      double
+                                 sc = (float)sc64;  q = (float)((sc64 * S_dc) / S_cc)    one rounding each
+                                 dn = sc * d;  par = q * c;  upd = (dn - par) + eta * par          fp32, one rounding per operation
+                                 mn = c + (s - 1.f) * upd                                the guided data prediction
+                                 then the update form, DPM_F_STORE_M and the stores as without the flag
+                               A degenerate sample (S_cc == 0) gets what IEEE gives.  With eta = 1, r = 0 and beta = 0 the result
+                               is classifier-free guidance up to rounding.
+                               DPM_ERR_ARG: the flag without DPM_GUIDE_CFG; eta, r or beta out of range or NaN; beta != 0 with a
+                               null workspace; an unknown form; P < 1 (an empty batch, n == 0, is DPM_OK and launches nothing).
+                               DPM_ERR_UNSUPPORTED (this version): the flag without DPM_F_TO_X0 (it is defined on the data
+                               prediction); together with DPM_F_CFG_RESCALE, DPM_F_THRESH, DPM_F_BLEND or DPM_F_NOISE;
+                               DPM_FORM_UNIPC; a double state; eps_stride other than 0 or P; device-resident coefficients.  No
+                               output byte is written in any error case, the running average neither.  One workgroup per
+                               sample (stage_apg_kernel); such a stage runs on its own in a multi-request launch, in every mode
+                               of dpm_stage_launch_multi (in a table call it cannot be st[0] with beta != 0: bs[0].workspace is
+                               the table there -- DPM_ERR_ARG) */
+
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
 
@@ -234,12 +274,12 @@ typedef struct dpm_stage {
   float alpha_e;       /* alpha(t_eval)                                                          */
   float sigma_e;       /* sigma(t_eval)                                                          */
   float cfg_scale;     /* guidance_scale as fp32 (ref :330)                                      */
-  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi */
+  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi; DPM_F_CFG_APG: eta */
   float cx, c0, c1, c2; /* update coefficients, reference association (see kernels)              */
   float k[5];          /* difference-quotient scalars: 1/r0, 1/r1, ...                           */
-  float thr_ratio;     /* dynamic_thresholding_ratio                                             */
-  float thr_max;       /* thresholding_max_val                                                   */
-  float blend_alpha;   /* DPM_F_BLEND: alpha at the time the known image is noised to (add_noise, ref :1028)  */
+  float thr_ratio;     /* dynamic_thresholding_ratio;  DPM_F_CFG_APG: the norm threshold r       */
+  float thr_max;       /* thresholding_max_val;        DPM_F_CFG_APG: the momentum beta          */
+  float blend_alpha;  /* DPM_F_BLEND: alpha at the time the known image is noised to (add_noise, ref :1028)  */
   float blend_sigma;   /* DPM_F_BLEND: sigma at that time                                        */
 } dpm_stage;
 
@@ -308,7 +348,8 @@ typedef struct dpm_buffers {
   const void* h2;   /* cached model value                                    [n] state dtype     */
   void* x_out;      /* result of the update                                  [n] state dtype     */
   void* m_out;      /* new model value (only if DPM_F_STORE_M)               [n] state dtype     */
-  void* workspace;  /* thresholding scratch, dpm_threshold_workspace_bytes() bytes (may be NULL) */
+  void* workspace;  /* thresholding scratch, dpm_threshold_workspace_bytes() bytes (may be NULL);
+                       DPM_F_CFG_APG with a momentum: the running average, n fp32 values             */
   int64_t n;          /* total elements = batch * per_sample                                     */
   int64_t batch;      /* number of independent samples                                           */
   int32_t state_dtype; /* DPM_DTYPE_* of x, xe, h1, h2, x_out, m_out                             */
