@@ -61,15 +61,13 @@ int dpm_table_launch_thresh(const dpm_stage* st, const dpm_buffers* bs, int n_re
 template <typename TS, typename TE>
 int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
-// (unit E, DPM_F_CFG_RESCALE) one classifier-free stage with guidance rescale: one workgroup per sample (stage_rescale_kernel)
-template <typename TS, typename TE>
-int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+// one classifier-free stage under a per-sample guidance FLAG, one workgroup per sample: DPM_F_CFG_RESCALE (unit E, guidance
+// rescale, stage_rescale_kernel) or DPM_F_CFG_APG (unit F, adaptive projected guidance, stage_apg_kernel)
+template <typename TS, typename TE, unsigned FLAG>
+int dpm_launch_sample(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
 // (unit E, DPM_TABLE_RESCALE) DPM_F_CFG_RESCALE rows -- rows like any other, no records --, one workgroup per sample
 template <typename TS, typename TE>
 int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
-// (unit F, DPM_F_CFG_APG) one classifier-free stage with adaptive projected guidance: one workgroup per sample (stage_apg_kernel)
-template <typename TS, typename TE>
-int dpm_launch_apg(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -35,7 +35,7 @@ using FusedFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*, void*,
 using HetFn = int (*)(const dpm_stage*, const dpm_buffers*, int, void*);
 // the one launch over a group's run of table rows and its records (null: the kind has none), both in device memory
 using TableLaunchFn = int (*)(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
-using RescaleFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
+using SampleFn = int (*)(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 struct PairUnits {
   int state_dtype, eps_dtype;
   UnitFn a, b;
@@ -45,14 +45,15 @@ struct PairUnits {
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
   // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows
   TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale;
-  RescaleFn rescale;  // unit E's guidance-rescale stage (DPM_F_CFG_RESCALE)
-  RescaleFn apg;      // unit F's adaptive-projected-guidance stage (DPM_F_CFG_APG)
+  // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance
+  SampleFn rescale, apg;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
-   dpm_table_launch_rescale<TS, TE>, dpm_launch_rescale<TS, TE>, dpm_launch_apg<TS, TE>},
+   dpm_table_launch_rescale<TS, TE>, dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>,                         \
+   dpm_launch_sample<TS, TE, DPM_F_CFG_APG>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -76,6 +77,77 @@ int launch_fused(const PairUnits& p, const dpm_stage* st, const dpm_buffers* bs,
   return p.fused(st, bs, n_req, stream, ev_start, ev_stop);
 }
 
+// The per-sample guidance flags (include/dpm_hip.h): a stage under one of them is a launch of its own kernel, one workgroup
+// per sample (dpm_sample_frame.hpp), never fused and never with device-resident coefficients.  What dpm_stage_launch asks of
+// such a stage is check_sample_guidance on the flag's row.
+struct SampleGuidance {
+  unsigned flag;
+  const char* name;                                      // ... in every message
+  int min_per;                                           // the smallest sample, in elements
+  unsigned banned;                                       // the flags its kernel has no path for
+  const char* banned_text;                               // ... as the message lists them
+  bool needs_x0;                                         // defined on the data prediction: DPM_F_TO_X0 is required
+  const char* f64_text;                                  // the double state's refusal, in brackets
+  int (*scalars)(const dpm_stage*, const dpm_buffers*);  // the checks of the flag's own fields
+  SampleFn PairUnits::*launch;
+};
+int check_rescale_scalars(const dpm_stage* st, const dpm_buffers*) {
+  if (!(st->cg_scale > 0.f && st->cg_scale <= 1.f))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE with phi=%g (dpm_stage.cg_scale), which is not in (0, 1]", (double)st->cg_scale);
+  return DPM_OK;
+}
+int check_apg_scalars(const dpm_stage* st, const dpm_buffers* b) {
+  const float eta = st->cg_scale, r = st->thr_ratio, beta = st->thr_max;
+  if (!(eta >= 0.f && eta <= 1.f))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with eta=%g (dpm_stage.cg_scale), which is not in [0, 1]", (double)eta);
+  if (!(r >= 0.f))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a norm threshold of %g (dpm_stage.thr_ratio), which is not >= 0", (double)r);
+  if (!(beta > -1.f && beta < 1.f))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum of %g (dpm_stage.thr_max), which is not in (-1, 1)", (double)beta);
+  if (beta != 0.f && !b->workspace)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum needs the running average in dpm_buffers.workspace");
+  return DPM_OK;
+}
+// DPM_F_CFG_APG first: a record that sets both flags (eta shares cg_scale with phi) is reported by that flag's checks
+constexpr SampleGuidance kSampleGuidance[] = {
+    {DPM_F_CFG_APG, "DPM_F_CFG_APG", 1, DPM_F_CFG_RESCALE | DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE,
+     "guidance rescale, thresholding, mask blend or noise", true, "no double kernel", check_apg_scalars, &PairUnits::apg},
+    {DPM_F_CFG_RESCALE, "DPM_F_CFG_RESCALE", 2, DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE, "thresholding, mask blend or noise", false,
+     "no double rescale kernel", check_rescale_scalars, &PairUnits::rescale},
+};
+// the row of a stage's per-sample guidance flag; nullptr: it has none
+const SampleGuidance* sample_guidance(unsigned flags) {
+  for (const SampleGuidance& g : kSampleGuidance)
+    if (flags & g.flag) return &g;
+  return nullptr;
+}
+
+// the checks of a stage under g.flag, in the order they speak (b->batch >= 1, n a multiple of it)
+int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dpm_buffers* b) {
+  auto fail = [&](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, g.name, args...); };
+  const int64_t per = b->n / b->batch;
+  if (st->guidance != DPM_GUIDE_CFG)
+    return fail(DPM_ERR_ARG, "stage_launch: %s is valid under classifier-free guidance only (guidance %d)", st->guidance);
+  if (b->n > 0 && per < g.min_per)  // (an empty batch is DPM_OK, as for every stage; its record is still checked)
+    return fail(DPM_ERR_ARG, "stage_launch: %s needs samples of at least %d element%s (got %lld)", g.min_per,
+                g.min_per == 1 ? "" : "s", (long long)per);
+  if (const int rc = g.scalars(st, b)) return rc;
+  // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
+  const bool known = st->form >= DPM_FORM_LIN1 && st->form <= DPM_FORM_UNIPC;
+  if (g.needs_x0) {  // what the flag is defined on comes before what it is combined with
+    if (!known) return dpm_set_error(DPM_ERR_ARG, "unknown update form %d", st->form);
+    if (!(st->flags & DPM_F_TO_X0)) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: %s without DPM_F_TO_X0 (it is defined on the data prediction)");
+  }
+  if (st->flags & g.banned) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: %s with %s (flags %u)", g.banned_text, st->flags);
+  if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: %s on a DPM_FORM_UNIPC stage");
+  if (!known) return dpm_set_error(DPM_ERR_ARG, "unknown update form %d", st->form);
+  if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+    return fail(DPM_ERR_UNSUPPORTED, "stage_launch: %s with a double state (%s)", g.f64_text);
+  if (b->eps_stride != 0 && b->eps_stride != per)
+    return fail(DPM_ERR_UNSUPPORTED, "stage_launch: %s with eps_stride=%lld (a channel slice of a wider output)", (long long)b->eps_stride);
+  return DPM_OK;
+}
+
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
 // base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base)
 int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false) {
@@ -85,56 +157,8 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
   if (b->noise_sample0 != 0 && !base_ok)
     return fail(DPM_ERR_ARG, "stage_launch: noise_sample0=%d (honoured by the SDE rows of a DPM_TABLE_NOISE call only)",
                 b->noise_sample0);
-  // guidance rescale (include/dpm_hip.h): one workgroup per sample, stage_rescale_kernel.  (Together with DPM_F_CFG_APG, whose
-  // eta shares cg_scale with phi, the pair is reported by that flag's checks below.)
-  if ((st->flags & DPM_F_CFG_RESCALE) && !(st->flags & DPM_F_CFG_APG)) {
-    const int64_t per = b->n / b->batch;
-    if (st->guidance != DPM_GUIDE_CFG)
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE is valid under classifier-free guidance only (guidance %d)", st->guidance);
-    if (b->n > 0 && per < 2)  // (an empty batch is DPM_OK below, as for every stage; its record is still checked)
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE needs samples of at least 2 elements (got %lld)", (long long)per);
-    if (!(st->cg_scale > 0.f && st->cg_scale <= 1.f))
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE with phi=%g (dpm_stage.cg_scale), which is not in (0, 1]", (double)st->cg_scale);
-    if (st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with thresholding, mask blend or noise (flags %u)", st->flags);
-    if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE on a DPM_FORM_UNIPC stage");
-    // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
-    if (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_DENOISE) return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
-    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with a double state (no double rescale kernel)");
-    if (b->eps_stride != 0 && b->eps_stride != per)
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with eps_stride=%lld (a channel slice of a wider output)",
-                  (long long)b->eps_stride);
-  }
-  if (st->flags & DPM_F_CFG_APG) {  // adaptive projected guidance (include/dpm_hip.h): one workgroup per sample, stage_apg_kernel
-    const int64_t per = b->n / b->batch;
-    const float eta = st->cg_scale, r = st->thr_ratio, beta = st->thr_max;
-    if (st->guidance != DPM_GUIDE_CFG)
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG is valid under classifier-free guidance only (guidance %d)", st->guidance);
-    if (b->n > 0 && per < 1)  // (an empty batch is DPM_OK below, as for every stage; its record is still checked)
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG needs samples of at least 1 element (got %lld)", (long long)per);
-    if (!(eta >= 0.f && eta <= 1.f))
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with eta=%g (dpm_stage.cg_scale), which is not in [0, 1]", (double)eta);
-    if (!(r >= 0.f))
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a norm threshold of %g (dpm_stage.thr_ratio), which is not >= 0", (double)r);
-    if (!(beta > -1.f && beta < 1.f))
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum of %g (dpm_stage.thr_max), which is not in (-1, 1)", (double)beta);
-    if (beta != 0.f && !b->workspace)
-      return fail(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum needs the running average in dpm_buffers.workspace");
-    // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
-    if (st->form != DPM_FORM_UNIPC && (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_DENOISE))
-      return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
-    if (!(st->flags & DPM_F_TO_X0))
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG without DPM_F_TO_X0 (it is defined on the data prediction)");
-    if (st->flags & (DPM_F_CFG_RESCALE | DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with guidance rescale, thresholding, mask blend or noise (flags %u)", st->flags);
-    if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG on a DPM_FORM_UNIPC stage");
-    if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with a double state (no double kernel)");
-    if (b->eps_stride != 0 && b->eps_stride != per)
-      return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with eps_stride=%lld (a channel slice of a wider output)",
-                  (long long)b->eps_stride);
-  }
+  if (const SampleGuidance* g = sample_guidance(st->flags))
+    if (const int rc = check_sample_guidance(*g, st, b)) return rc;
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -208,10 +232,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_NOISE with device-resident coefficients");
   if (dyn && st->form == DPM_FORM_UNIPC)
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with device-resident coefficients");
-  if (dyn && (st->flags & DPM_F_CFG_RESCALE))
-    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with device-resident coefficients");
-  if (dyn && (st->flags & DPM_F_CFG_APG))
-    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_APG with device-resident coefficients");
+  const SampleGuidance* const g = sample_guidance(st->flags);
+  if (dyn && g) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: %s with device-resident coefficients", g->name);
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -222,8 +244,7 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   }
   const PairUnits* p = pair_of(sd, ed);
   if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
-  if (st->flags & DPM_F_CFG_APG) return p->apg(st, &bb, stream, ev_start, ev_stop);
-  if (st->flags & DPM_F_CFG_RESCALE) return p->rescale(st, &bb, stream, ev_start, ev_stop);
+  if (g) return (p->*g->launch)(st, &bb, stream, ev_start, ev_stop);
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused

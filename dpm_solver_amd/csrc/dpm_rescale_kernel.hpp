@@ -1,72 +1,27 @@
 // dpm_rescale_kernel.hpp -- classifier-free guidance with guidance rescale (DPM_F_CFG_RESCALE, include/dpm_hip.h; Lin et al.
 // 2023, section 3.4): stage_rescale_kernel, a stage kernel that owns a whole SAMPLE, and its launcher.  Included by unit E of
-// dpm_stage_unit.hip behind dpm_device.hpp -- and by unit F for the frame alone (rescale_index / rescale_load / rescale_store,
-// dpm_apg_kernel.hpp; it instantiates no kernel of this file) -- so that every other unit compiles to the code it compiled to.
+// dpm_stage_unit.hip behind dpm_sample_frame.hpp -- the workgroup, the lane-to-element map, the masked loads and stores, the
+// reduction, the two access paths -- and by nothing else, so that every other unit compiles to the code it compiled to.
 //
 // The streaming kernels have no notion of a sample; the rescale needs the standard deviation of the guided and of the
-// conditional output over each one.  One workgroup of 512 threads per sample, grid = batch:
+// conditional output over each one.  One workgroup per sample, grid = batch:
 //   pass 1   the sample's two raw outputs -> the guided output g, four sums in double per thread (shifted by the sample's first
-//            element: a constant sample gives exact zeros), reduced across the wavefront by cross-lane exchange and across the
-//            eight wavefronts through LDS behind ONE barrier; every thread then forms the same f = std_c / std_g
+//            element: a constant sample gives exact zeros), reduced (sf_reduce); every thread then forms the same
+//            f = std_c / std_g
 //   pass 2   r = phi * (g * f) + (1 - phi) * g, then the stage proper -- conversion, eps -> x0, update form, stores -- on the sample
 // Form, model type and prologue are read from the stage record (FORM_RT, PM_RT): one instantiation per dtype pair.
-// A workgroup depends on nothing outside itself: no cluster, no workspace, no wait.  Every thread reaches the barrier; a ragged
-// tail masks loads and stores, never control flow around it.
-//   register path  a sample of at most RS_KEEP_MAX = 16384 elements (SD's [4,64,64]): 32 elements per thread and tensor, the two
-//                  outputs stay in registers between the passes (non-temporal loads: nothing reads them again)
-//   re-read path   larger samples: pass 2 reads the outputs again, so pass 1 loads them with the default cache policy and the
-//                  second read comes from L2
-// Access: 8 consecutive elements per lane and 16-byte accesses where the sample is whole 8-element groups and every operand is
-// 16-byte aligned (`vec`), else one element per lane (ragged samples, views with offsets).  2-byte states leave by the
-// write-through stores of the streaming kernels; a 4-byte state's 32 bytes per lane are two instructions that each fill every
-// other 16 bytes, which stay cached stores as in the extended streaming kernels (dpm_access.hpp: store_pack).
+//   register path  the two outputs stay in registers between the passes (non-temporal loads: nothing reads them again)
+//   re-read path   pass 2 reads the outputs again, so pass 1 loads them with the default cache policy and the second read
+//                  comes from L2
 #pragma once
 
 namespace {
-
-constexpr int RS_THREADS = 512, RS_WAVES = RS_THREADS / 64;
-constexpr int RS_CHUNK = RS_THREADS * EPT;         // elements of one workgroup iteration
-constexpr int RS_KEEP_CHUNKS = 4;                  // iterations whose outputs the register path holds
-constexpr int64_t RS_KEEP_MAX = (int64_t)RS_CHUNK * RS_KEEP_CHUNKS;
 
 // the classifier-free blend of the RAW outputs: three half operations for a 2-byte noise-prediction network, as prologue()
 template <typename TE>
 __device__ __forceinline__ float rescale_guided(float oc, float ou, const KParams& p) {
   if (sizeof(TE) == 2 && p.model_type == DPM_MODEL_NOISE) return round_as<TE>(ou + round_as<TE>(p.cfg_scale * round_as<TE>(oc - ou)));
   return ou + p.cfg_scale * (oc - ou);
-}
-
-// element j of this lane in iteration k, relative to the sample
-template <bool VEC>
-__device__ __forceinline__ int64_t rescale_index(int64_t k, int j) {
-  return VEC ? k * RS_CHUNK + (int64_t)threadIdx.x * EPT + j : k * RS_CHUNK + (int64_t)j * RS_THREADS + threadIdx.x;
-}
-// the lane's 8 elements of iteration k; elements past the sample read a clamped (valid) address and are masked by the caller
-template <bool VEC, bool NT, typename T>
-__device__ __forceinline__ void rescale_load(const T* __restrict__ s, int64_t k, int64_t per, float (&out)[EPT]) {
-  if constexpr (VEC) {
-    const int64_t gi = k * RS_THREADS + threadIdx.x, ng = per / EPT;
-    load_pack<NT>(s, gi < ng ? gi : ng - 1, out);
-  } else {
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-      const int64_t i = rescale_index<false>(k, j);
-      out[j] = to_f32(s[i < per ? i : per - 1]);
-    }
-  }
-}
-template <bool VEC, typename T>
-__device__ __forceinline__ void rescale_store(T* __restrict__ s, int64_t k, int64_t per, const float (&in)[EPT]) {
-  if constexpr (VEC) {
-    const int64_t gi = k * RS_THREADS + threadIdx.x;
-    if (gi < per / EPT) store_pack<false, true>(s, gi, in);
-  } else {
-#pragma unroll
-    for (int j = 0; j < EPT; ++j) {
-      const int64_t i = rescale_index<false>(k, j);
-      if (i < per) s[i] = from_f32<T>(in[j]);
-    }
-  }
 }
 
 // the four sums of one iteration's elements: S1, S2 of the conditional output (acc[0], acc[1]) and of the guided one
@@ -76,7 +31,7 @@ __device__ __forceinline__ void rescale_accumulate(const float (&vc)[EPT], const
                                                    float g0, const KParams& p, double (&acc)[4]) {
 #pragma unroll
   for (int j = 0; j < EPT; ++j) {
-    const bool valid = rescale_index<VEC>(k, j) < per;
+    const bool valid = sf_index<VEC>(k, j) < per;
     const double dc = valid ? (double)vc[j] - (double)oc0 : 0.0;
     const double dg = valid ? (double)rescale_guided<TE>(vc[j], vu[j], p) - (double)g0 : 0.0;
     acc[0] += dc;
@@ -104,10 +59,10 @@ __device__ __forceinline__ void rescale_update(const float (&vc)[EPT], const flo
   // (the rescaled output is an fp32 tensor whatever the network's dtype: no difference of two model values is a half operation)
   const float phi = p.cg_scale, rest = 1.f - phi;
   float vx[EPT], vxe[EPT], vh1[EPT], vh2[EPT], ox[EPT], om[EPT];
-  if (nx || (need_xe && !sep)) rescale_load<VEC, true>(x, k, per, vx);
-  if (need_xe && sep) rescale_load<VEC, true>(xe, k, per, vxe);
-  if (nh1) rescale_load<VEC, true>(h1, k, per, vh1);
-  if (nh2) rescale_load<VEC, true>(h2, k, per, vh2);
+  if (nx || (need_xe && !sep)) sf_load<VEC, true>(x, k, per, vx);
+  if (need_xe && sep) sf_load<VEC, true>(xe, k, per, vxe);
+  if (nh1) sf_load<VEC, true>(h1, k, per, vh1);
+  if (nh2) sf_load<VEC, true>(h2, k, per, vh2);
 #pragma unroll
   for (int j = 0; j < EPT; ++j) {
     const float xv = (nx || (need_xe && !sep)) ? vx[j] : 0.f;
@@ -119,64 +74,49 @@ __device__ __forceinline__ void rescale_update(const float (&vc)[EPT], const flo
     om[j] = mn;
     ox[j] = combine_any<FORM_RT, float, TE>(nx ? xv : 0.f, mn, nh1 ? vh1[j] : 0.f, nh2 ? vh2[j] : 0.f, p, false);
   }
-  rescale_store<VEC>(xo, k, per, ox);
-  if (xo2) rescale_store<VEC>(xo2, k, per, ox);
-  if (p.flags & DPM_F_STORE_M) rescale_store<VEC>(mo, k, per, om);
+  sf_store<VEC>(xo, k, per, ox);
+  if (xo2) sf_store<VEC>(xo2, k, per, ox);
+  if (p.flags & DPM_F_STORE_M) sf_store<VEC>(mo, k, per, om);
 }
 
-// one sample, both passes.  KEEP: the register path (per <= RS_KEEP_MAX).  Called by every thread of the workgroup with
+// one sample, both passes.  KEEP: the register path (per <= SF_KEEP_MAX).  Called by every thread of the workgroup with
 // workgroup-uniform template arguments: the barrier inside is reached by all of them.
 template <bool VEC, bool KEEP, typename TS, typename TE>
 __device__ __forceinline__ void rescale_sample(const TS* __restrict__ x, const TS* __restrict__ xe, const TE* __restrict__ e0,
                                                const TE* __restrict__ e1, const TS* __restrict__ h1, const TS* __restrict__ h2,
                                                TS* __restrict__ xo, TS* __restrict__ mo, TS* __restrict__ xo2, int64_t per,
                                                const KParams& p, double* red) {
-  const int64_t nchunks = (per + RS_CHUNK - 1) / RS_CHUNK;
+  const int64_t nchunks = (per + SF_CHUNK - 1) / SF_CHUNK;
   const float oc0 = to_f32(e0[0]), g0 = rescale_guided<TE>(oc0, to_f32(e1[0]), p);
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
-  float kc[KEEP ? RS_KEEP_CHUNKS : 1][EPT], ku[KEEP ? RS_KEEP_CHUNKS : 1][EPT];
+  float kc[KEEP ? SF_KEEP_CHUNKS : 1][EPT], ku[KEEP ? SF_KEEP_CHUNKS : 1][EPT];
   if constexpr (KEEP) {
 #pragma unroll
-    for (int k = 0; k < RS_KEEP_CHUNKS; ++k) {  // every load of the sample's outputs in flight before the first use
-      rescale_load<VEC, true>(e0, k, per, kc[k]);
-      rescale_load<VEC, true>(e1, k, per, ku[k]);
+    for (int k = 0; k < SF_KEEP_CHUNKS; ++k) {  // every load of the sample's outputs in flight before the first use
+      sf_load<VEC, true>(e0, k, per, kc[k]);
+      sf_load<VEC, true>(e1, k, per, ku[k]);
     }
 #pragma unroll
-    for (int k = 0; k < RS_KEEP_CHUNKS; ++k) rescale_accumulate<VEC, TE>(kc[k], ku[k], k, per, oc0, g0, p, acc);
+    for (int k = 0; k < SF_KEEP_CHUNKS; ++k) rescale_accumulate<VEC, TE>(kc[k], ku[k], k, per, oc0, g0, p, acc);
   } else {
     for (int64_t k = 0; k < nchunks; ++k) {
-      rescale_load<VEC, false>(e0, k, per, kc[0]);  // default cache policy: pass 2 reads these lines again
-      rescale_load<VEC, false>(e1, k, per, ku[0]);
+      sf_load<VEC, false>(e0, k, per, kc[0]);  // default cache policy: pass 2 reads these lines again
+      sf_load<VEC, false>(e1, k, per, ku[0]);
       rescale_accumulate<VEC, TE>(kc[0], ku[0], k, per, oc0, g0, p, acc);
     }
   }
-  // across the wavefront by cross-lane exchange, across the wavefronts through LDS; every thread sums the eight partial
-  // sums in the same order and holds the same f
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off, 64);
-  const int wave = (int)(threadIdx.x >> 6);
-  if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) red[wave * 4 + q] = acc[q];
-  }
-  __syncthreads();
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int w = 0; w < RS_WAVES; ++w)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) s[q] += red[w * 4 + q];
+  double s[4];  // every thread holds the same sums, hence the same f
+  sf_reduce(acc, red, s);
   const double P = (double)per;
   const float f = (float)(rescale_std(s[0], s[1], P) / rescale_std(s[2], s[3], P));
   if constexpr (KEEP) {
 #pragma unroll
-    for (int k = 0; k < RS_KEEP_CHUNKS; ++k)
+    for (int k = 0; k < SF_KEEP_CHUNKS; ++k)
       if ((int64_t)k < nchunks) rescale_update<VEC, TS, TE>(kc[k], ku[k], x, xe, h1, h2, xo, mo, xo2, k, per, f, p);
   } else {
     for (int64_t k = 0; k < nchunks; ++k) {
-      rescale_load<VEC, true>(e0, k, per, kc[0]);
-      rescale_load<VEC, true>(e1, k, per, ku[0]);
+      sf_load<VEC, true>(e0, k, per, kc[0]);
+      sf_load<VEC, true>(e1, k, per, ku[0]);
       rescale_update<VEC, TS, TE>(kc[0], ku[0], x, xe, h1, h2, xo, mo, xo2, k, per, f, p);
     }
   }
@@ -185,12 +125,12 @@ __device__ __forceinline__ void rescale_sample(const TS* __restrict__ x, const T
 // x: the state the update starts from (the evaluation state where the form reads none), xe: the state the network saw (= x when
 // there is no separate one); h1 / h2 / mo / xo2 may be null where the stage does not name them.  `vec`: 16-byte accesses.
 template <typename TS, typename TE>
-__global__ __launch_bounds__(RS_THREADS) void stage_rescale_kernel(const TS* __restrict__ x, const TS* __restrict__ xe,
+__global__ __launch_bounds__(SF_THREADS) void stage_rescale_kernel(const TS* __restrict__ x, const TS* __restrict__ xe,
                                                                    const TE* __restrict__ e0, const TE* __restrict__ e1,
                                                                    const TS* __restrict__ h1, const TS* __restrict__ h2,
                                                                    TS* __restrict__ xo, TS* __restrict__ mo, TS* __restrict__ xo2,
                                                                    int64_t per, const KParams p, int vec) {
-  __shared__ double red[RS_WAVES * 4];
+  __shared__ double red[SF_WAVES * 4];
   const int64_t base = (int64_t)blockIdx.x * per;  // this workgroup's sample
   if (x) x += base;
   if (xe) xe += base;
@@ -201,7 +141,7 @@ __global__ __launch_bounds__(RS_THREADS) void stage_rescale_kernel(const TS* __r
   xo += base;
   if (mo) mo += base;
   if (xo2) xo2 += base;
-  const bool keep = per <= RS_KEEP_MAX;
+  const bool keep = per <= SF_KEEP_MAX;
   if (vec) {
     if (keep) rescale_sample<true, true>(x, xe, e0, e1, h1, h2, xo, mo, xo2, per, p, red);
     else rescale_sample<true, false>(x, xe, e0, e1, h1, h2, xo, mo, xo2, per, p, red);
@@ -211,21 +151,11 @@ __global__ __launch_bounds__(RS_THREADS) void stage_rescale_kernel(const TS* __r
   }
 }
 
-// the launch of one flagged stage (checked by dpm_stage_launch: CFG, P >= 2, phi, no thresholding / blend / noise / UniPC /
-// double state / strided outputs / device-resident coefficients)
+// this unit's launch of one flagged stage (checked by dpm_stage_launch: kSampleGuidance, dpm_kernels.hip)
 template <typename TS, typename TE>
-int launch_rescale_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& c) {
-  const Operands<TS, TE> op(st, b);
-  const int64_t per = b->n / b->batch;
-  if (b->batch > (int64_t)0x7fffffff)
-    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with a batch of %lld (one workgroup per sample)",
-                         (long long)b->batch);
-  TS* const xo2 = static_cast<TS*>(b->x_out2);
-  const bool vec = per % EPT == 0 && aligned(op.x, 16) && aligned(op.xe, 16) && aligned(op.h1, 16) && aligned(op.h2, 16) &&
-                   aligned(op.xo, 16) && aligned(op.mo, 16) && aligned(xo2, 16) && aligned(op.e0, 16) && aligned(op.e1, 16);
-  launch(stage_rescale_kernel<TS, TE>, dim3((unsigned)b->batch), dim3(RS_THREADS), 0, c, op.x, op.xe ? op.xe : op.x, op.e0, op.e1,
-         op.h1, op.h2, op.xo, op.mo, xo2, per, op.p, vec ? 1 : 0);
-  return launch_status("rescale stage kernel launch failed");
+int launch_sample_typed(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& c) {
+  return launch_sample_stage<TS, TE>(stage_rescale_kernel<TS, TE>, "DPM_F_CFG_RESCALE", "rescale stage kernel launch failed", st, b, c,
+                                     nullptr);
 }
 
 }  // namespace

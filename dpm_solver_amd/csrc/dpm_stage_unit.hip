@@ -12,9 +12,9 @@
 //   unit E (4): the launch of a guidance-rescale stage (stage_rescale_kernel, DPM_F_CFG_RESCALE; dpm_rescale_kernel.hpp, which
 //               no other unit includes) and of the table's guidance-rescale rows (stage_rescale_kernel_table, DPM_TABLE_RESCALE;
 //               dpm_table_rescale.hpp) and nothing else -- units A to D compile to the code they compiled to before it existed
-//   unit F (5): the launch of an adaptive-projected-guidance stage (stage_apg_kernel, DPM_F_CFG_APG; dpm_apg_kernel.hpp on the
-//               frame of dpm_rescale_kernel.hpp, none of whose kernels it instantiates) and nothing else -- units A to E compile
-//               to the code they compiled to before it existed
+//   unit F (5): the launch of an adaptive-projected-guidance stage (stage_apg_kernel, DPM_F_CFG_APG; dpm_apg_kernel.hpp, which
+//               no other unit includes) and nothing else -- units A to E compile to the code they compiled to before it existed
+// Units E and F are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
 #error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5>"
@@ -24,11 +24,12 @@
 #endif
 #include "dpm_device.hpp"
 #if DPM_UNIT == 4
+#include "dpm_sample_frame.hpp"
 #include "dpm_rescale_kernel.hpp"
 #include "dpm_table_rescale.hpp"
 #endif
 #if DPM_UNIT == 5
-#include "dpm_rescale_kernel.hpp"
+#include "dpm_sample_frame.hpp"
 #include "dpm_apg_kernel.hpp"
 #endif
 
@@ -122,27 +123,22 @@ int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req
 template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif
 
-#if DPM_UNIT == 4
-template <typename TS, typename TE>
-int dpm_launch_rescale(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
+// The launch of a per-sample guidance stage (dpm_kernels.hip: kSampleGuidance), FLAG the unit's own.
+#if DPM_UNIT == 4 || DPM_UNIT == 5
+template <typename TS, typename TE, unsigned FLAG>
+int dpm_launch_sample(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
-  return launch_rescale_typed<TS, TE>(st, b, s);
+  return launch_sample_typed<TS, TE>(st, b, s);  // (the one of the unit's kernel header)
 }
-template int dpm_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
+template int dpm_launch_sample<State, Eps, DPM_UNIT == 4 ? DPM_F_CFG_RESCALE : DPM_F_CFG_APG>(const dpm_stage*, const dpm_buffers*,
+                                                                                             void*, void*, void*);
+#endif
 
+#if DPM_UNIT == 4
 template <typename TS, typename TE>
 int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void*, void* stream) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
   return launch_table_rescale_typed<TS, TE>(st, bs, n_req, rows, s);
 }
 template int dpm_table_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
-#endif
-
-#if DPM_UNIT == 5
-template <typename TS, typename TE>
-int dpm_launch_apg(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
-  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
-  return launch_apg_typed<TS, TE>(st, b, s);
-}
-template int dpm_launch_apg<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 #endif

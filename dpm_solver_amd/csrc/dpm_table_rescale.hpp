@@ -1,5 +1,6 @@
 // dpm_table_rescale.hpp -- guidance-rescale rows of the table-driven launch (DPM_TABLE_RESCALE): stage_rescale_kernel_table and
-// its launcher.  Included by unit E of dpm_stage_unit.hip behind dpm_rescale_kernel.hpp and by nothing else.
+// its launcher.  Included by unit E of dpm_stage_unit.hip behind dpm_sample_frame.hpp and dpm_rescale_kernel.hpp and by nothing
+// else.
 #pragma once
 
 namespace {
@@ -19,8 +20,8 @@ namespace {
 // Every sample gets the bits of its request's own launch: the sums are added in the same order by the same source.
 // ------------------------------------------------------------------------------------------------
 template <typename TS, typename TE>
-__global__ __launch_bounds__(RS_THREADS) void stage_rescale_kernel_table(const TableRow* __restrict__ rows, int64_t per, uint32_t bpr) {
-  __shared__ double red[RS_WAVES * 4];
+__global__ __launch_bounds__(SF_THREADS) void stage_rescale_kernel_table(const TableRow* __restrict__ rows, int64_t per, uint32_t bpr) {
+  __shared__ double red[SF_WAVES * 4];
   const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x / bpr));
   const int64_t base = (int64_t)(blockIdx.x - r * bpr) * per;  // this workgroup's sample of row r
   const TableRow& row = rows[r];
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(RS_THREADS) void stage_rescale_kernel_table(const T
   xo += base;
   if (mo) mo += base;
   if (xo2) xo2 += base;
-  if (per <= RS_KEEP_MAX) rescale_sample<true, true>(x, x, e0, e1, h1, h2, xo, mo, xo2, per, p, red);
+  if (per <= SF_KEEP_MAX) rescale_sample<true, true>(x, x, e0, e1, h1, h2, xo, mo, xo2, per, p, red);
   else rescale_sample<true, false>(x, x, e0, e1, h1, h2, xo, mo, xo2, per, p, red);
 }
 
@@ -55,7 +56,7 @@ int launch_table_rescale_typed(const dpm_stage* st, const dpm_buffers* bs, int n
     if (!rescale_row_ok(st[r], bs[r]) || bs[r].n != bs[0].n || bs[r].batch != bs[0].batch)
       return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: a stage that is no guidance-rescale row of this group in a table rescale launch");
   const int64_t batch = bs[0].batch, per = bs[0].n / batch;
-  launch(stage_rescale_kernel_table<TS, TE>, dim3((unsigned)((int64_t)n_req * batch)), dim3(RS_THREADS), 0, c,
+  launch(stage_rescale_kernel_table<TS, TE>, dim3((unsigned)((int64_t)n_req * batch)), dim3(SF_THREADS), 0, c,
          static_cast<const TableRow*>(rows), per, (uint32_t)batch);
   return launch_status("table rescale stage kernel launch failed");
 }

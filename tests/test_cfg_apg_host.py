@@ -394,6 +394,72 @@ def test_argument_errors_are_decided_before_hip(kw, code, text):
         L.check(code)
 
 
+PRE = "stage_launch: DPM_F_CFG_APG "
+BOTH = X0M | L.F_CFG_RESCALE
+TEXTS = [   # every refusal of the flag, in the order dpm_stage_launch asks: return code and the whole message
+    (dict(guidance=L.GUIDE["classifier"]), L.ERR_ARG, PRE + "is valid under classifier-free guidance only (guidance 2)"),
+    (dict(eta=1.5), L.ERR_ARG, PRE + "with eta=1.5 (dpm_stage.cg_scale), which is not in [0, 1]"),
+    (dict(r=-1.0), L.ERR_ARG, PRE + "with a norm threshold of -1 (dpm_stage.thr_ratio), which is not >= 0"),
+    (dict(beta=1.0), L.ERR_ARG, PRE + "with a momentum of 1 (dpm_stage.thr_max), which is not in (-1, 1)"),
+    (dict(ws=False), L.ERR_ARG, PRE + "with a momentum needs the running average in dpm_buffers.workspace"),
+    (dict(form=6), L.ERR_ARG, "unknown update form 6"),
+    (dict(flags=L.F_STORE_M | L.F_CFG_APG), L.ERR_UNSUPPORTED, PRE + "without DPM_F_TO_X0 (it is defined on the data prediction)"),
+    (dict(flags=X0M | L.F_THRESH), L.ERR_UNSUPPORTED,
+     PRE + "with guidance rescale, thresholding, mask blend or noise (flags 2059)"),
+    (dict(form=L.FORM_UNIPC), L.ERR_UNSUPPORTED, PRE + "on a DPM_FORM_UNIPC stage"),
+    (dict(dtype=L.DTYPE_F64), L.ERR_UNSUPPORTED, PRE + "with a double state (no double kernel)"),
+    (dict(stride=40), L.ERR_UNSUPPORTED, PRE + "with eps_stride=40 (a channel slice of a wider output)"),
+    # both guidance flags: this flag's checks speak, whatever phi / eta is, and none of the other flag's
+    (dict(flags=BOTH), L.ERR_UNSUPPORTED, PRE + "with guidance rescale, thresholding, mask blend or noise (flags 3075)"),
+    (dict(flags=BOTH, eta=0.0), L.ERR_UNSUPPORTED, PRE + "with guidance rescale, thresholding, mask blend or noise (flags 3075)"),
+    (dict(flags=BOTH, eta=1.5), L.ERR_ARG, PRE + "with eta=1.5 (dpm_stage.cg_scale), which is not in [0, 1]"),
+    (dict(flags=BOTH, guidance=0), L.ERR_ARG, PRE + "is valid under classifier-free guidance only (guidance 0)"),
+    (dict(flags=BOTH & ~L.F_TO_X0), L.ERR_UNSUPPORTED, PRE + "without DPM_F_TO_X0 (it is defined on the data prediction)"),
+    # ... and which of two speaks first: each row fails the check of its own line and every later one it can
+    (dict(guidance=0, eta=NAN, r=NAN, beta=NAN, ws=False, form=6, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_ARG, PRE + "is valid under classifier-free guidance only (guidance 0)"),
+    (dict(eta=NAN, r=NAN, beta=NAN, ws=False, form=6, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_ARG, PRE + "with eta=nan (dpm_stage.cg_scale), which is not in [0, 1]"),
+    (dict(r=NAN, beta=NAN, ws=False, form=6, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_ARG, PRE + "with a norm threshold of nan (dpm_stage.thr_ratio), which is not >= 0"),
+    (dict(beta=NAN, ws=False, form=6, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_ARG, PRE + "with a momentum of nan (dpm_stage.thr_max), which is not in (-1, 1)"),
+    (dict(ws=False, form=6, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_ARG, PRE + "with a momentum needs the running average in dpm_buffers.workspace"),
+    (dict(form=-1, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40), L.ERR_ARG, "unknown update form -1"),
+    (dict(form=L.FORM_UNIPC, flags=L.F_CFG_APG | L.F_NOISE, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_UNSUPPORTED, PRE + "without DPM_F_TO_X0 (it is defined on the data prediction)"),
+    (dict(form=L.FORM_UNIPC, flags=X0M | L.F_BLEND, dtype=L.DTYPE_F64, stride=40),
+     L.ERR_UNSUPPORTED, PRE + "with guidance rescale, thresholding, mask blend or noise (flags 2083)"),
+    (dict(form=L.FORM_UNIPC, dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED, PRE + "on a DPM_FORM_UNIPC stage"),
+    (dict(dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED, PRE + "with a double state (no double kernel)"),
+]
+
+
+@pytest.mark.parametrize("kw,code,text", TEXTS, ids=[str(i) for i in range(len(TEXTS))])
+def test_every_refusal_keeps_its_code_its_text_and_its_turn(kw, code, text):
+    kw = dict(kw)
+    stride = kw.pop("stride", 0)
+    st, b, arena = _record(**kw)
+    b.eps_stride = stride
+    assert L.lib.dpm_stage_launch(C.byref(st), C.byref(b), None) == code
+    assert L.lib.dpm_last_error().decode() == text and not arena.any()
+
+
+def test_device_resident_coefficients_are_refused_in_so_many_words():
+    """dpm_adaptive_stage_launch hands the stage the ADDRESS of a coefficient record in the handle's device block and refuses
+    the flag before anything reads it: zeroed host memory stands in for the handle (no device to create one on), so that the
+    address is a small number nobody follows"""
+    st, b, arena = _record()
+    handle = np.zeros(1 << 16, dtype=np.uint8)
+    assert L.lib.dpm_adaptive_stage_launch(handle.ctypes.data, 1, C.byref(st), C.byref(b), None) == L.ERR_UNSUPPORTED
+    assert L.lib.dpm_last_error().decode() == PRE + "with device-resident coefficients"
+    assert not arena.any() and not handle.any()
+    st.flags |= L.F_CFG_RESCALE                         # the record's own errors come first: here, the two flags together
+    assert L.lib.dpm_adaptive_stage_launch(handle.ctypes.data, 1, C.byref(st), C.byref(b), None) == L.ERR_UNSUPPORTED
+    assert L.lib.dpm_last_error().decode() == PRE + "with guidance rescale, thresholding, mask blend or noise (flags 3075)"
+
+
 def test_an_empty_batch_is_ok_and_its_record_is_still_checked():
     st, b, _ = _record(n=0, batch=1)
     assert L.lib.dpm_stage_launch(C.byref(st), C.byref(b), None) == 0

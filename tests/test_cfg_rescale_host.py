@@ -266,6 +266,62 @@ def test_argument_errors_are_decided_before_hip(kw, code, text):
         L.check(code)
 
 
+RS = L.F_TO_X0 | L.F_CFG_RESCALE
+TEXTS = [   # every refusal of the flag, in the order dpm_stage_launch asks: return code and the whole message
+    (dict(guidance=L.GUIDE["classifier"]), L.ERR_ARG,
+     "stage_launch: DPM_F_CFG_RESCALE is valid under classifier-free guidance only (guidance 2)"),
+    (dict(n=3, batch=3), L.ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE needs samples of at least 2 elements (got 1)"),
+    (dict(phi=1.5), L.ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE with phi=1.5 (dpm_stage.cg_scale), which is not in (0, 1]"),
+    (dict(flags=RS | L.F_THRESH), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE with thresholding, mask blend or noise (flags 1033)"),
+    (dict(form=L.FORM_UNIPC), L.ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE on a DPM_FORM_UNIPC stage"),
+    (dict(form=6), L.ERR_ARG, "unknown update form 6"),
+    (dict(dtype=L.DTYPE_F64), L.ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG_RESCALE with a double state (no double rescale kernel)"),
+    (dict(stride=40), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE with eps_stride=40 (a channel slice of a wider output)"),
+    # ... and which of two speaks first: each row fails the check of its own line and every later one it can
+    (dict(guidance=0, n=3, batch=3, phi=0.0, flags=RS | L.F_NOISE, form=6, dtype=L.DTYPE_F64, stride=40), L.ERR_ARG,
+     "stage_launch: DPM_F_CFG_RESCALE is valid under classifier-free guidance only (guidance 0)"),
+    (dict(n=3, batch=3, phi=0.0, flags=RS | L.F_NOISE, form=6, dtype=L.DTYPE_F64, stride=40), L.ERR_ARG,
+     "stage_launch: DPM_F_CFG_RESCALE needs samples of at least 2 elements (got 1)"),
+    (dict(phi=0.0, flags=RS | L.F_NOISE, form=6, dtype=L.DTYPE_F64, stride=40), L.ERR_ARG,
+     "stage_launch: DPM_F_CFG_RESCALE with phi=0 (dpm_stage.cg_scale), which is not in (0, 1]"),
+    (dict(flags=RS | L.F_NOISE, form=6, dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE with thresholding, mask blend or noise (flags 1089)"),
+    (dict(flags=RS | L.F_BLEND, form=L.FORM_UNIPC, dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE with thresholding, mask blend or noise (flags 1057)"),
+    (dict(form=L.FORM_UNIPC, dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE on a DPM_FORM_UNIPC stage"),
+    (dict(form=-1, dtype=L.DTYPE_F64, stride=40), L.ERR_ARG, "unknown update form -1"),
+    (dict(dtype=L.DTYPE_F64, stride=40), L.ERR_UNSUPPORTED,
+     "stage_launch: DPM_F_CFG_RESCALE with a double state (no double rescale kernel)"),
+]
+
+
+@pytest.mark.parametrize("kw,code,text", TEXTS, ids=[str(i) for i in range(len(TEXTS))])
+def test_every_refusal_keeps_its_code_its_text_and_its_turn(kw, code, text):
+    kw = dict(kw)
+    stride = kw.pop("stride", 0)
+    st, b, arena = _record(**kw)
+    b.eps_stride = stride
+    assert L.lib.dpm_stage_launch(C.byref(st), C.byref(b), None) == code
+    assert L.lib.dpm_last_error().decode() == text and not arena.any()
+
+
+def test_device_resident_coefficients_are_refused_in_so_many_words():
+    """dpm_adaptive_stage_launch hands the stage the ADDRESS of a coefficient record in the handle's device block and refuses
+    the flag before anything reads it: zeroed host memory stands in for the handle (no device to create one on), so that the
+    address is a small number nobody follows"""
+    st, b, arena = _record()
+    handle = np.zeros(1 << 16, dtype=np.uint8)
+    assert L.lib.dpm_adaptive_stage_launch(handle.ctypes.data, 1, C.byref(st), C.byref(b), None) == L.ERR_UNSUPPORTED
+    assert L.lib.dpm_last_error().decode() == "stage_launch: DPM_F_CFG_RESCALE with device-resident coefficients"
+    assert not arena.any() and not handle.any()
+    st.cg_scale = 1.5                                   # the record's own errors come first
+    assert L.lib.dpm_adaptive_stage_launch(handle.ctypes.data, 1, C.byref(st), C.byref(b), None) == L.ERR_ARG
+    assert "not in (0, 1]" in L.lib.dpm_last_error().decode()
+
+
 def test_an_empty_batch_is_ok_and_its_record_is_still_checked():
     """n == 0 launches nothing and returns DPM_OK, as for every stage (the sample-size rule has no sample to apply to);
     the record's own errors are reported all the same"""
