@@ -9,6 +9,7 @@ writes of these names here, so `solver._stage_launch_raw = shim` keeps working.
 
 `ref :NNN` = line in the reference's dpm_solver_pytorch.py.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -48,6 +49,12 @@ def _launch_ctx(dev):
     """(hipStream_t, device index, stream is capturing, device is not the current one) for launches on `dev`"""
     stream, idx = _raw_stream(dev)
     return stream, idx, torch.cuda.is_current_stream_capturing(), idx != torch.cuda.current_device()
+
+
+def _on_device(idx, other):
+    """the context for launches on device `idx` (`idx`, `other`: _launch_ctx's): it becomes the current device for their
+    duration when it is not already"""
+    return torch.cuda.device(idx) if other else contextlib.nullcontext()
 
 
 # the C entry point the prebuilt launch records of _FastRun go through (a module attribute so that the CPU test suite

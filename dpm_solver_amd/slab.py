@@ -104,6 +104,7 @@ Guarantee: every result is bit-identical to `sample(x, ...)` on the request alon
 guidance scale and `cfg_rescale(..., phi)`, for any b, whichever rows it landed in.
 """
 import ctypes as C
+import math
 import numbers
 
 import numpy as np
@@ -123,6 +124,43 @@ _BUFS = np.dtype(dict(names=[{"_ns0": "noise_sample0"}.get(n, n) for n, _ in L.B
                       formats=[{4: np.int32, 8: np.uint64}[getattr(L.Buffers, n).size] for n, _ in L.Buffers._fields_],
                       offsets=[getattr(L.Buffers, n).offset for n, _ in L.Buffers._fields_], itemsize=C.sizeof(L.Buffers)))
 assert _STAGE.itemsize == C.sizeof(L.Stage)
+
+# What a row holds: (name, numpy dtype, idle value).  The pool keeps one array `_<name>` of S entries per field, and admission
+# resets EVERY field of the rows it takes to the idle value before it writes the request's own: a row that passes from a
+# request of one kind to a request of another carries nothing over, and a field added here cannot forget its reset.
+_ROW = (
+    ("req", np.int64, -1),       # its request's handle (-1: idle)
+    ("off", np.int64, 0),        # its plan's offset into the record array
+    ("pos", np.int64, 0),        # its position in its plan
+    ("len", np.int64, 0),        # its plan's length
+    ("samp", np.int32, 0),       # the sample of its request it holds: request rows[k] holds sample k
+    # SDE rows (see "SDE requests" below)
+    ("optp", np.uint64, 0),      # its request's dpm_launch_opts (0: the solver's)
+    ("seed", np.uint64, 0),      # its request's seed
+    # per-request guidance (see "per-request guidance" below)
+    ("gon", np.bool_, False),    # does its request bring its own guidance (submit's guidance_scale= / guidance_rescale=)?
+    ("gs", np.float32, 0),       # its guidance scale
+    ("gphi", np.float32, 0),     # its phi
+    # inpainting rows (see "inpainting requests" below)
+    ("bslot", np.int64, -1),     # the first row of its inpainting request: where _brec holds its blend records (-1: none)
+    ("bmask", np.uint64, 0),     # the mask of its sample
+    ("bper", np.int64, 0),       # its mask period
+)
+
+# The first-submit check of a sample's element count, per kind the pool was built with, in this order: (the pool's switch, the
+# smallest and the largest admissible count, the message).  Every kind wants whole 8-element groups of 16-byte aligned rows.
+_GROUPS = "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
+_ROW_CHECKS = (
+    ("_sde", 0, math.inf, "slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is " + _GROUPS),
+    ("_rsc", 8, math.inf, "slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is " + _GROUPS),
+    ("_thr", 0, L.THR_ROW_MAX, "slab pool: thresholding=True with a sample of %%d elements -- a thresholded row of the table is "
+                               "at most %d elements (one workgroup's LDS), " % L.THR_ROW_MAX + _GROUPS),
+)
+
+
+def _esize(dtype):
+    """bytes per element of a torch dtype"""
+    return torch.empty((), dtype=dtype).element_size()
 
 
 def _runs(rows):
@@ -145,6 +183,12 @@ class _Blend:
     __slots__ = ("keep", "rec", "mask", "mstep", "period", "first")
 
 
+class _Slot:
+    """one slot of the staging ring: the pinned buffer, the device buffers for its first two parts (`dev`) and for the third
+    (`devt`), the event behind its table copy, and views of the pinned parts (`pin_cur`: this tick's times as a tensor)"""
+    __slots__ = ("pin", "dev", "devt", "ev", "t_next", "t_cur", "st", "bufs", "bufs_raw", "pin_cur")
+
+
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
@@ -160,18 +204,13 @@ class SlabPool:
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
                         | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
                         | (L.TABLE_RESCALE if self._rsc else 0))
-        self._gon = np.zeros(slots, dtype=bool)          # per row: does its request bring its own guidance (submit's
-        self._gs = np.zeros(slots, dtype=np.float32)     # guidance_scale= / guidance_rescale=)?  its scale, its phi
-        self._gphi = np.zeros(slots, dtype=np.float32)
+        self._cols = []                  # the per-row arrays of _ROW (self._req, self._pos, ...), each with its idle value
+        for name, dtype, idle in _ROW:
+            setattr(self, "_" + name, np.full(slots, idle, dtype=dtype))
+            self._cols.append((getattr(self, "_" + name), idle))
         self._blends = {}                # handle -> the _Blend of an active inpainting request
         self._brec = np.zeros((slots, 0), dtype=_BLEND)  # [first row of the request, position]: its blend records
-        self._bslot = np.full(slots, -1, dtype=np.int64) # per row: the first row of its inpainting request (-1: none), the
-        self._bmask = np.zeros(slots, dtype=np.uint64)   # mask of its sample, its mask period
-        self._bper = np.zeros(slots, dtype=np.int64)
         self._ropts = {}                 # handle -> the dpm_launch_opts of an active SDE request (the solver's + its seed)
-        self._optp = np.zeros(slots, dtype=np.uint64)    # per row: its request's options (0: the solver's), the sample of
-        self._ns0 = np.zeros(slots, dtype=np.int32)      # its request it holds, its request's seed (SDE rows)
-        self._seed = np.zeros(slots, dtype=np.uint64)
         self._wait = []                  # FIFO of _Waiting: requests that found too few free rows
         self._rows = {}                  # handle -> (rows, memory format of x_T) of the admitted requests
         self._free = list(range(slots))  # sorted
@@ -179,10 +218,6 @@ class SlabPool:
         self._like = None                # (sample shape, dtype, device)
         self._plans = {}                 # id(plan) -> (offset into the record arrays, plan)
         self._recs = np.zeros(0, dtype=_STAGE)
-        self._off = np.zeros(slots, dtype=np.int64)      # per row: its plan's offset, its position, its plan's length,
-        self._pos = np.zeros(slots, dtype=np.int64)      # its request's handle (-1: idle)
-        self._len = np.zeros(slots, dtype=np.int64)
-        self._req = np.full(slots, -1, dtype=np.int64)
         self._opts = L.LaunchOpts()
         self._tick = 0
         self._t_next = None              # host copy of the time vector that rode with the last table, and where it is
@@ -252,24 +287,11 @@ class SlabPool:
         if sd in (torch.float16, torch.bfloat16) and s._state_dtype is None:
             raise NotImplementedError("slab pool: a half-precision slab needs a solver built with an explicit state_dtype -- "
                                       "the reference's type promotion would depend on the first network output")
-        if self._sde and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
+        if self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
             per = x.numel() // x.shape[0]
-            if per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
-                raise NotImplementedError("slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is "
-                                          "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
-                                          % per)
-        if self._rsc and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
-            per = x.numel() // x.shape[0]
-            if per < 8 or per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
-                raise NotImplementedError("slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is "
-                                          "whole 8-element groups of 16-byte aligned buffers; use request_pool() without slots"
-                                          % per)
-        if self._thr and self._like is None and torch.is_tensor(x) and x.dim() >= 1 and x.numel() > 0:
-            per = x.numel() // x.shape[0]
-            if per > L.THR_ROW_MAX or per % 8 != 0 or (per * torch.empty((), dtype=sd).element_size()) % 16 != 0:
-                raise NotImplementedError("slab pool: thresholding=True with a sample of %d elements -- a thresholded row of the "
-                                          "table is at most %d elements (one workgroup's LDS), whole 8-element groups of "
-                                          "16-byte aligned buffers; use request_pool() without slots" % (per, L.THR_ROW_MAX))
+            for switch, lo, hi, text in _ROW_CHECKS:
+                if getattr(self, switch) and not (lo <= per <= hi and per % 8 == 0 and (per * _esize(sd)) % 16 == 0):
+                    raise NotImplementedError(text % per)
         DV._require_gpu(x)
         if not torch.is_tensor(x) or x.dim() < 1 or x.numel() == 0:
             raise ValueError("slab pool: x must be a tensor [b, *sample_shape] with at least one element")
@@ -378,7 +400,7 @@ class SlabPool:
 
     def _blend_of(self, mb, x, plan, sd):
         """the request's `_Blend`: everything a tick must not compute per request, once, in the state dtype and contiguous"""
-        shape, dev, es = tuple(x.shape), x.device, torch.empty((), dtype=sd).element_size()
+        shape, dev, es = tuple(x.shape), x.device, _esize(sd)
         b, per = int(shape[0]), self._per
         q = _Blend()
         m, period = mb._mask_for(shape, sd, dev)
@@ -453,7 +475,7 @@ class SlabPool:
         self._cfg = w is not None and w.effective_guidance == "classifier-free"
         self._nS = nS = 2 * S if self._cfg else S
         self._per = per = int(np.prod(shape, dtype=np.int64)) if shape else 1
-        self._rowb = per * torch.empty((), dtype=sd).element_size()
+        self._rowb = per * _esize(sd)
         self._x = [torch.zeros((nS,) + shape, dtype=sd, device=dev) for _ in range(2)]
         self._hist = [torch.zeros((S,) + shape, dtype=sd, device=dev) for _ in range(3)]
         self._hbase = np.array([t.data_ptr() for t in self._hist], dtype=np.uint64)
@@ -468,15 +490,16 @@ class SlabPool:
         o_cur = (self._copyb + 15) // 16 * 16
         o_st = (o_cur + 4 * nS + 15) // 16 * 16
         o_bs = o_st + S * _STAGE.itemsize
-        self._pin, self._dev, self._devt, self._ev, self._views = [], [], [], [None] * _RING, []
+        self._ring = []
         for _ in range(_RING):
-            pin = DV._pinned_bytes(o_bs + S * _BUFS.itemsize)
-            a = pin.numpy()
-            self._pin.append(pin)
-            self._dev.append(DV._device_bytes(self._copyb, dev))
-            self._devt.append(DV._device_bytes(4 * nS, dev))
-            self._views.append((a[self._tabb:self._copyb].view(np.float32), a[o_cur:o_cur + 4 * nS].view(np.float32),
-                                a[o_st:o_bs].view(_STAGE), a[o_bs:].view(_BUFS), pin[o_cur:o_cur + 4 * nS], a[o_bs:]))
+            g = _Slot()
+            g.pin, g.ev = DV._pinned_bytes(o_bs + S * _BUFS.itemsize), None
+            g.dev, g.devt = DV._device_bytes(self._copyb, dev), DV._device_bytes(4 * nS, dev)
+            a = g.pin.numpy()
+            g.t_next, g.t_cur = a[self._tabb:self._copyb].view(np.float32), a[o_cur:o_cur + 4 * nS].view(np.float32)
+            g.st, g.bufs, g.bufs_raw = a[o_st:o_bs].view(_STAGE), a[o_bs:].view(_BUFS), a[o_bs:]
+            g.pin_cur = g.pin[o_cur:o_cur + 4 * nS]
+            self._ring.append(g)
         self._t_attr = "t_input" if w is not None else "t_eval"
 
     def _plan_offset(self, plan):
@@ -492,69 +515,49 @@ class SlabPool:
     def _admit(self):
         """waiting requests, first in first out, into free rows: their x_T (both halves under guidance) and conditions.
         Returns the inpainting requests among them as (rows, _Blend): their x_T is blended after the tick's network call."""
-        S, cur = self.S, self._x[self._cur]
-        blends = []
+        taken = []
         while self._wait and int(self._wait[0].x.shape[0]) <= len(self._free):
-            q = self._wait.pop(0)
-            b = int(q.x.shape[0])
-            rows, self._free = self._free[:b], self._free[b:]
-            x = q.x.to(self._sd)
-            k = 0
-            for r0, cnt in _runs(rows):
-                cur[r0:r0 + cnt].copy_(x[k:k + cnt])
-                if self._cfg:
-                    cur[S + r0:S + r0 + cnt].copy_(x[k:k + cnt])
-                if q.cond is not None:
-                    c = q.cond.to(self._cslab.device)
-                    self._cslab[(S if self._cfg else 0) + r0:(S if self._cfg else 0) + r0 + cnt].copy_(
-                        c if c.shape[0] == 1 else c[k:k + cnt])
-                if q.uncond is not None:
-                    u = q.uncond.to(self._cslab.device)
-                    self._cslab[r0:r0 + cnt].copy_(u if u.shape[0] == 1 else u[k:k + cnt])
-                k += cnt
+            b = int(self._wait[0].x.shape[0])
+            taken.append((self._wait.pop(0), self._free[:b]))
+            self._free = self._free[b:]
+        if taken:                        # whatever the rows' last requests left: gone, field by field of _ROW
+            ra = np.array([r for _, rows in taken for r in rows], dtype=np.int64)
+            for col, idle in self._cols:
+                col[ra] = idle
+        blends = []
+        for q, rows in taken:
+            self._load_rows(q, rows)
             ra = np.asarray(rows, dtype=np.int64)
             self._off[ra], self._pos[ra], self._len[ra], self._req[ra] = self._plan_offset(q.plan), 0, len(q.plan.stages), q.h
-            self._optp[ra], self._ns0[ra], self._seed[ra] = 0, 0, 0
-            if q.seed is not None:       # sample k of the request sits in rows[k]: its z starts at element k * per_sample
-                o = self._ropts[q.h] = _sde.request_opts(q.seed, self._s._opts_ptr())
-                self._optp[ra], self._ns0[ra], self._seed[ra] = C.addressof(o), np.arange(b, dtype=np.int32), np.uint64(q.seed)
-            self._gon[ra] = q.guide is not None
+            self._samp[ra] = np.arange(len(rows), dtype=np.int32)
+            if q.seed is not None:
+                self._sde_admit(q, ra)
             if q.guide is not None:
-                self._gs[ra], self._gphi[ra] = q.guide
-            self._bslot[ra] = -1
-            if q.blend is not None:      # sample k of the request sits in rows[k]: its tensors start at element k * per_sample
-                bl = self._blends[q.h] = q.blend
-                if self._brec.shape[1] < len(bl.rec):
-                    grown = np.zeros((S, len(bl.rec)), dtype=_BLEND)
-                    grown[:, :self._brec.shape[1]] = self._brec
-                    self._brec = grown
-                self._brec[rows[0], :len(bl.rec)] = bl.rec
-                self._bslot[ra], self._bper[ra] = rows[0], bl.period
-                self._bmask[ra] = np.uint64(bl.mask.data_ptr()) + np.arange(b, dtype=np.uint64) * np.uint64(bl.mstep)
-                self._ns0[ra] = np.arange(b, dtype=np.int32)
-                blends.append((rows, bl))
+                self._guide_admit(q, ra)
+            if q.blend is not None:
+                self._blend_admit(q, rows, ra)
+                blends.append((rows, q.blend))
             self._rows[q.h] = (rows, q.mf)
         return blends
 
-    def _blend_first(self, blends, xin, stream):
-        """x_T of the inpainting requests admitted on this tick, blended in the current state slab as run_plan blends it at
-        i == 0 -- after the network has seen it.  One dpm_blend_launch per run of consecutive rows, through a temporary (the
-        kernel's x and out are __restrict__: not in place); both halves under guidance."""
-        S, per, rowb, code = self.S, self._per, self._rowb, DV._DT[self._sd]
-        for rows, bl in blends:
-            a, bb, alpha, sigma = bl.first
-            k = 0
-            for r0, cnt in _runs(rows):
-                tmp = torch.empty_like(xin[r0:r0 + cnt])
-                full = bl.mstep != 0
-                L.check(DV._blend_launch_raw(xin[r0:r0 + cnt].data_ptr(), bl.mask.data_ptr() + k * bl.mstep,
-                                             a.data_ptr() + k * rowb, None if bb is None else bb.data_ptr() + k * rowb,
-                                             alpha, sigma, tmp.data_ptr(), cnt * per, cnt * per if full else bl.period, code,
-                                             stream))
-                xin[r0:r0 + cnt].copy_(tmp)
-                if self._cfg:
-                    xin[S + r0:S + r0 + cnt].copy_(tmp)
-                k += cnt
+    def _load_rows(self, q, rows):
+        """the request's x_T into its rows of the current state slab (both halves under guidance), its conditions into the
+        condition slab's: one copy per run of consecutive rows"""
+        S, cur = self.S, self._x[self._cur]
+        half = S if self._cfg else 0     # the condition slab's conditional half (the unconditional one comes first)
+        x = q.x.to(self._sd)
+        k = 0
+        for r0, cnt in _runs(rows):
+            cur[r0:r0 + cnt].copy_(x[k:k + cnt])
+            if self._cfg:
+                cur[S + r0:S + r0 + cnt].copy_(x[k:k + cnt])
+            if q.cond is not None:
+                c = q.cond.to(self._cslab.device)
+                self._cslab[half + r0:half + r0 + cnt].copy_(c if c.shape[0] == 1 else c[k:k + cnt])
+            if q.uncond is not None:
+                u = q.uncond.to(self._cslab.device)
+                self._cslab[r0:r0 + cnt].copy_(u if u.shape[0] == 1 else u[k:k + cnt])
+            k += cnt
 
     def _network(self, x, t):
         """ONE call on the whole slab: the raw output(s) as (e0, e1), e1 the unconditional half under guidance"""
@@ -582,7 +585,98 @@ class SlabPool:
         return t
 
     # ------------------------------------------------------------------------------------------------------------------
-    # one tick
+    # SDE requests.  Row fields: optp, seed (and samp, which every row has).  Kept per request: _ropts.
+    # ------------------------------------------------------------------------------------------------------------------
+    def _sde_admit(self, q, ra):
+        """the request's own options (the solver's + its seed), kept while it is active; its rows point at them"""
+        o = self._ropts[q.h] = _sde.request_opts(q.seed, self._s._opts_ptr())
+        self._optp[ra], self._seed[ra] = C.addressof(o), np.uint64(q.seed)
+
+    def _sde_tick(self, b, rows, rec):
+        """the rows' own options; sample k's z starts at element k * per_sample; row 0's options are the call's: they carry
+        its seed"""
+        own = self._optp[rows]
+        b["opts"] = np.where(own != 0, own, b["opts"])
+        b["noise_sample0"] = np.where((rec["flags"] & L.F_NOISE) != 0, self._samp[rows], 0)
+        seed0 = int(self._seed[rows[0]]) if own[0] else 0
+        self._opts.noise_seed_lo, self._opts.noise_seed_hi = seed0 & 0xffffffff, seed0 >> 32
+
+    def _sde_retire(self, h):
+        self._ropts.pop(h, None)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # per-request guidance (any classifier-free pool).  Row fields: gon, gs, gphi.  Checked at submit: _guidance.
+    # ------------------------------------------------------------------------------------------------------------------
+    def _guide_admit(self, q, ra):
+        self._gon[ra] = True
+        self._gs[ra], self._gphi[ra] = q.guide
+
+    def _guide_tick(self, st, rows, rec):
+        """rows whose request brought its own guidance: what the planner and _bind_rescale write for a wrapper of that scale
+        and phi (phi 0: no flag, a plain row), over the gathered records"""
+        on = self._gon[rows] & (rec["guidance"] == L.GUIDE["classifier-free"])
+        cs, cg, fl = DV._cfg_fields(self._gs[rows], self._gphi[rows], rec["sigma_e"], rec["flags"])
+        st["cfg_scale"] = np.where(on, cs, rec["cfg_scale"])
+        st["cg_scale"] = np.where(on, cg, rec["cg_scale"])
+        st["flags"] = np.where(on, fl, rec["flags"])
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # inpainting requests.  Row fields: bslot, bmask, bper (and samp).  Kept per request: _blends (built at submit: _blend_of)
+    # and its records in _brec.
+    # ------------------------------------------------------------------------------------------------------------------
+    def _blend_admit(self, q, rows, ra):
+        """the request's blend records at its first row; sample k of the request sits in rows[k]: its mask starts at element
+        k * mstep"""
+        bl = self._blends[q.h] = q.blend
+        if self._brec.shape[1] < len(bl.rec):
+            grown = np.zeros((self.S, len(bl.rec)), dtype=_BLEND)
+            grown[:, :self._brec.shape[1]] = self._brec
+            self._brec = grown
+        self._brec[rows[0], :len(bl.rec)] = bl.rec
+        self._bslot[ra], self._bper[ra] = rows[0], bl.period
+        self._bmask[ra] = np.uint64(bl.mask.data_ptr()) + np.arange(len(rows), dtype=np.uint64) * np.uint64(bl.mstep)
+
+    def _blend_first(self, blends, xin, stream):
+        """x_T of the inpainting requests admitted on this tick, blended in the current state slab as run_plan blends it at
+        i == 0 -- after the network has seen it.  One dpm_blend_launch per run of consecutive rows, through a temporary (the
+        kernel's x and out are __restrict__: not in place); both halves under guidance."""
+        S, per, rowb, code = self.S, self._per, self._rowb, DV._DT[self._sd]
+        for rows, bl in blends:
+            a, bb, alpha, sigma = bl.first
+            k = 0
+            for r0, cnt in _runs(rows):
+                tmp = torch.empty_like(xin[r0:r0 + cnt])
+                full = bl.mstep != 0
+                L.check(DV._blend_launch_raw(xin[r0:r0 + cnt].data_ptr(), bl.mask.data_ptr() + k * bl.mstep,
+                                             a.data_ptr() + k * rowb, None if bb is None else bb.data_ptr() + k * rowb,
+                                             alpha, sigma, tmp.data_ptr(), cnt * per, cnt * per if full else bl.period, code,
+                                             stream))
+                xin[r0:r0 + cnt].copy_(tmp)
+                if self._cfg:
+                    xin[S + r0:S + r0 + cnt].copy_(tmp)
+                k += cnt
+
+    def _blend_tick(self, st, b, rows):
+        """blend rows: DPM_F_BLEND, the scalars and the pointers of (request, position), sample k at base + k * stride"""
+        slot = self._bslot[rows]
+        width = self._brec.shape[1]
+        br = (self._brec[np.clip(slot, 0, None), np.minimum(self._pos[rows], width - 1)] if width
+              else np.zeros(len(rows), dtype=_BLEND))
+        on = (slot >= 0) & (br["flag"] != 0)
+        kb = self._samp[rows].astype(np.uint64) * np.uint64(self._rowb)
+        st["flags"] |= np.where(on, br["flag"], 0).astype(np.uint32)
+        st["blend_alpha"] = np.where(on, br["alpha"], np.float32(0))
+        st["blend_sigma"] = np.where(on, br["sigma"], np.float32(0))
+        b["mask"] = np.where(on, self._bmask[rows], np.uint64(0))
+        b["blend_a"] = np.where(on, br["a"] + kb, np.uint64(0))
+        b["blend_b"] = np.where(on & (br["b"] != 0), br["b"] + kb, np.uint64(0))
+        b["mask_period"] = np.where(on, self._bper[rows], 0)
+
+    def _blend_retire(self, h):
+        self._blends.pop(h, None)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # one tick: step() and its phases, in the order they run
     # ------------------------------------------------------------------------------------------------------------------
     def step(self):
         """One stage of every active row: one network call, one table launch.  Returns {handle: result} of the requests that
@@ -590,7 +684,6 @@ class SlabPool:
         done = {}
         if self._like is None or not (self._rows or self._wait):
             return done
-        s, S = self._s, self.S
         stream, idx_dev, capturing, other = DV._launch_ctx(self._like[2])
         if capturing:
             raise RuntimeError("slab pool: ticks are not captured into graphs")
@@ -600,127 +693,53 @@ class SlabPool:
             R = len(rows)
             if R == 0:
                 return done
-            j = self._tick % _RING
+            g = self._ring[self._tick % _RING]
             self._tick += 1
-            DV._event_wait(self._ev[j])
-            t_next_v, t_cur_v, st_v, b_v, pin_cur, b_raw = self._views[j]
+            DV._event_wait(g.ev)
             idx = self._off[rows] + self._pos[rows]
             rec = self._recs[idx]
-            # the model-time vector: the one that rode with the previous tick's table, unless rows were admitted since
-            t_now = self._times_of(rows, idx)
-            if self._t_dev is not None and np.array_equal(t_now, self._t_next):
-                t_dev = self._t_dev
-            else:
-                t_cur_v[:] = t_now
-                DV._copy_to_device(self._devt[j], pin_cur)
-                self.copies += 1
-                t_dev = self._devt[j].view(torch.float32)
+            last = self._pos[rows] + 1 == self._len[rows]
             xin, xout = self._x[self._cur], self._x[1 - self._cur]
-            e0, e1 = self._network(xin if self._cfg else xin[:S], t_dev)
-            e0, e1, ed = self._bind(e0, e1)
+            e0, e1, ed = self._bind(*self._network(xin if self._cfg else xin[:self.S], self._tick_times(g, rows, idx)))
             if admitted:
-                if other:
-                    with torch.cuda.device(idx_dev):
-                        self._blend_first(admitted, xin, stream)
-                else:
+                with DV._on_device(idx_dev, other):
                     self._blend_first(admitted, xin, stream)
             # the tick's records, vectorised: stage r = the record of row rows[r] at its position, pointers = base + row * stride
-            st_v[:R] = rec
+            st, b = g.st[:R], g.bufs[:R]
+            st[:] = rec
             if self._cfg:
-                # rows whose request brought its own guidance: what the planner and _bind_rescale write for a wrapper of that
-                # scale and phi (phi 0: no flag, a plain row)
-                on = self._gon[rows] & (rec["guidance"] == L.GUIDE["classifier-free"])
-                cs, cg, fl = DV._cfg_fields(self._gs[rows], self._gphi[rows], rec["sigma_e"], rec["flags"])
-                st_v["cfg_scale"][:R] = np.where(on, cs, rec["cfg_scale"])
-                st_v["cg_scale"][:R] = np.where(on, cg, rec["cg_scale"])
-                st_v["flags"][:R] = np.where(on, fl, rec["flags"])
-            b = b_v[:R]
-            b_raw[:R * _BUFS.itemsize] = 0
-            rb = rows.astype(np.uint64) * np.uint64(self._rowb)
-            eb = rows.astype(np.uint64) * np.uint64(self._per * e0.element_size())
-            last = self._pos[rows] + 1 == self._len[rows]
-            b["x"] = np.uint64(xin.data_ptr()) + rb
-            b["x_out"] = np.uint64(xout.data_ptr()) + rb
-            if self._cfg:
-                b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + S * self._rowb) + rb)
-                b["e1"] = np.uint64(e1.data_ptr()) + eb
-            b["e0"] = np.uint64(e0.data_ptr()) + eb
-            for name, slot, used in (("h1", rec["h1_slot"], rec["h1_slot"] >= 0), ("h2", rec["h2_slot"], rec["h2_slot"] >= 0),
-                                     ("m_out", rec["m_slot"], (rec["flags"] & L.F_STORE_M) != 0)):
-                b[name] = np.where(used, self._hbase[np.clip(slot, 0, 2)] + rb, np.uint64(0))
-            b["n"], b["batch"] = self._per, 1
-            b["state_dtype"], b["eps_dtype"] = DV._DT[self._sd], DV._DT[ed]
-            o = s._opts_ptr()
-            if o is not None:
-                C.memmove(C.byref(self._opts), o, C.sizeof(L.LaunchOpts))
-                b["opts"] = C.addressof(o.contents)
-            self._opts.per_request_stages, self._opts.fuse_shapes = 1, 0
-            self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
+                self._guide_tick(st, rows, rec)
+            self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed)
+            self._call_opts(b)
             if self._sde:
-                own = self._optp[rows]
-                b["opts"] = np.where(own != 0, own, b["opts"])
-                b["noise_sample0"] = np.where((rec["flags"] & L.F_NOISE) != 0, self._ns0[rows], 0)
-                seed0 = int(self._seed[rows[0]]) if own[0] else 0      # row 0's options are the call's: they carry its seed
-                self._opts.noise_seed_lo, self._opts.noise_seed_hi = seed0 & 0xffffffff, seed0 >> 32
+                self._sde_tick(b, rows, rec)
             if self._inp:
-                # blend rows: DPM_F_BLEND, the scalars and the pointers of (request, position), sample k at base + k * stride
-                slot = self._bslot[rows]
-                width = self._brec.shape[1]
-                br = (self._brec[np.clip(slot, 0, None), np.minimum(self._pos[rows], width - 1)] if width
-                      else np.zeros(R, dtype=_BLEND))
-                on = (slot >= 0) & (br["flag"] != 0)
-                kb = self._ns0[rows].astype(np.uint64) * np.uint64(self._rowb)
-                st_v["flags"][:R] |= np.where(on, br["flag"], 0).astype(np.uint32)
-                st_v["blend_alpha"][:R] = np.where(on, br["alpha"], np.float32(0))
-                st_v["blend_sigma"][:R] = np.where(on, br["sigma"], np.float32(0))
-                b["mask"] = np.where(on, self._bmask[rows], np.uint64(0))
-                b["blend_a"] = np.where(on, br["a"] + kb, np.uint64(0))
-                b["blend_b"] = np.where(on & (br["b"] != 0), br["b"] + kb, np.uint64(0))
-                b["mask_period"] = np.where(on, self._bper[rows], 0)
+                self._blend_tick(st, b, rows)
             b["opts"][0] = C.addressof(self._opts)
-            flag = self._tflags
             # next tick's time vector rides with this tick's table
-            go = ~last
-            t_next = self._times_of(rows[go], idx[go] + 1)
-            t_next_v[:] = t_next
-            sts = C.cast(st_v.ctypes.data, C.POINTER(L.Stage))
-            bufs = C.cast(b_v.ctypes.data, C.POINTER(L.Buffers))
-            pin, dev = self._pin[j], self._dev[j]
-
-            def tick():
-                self._opts.table_mode = L.TABLE_FILL | flag
-                b["workspace"][0] = pin.data_ptr()
-                rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
-                if rc == 0:
-                    self._ev[j] = DV._copy_to_device(dev, pin[:self._copyb])
-                    self.copies += 1
-                    self._opts.table_mode = L.TABLE_LAUNCH | flag
-                    b["workspace"][0] = dev.data_ptr()
-                    rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
-                self._opts.table_mode = 0
-                return rc
-            if other:
-                with torch.cuda.device(idx_dev):
-                    rc = tick()
-            else:
-                rc = tick()
+            t_next = self._times_of(rows[~last], idx[~last] + 1)
+            g.t_next[:] = t_next
+            with DV._on_device(idx_dev, other):
+                rc = self._fill_copy_launch(g, b, R, stream)
             if rc:
                 L.check(rc)
             del e0, e1
-            self._t_next, self._t_dev = t_next, dev[self._tabb:self._copyb].view(torch.float32)
+            self._t_next, self._t_dev = t_next, g.dev[self._tabb:self._copyb].view(torch.float32)
             self._cur = 1 - self._cur
             self._pos[rows] += 1
-            # finished requests: their rows, cloned from the output slab, are free again
-            for h in np.unique(self._req[rows[last]]).tolist():
-                rws, mf = self._rows.pop(h)
-                self._ropts.pop(h, None)
-                self._blends.pop(h, None)
-                parts = [xout[r0:r0 + cnt] for r0, cnt in _runs(rws)]
-                out = parts[0].clone() if len(parts) == 1 else torch.cat(parts)
-                done[h] = out if mf is None else DV._conv(out, out.dtype, mf)
-                self._req[np.asarray(rws, dtype=np.int64)] = -1
-                self._free = sorted(self._free + rws)
+            self._retire(rows[last], xout, done)
         return done
+
+    def _tick_times(self, g, rows, idx):
+        """the device's model-time vector of this tick: the one that rode with the previous tick's table, unless rows were
+        admitted since -- then a copy of its own from ring slot `g`"""
+        t_now = self._times_of(rows, idx)
+        if self._t_dev is not None and np.array_equal(t_now, self._t_next):
+            return self._t_dev
+        g.t_cur[:] = t_now
+        DV._copy_to_device(g.devt, g.pin_cur)
+        self.copies += 1
+        return g.devt.view(torch.float32)
 
     def _bind(self, e0, e1):
         """the network's output as dense slabs of a dtype the kernels pair with the state's (launch_list._bind_outputs)"""
@@ -737,3 +756,60 @@ class SlabPool:
         e0 = DV._conv(e0, ed)
         e1 = DV._conv(e1, ed)
         return e0, e1, ed
+
+    def _buffer_records(self, g, b, rows, rec, last, xin, xout, e0, e1, ed):
+        """the rows' dpm_buffers, zeroed and filled: every pointer is base + row * stride, a history slot the record names"""
+        g.bufs_raw[:len(rows) * _BUFS.itemsize] = 0
+        rb = rows.astype(np.uint64) * np.uint64(self._rowb)
+        eb = rows.astype(np.uint64) * np.uint64(self._per * e0.element_size())
+        b["x"] = np.uint64(xin.data_ptr()) + rb
+        b["x_out"] = np.uint64(xout.data_ptr()) + rb
+        if self._cfg:
+            b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + self.S * self._rowb) + rb)
+            b["e1"] = np.uint64(e1.data_ptr()) + eb
+        b["e0"] = np.uint64(e0.data_ptr()) + eb
+        for name, slot, used in (("h1", rec["h1_slot"], rec["h1_slot"] >= 0), ("h2", rec["h2_slot"], rec["h2_slot"] >= 0),
+                                 ("m_out", rec["m_slot"], (rec["flags"] & L.F_STORE_M) != 0)):
+            b[name] = np.where(used, self._hbase[np.clip(slot, 0, 2)] + rb, np.uint64(0))
+        b["n"], b["batch"] = self._per, 1
+        b["state_dtype"], b["eps_dtype"] = DV._DT[self._sd], DV._DT[ed]
+
+    def _call_opts(self, b):
+        """the call's options: a copy of the solver's with per-request stages and no seed (an SDE row 0 brings its own:
+        _sde_tick); every row points at the solver's, row 0 -- once the kinds have written theirs -- at the copy"""
+        o = self._s._opts_ptr()
+        if o is not None:
+            C.memmove(C.byref(self._opts), o, C.sizeof(L.LaunchOpts))
+            b["opts"] = C.addressof(o.contents)
+        self._opts.per_request_stages, self._opts.fuse_shapes = 1, 0
+        self._opts.noise_seed_lo = self._opts.noise_seed_hi = 0
+
+    def _fill_copy_launch(self, g, b, R, stream):
+        """DPM_TABLE_FILL into ring slot `g`'s pinned buffer, its ONE copy (the table and the next tick's times), DPM_TABLE_LAUNCH
+        on the device's; returns the library's error code, table_mode 0 again either way"""
+        flag, pin, dev = self._tflags, g.pin, g.dev
+        sts = C.cast(g.st.ctypes.data, C.POINTER(L.Stage))
+        bufs = C.cast(g.bufs.ctypes.data, C.POINTER(L.Buffers))
+        self._opts.table_mode = L.TABLE_FILL | flag
+        b["workspace"][0] = pin.data_ptr()
+        rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
+        if rc == 0:
+            g.ev = DV._copy_to_device(dev, pin[:self._copyb])
+            self.copies += 1
+            self._opts.table_mode = L.TABLE_LAUNCH | flag
+            b["workspace"][0] = dev.data_ptr()
+            rc = DV._stage_launch_multi_raw(sts, bufs, R, stream)
+        self._opts.table_mode = 0
+        return rc
+
+    def _retire(self, rows, xout, done):
+        """the requests of the finished `rows` into `done`: their rows, cloned from the output slab, are free again"""
+        for h in np.unique(self._req[rows]).tolist():
+            rws, mf = self._rows.pop(h)
+            self._sde_retire(h)
+            self._blend_retire(h)
+            parts = [xout[r0:r0 + cnt] for r0, cnt in _runs(rws)]
+            out = parts[0].clone() if len(parts) == 1 else torch.cat(parts)
+            done[h] = out if mf is None else DV._conv(out, out.dtype, mf)
+            self._req[np.asarray(rws, dtype=np.int64)] = -1
+            self._free = sorted(self._free + rws)

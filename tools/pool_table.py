@@ -148,24 +148,25 @@ def run(mode, ticks, lone, warmup, n_ticks, stream, parent=None):
     return dict(ticks=n_ticks, region_s=sec, us_per_tick=sec * 1e6 / n_ticks)
 
 
-def wall(dev, dtype, R, ticks):
-    """host wall time per tick, steady state: a SlabPool of R rows against a RequestPool of the same R requests"""
+def wall(dev, dtype, R, ticks, pools):
+    """host wall time per tick, steady state, of each of `pools`: name -> make.  make(td, g) returns the pool and the function
+    kwargs(n) of what `submit` gets for request n beside its x_T, steps and order (it may draw what they need from the generator
+    g).  R / 20 requests are submitted per tick: as many finish as arrive."""
     td = DTYPES[dtype][0]
     out = {}
-    for name in ("slab", "request_pool"):
-        dpm = solver(td, net=lambda x, t: x * 0.5)
-        pool = dpm.request_pool(slots=R) if name == "slab" else dpm.request_pool()
+    for name, make in pools.items():
         g = torch.Generator(device=dev).manual_seed(1)
         xs = [torch.randn((1,) + SHAPE, generator=g, device=dev).to(td) for _ in range(R)]
+        pool, kwargs = make(td, g)
         nxt = 0
         per = max(1, R // STEPS)
 
         def feed():
             nonlocal nxt
             for _ in range(per):
-                pool.submit(xs[nxt % R], steps=STEPS, order=2)
+                pool.submit(xs[nxt % R], steps=STEPS, order=2, **kwargs(nxt))
                 nxt += 1
-        for _ in range(STEPS + 2):          # fill: R / 20 requests per tick, then steady state (as many finish as arrive)
+        for _ in range(STEPS + 2):          # fill: R / 20 requests per tick, then steady state
             feed()
             pool.step()
         torch.cuda.synchronize()
@@ -180,6 +181,15 @@ def wall(dev, dtype, R, ticks):
                          wall_us_per_tick=(t2 - t0) * 1e6 / ticks)
         del pool
     return out
+
+
+def wall_solver(td):
+    """the solver of the --wall pools: a cheap elementwise network"""
+    return solver(td, net=lambda x, t: x * 0.5)
+
+
+def no_kwargs(n):
+    return {}
 
 
 def main():
@@ -204,7 +214,9 @@ def main():
     res = {"workload": "%d x [1,4,64,64] %s, 2M, 20 steps, staggered, frozen eps, %d slab sets" % (a.requests, a.dtype, a.sets),
            "label": a.label, "device": torch.cuda.get_device_name(0), "version": int(L.lib.dpm_version()), "ticks": a.ticks}
     if a.wall:
-        res["wall"] = wall(dev, a.dtype, a.requests, min(a.ticks, 400))
+        res["wall"] = wall(dev, a.dtype, a.requests, min(a.ticks, 400), {
+            "slab": lambda td, g: (wall_solver(td).request_pool(slots=a.requests), no_kwargs),
+            "request_pool": lambda td, g: (wall_solver(td).request_pool(), no_kwargs)})
     else:
         slabs = Slabs(dev, a.dtype, a.requests, a.sets)
         parent, modes = None, a.modes

@@ -21,7 +21,6 @@ import argparse
 import ctypes as C
 import json
 import sys
-import time
 
 import numpy as np
 import torch
@@ -111,41 +110,15 @@ def run(mode, ticks, ode_ticks, warmup, n_ticks, stream):
 
 def wall(dev, dtype, R, ticks, mask):
     """host wall time per tick, steady state: a SlabPool(inpaint=True) of R inpainting rows against a plain SlabPool of R rows"""
-    td = T.DTYPES[dtype][0]
-    out = {}
-    for name in ("slab_inpaint", "slab_plain"):
-        dpm = T.solver(td, net=lambda x, t: x * 0.5)
-        pool = dpm.request_pool(slots=R, inpaint=True) if name == "slab_inpaint" else dpm.request_pool(slots=R)
-        g = torch.Generator(device=dev).manual_seed(1)
+    def inpaint(td, g):
+        dpm = T.wall_solver(td)
         mk = lambda: torch.randn((1,) + SHAPE, generator=g, device=dev).to(td)
-        xs = [mk() for _ in range(R)]
         mshape = SHAPE if mask == "full" else SHAPE[1:]
         mbs = [D.MaskBlend(dpm.noise_schedule, (torch.rand(mshape, generator=g, device=dev) > 0.5).to(td), x0=mk(), noise=mk())
-               for _ in range(R)] if name == "slab_inpaint" else [None] * R
-        nxt = 0
-        per = max(1, R // STEPS)
-
-        def feed():
-            nonlocal nxt
-            for _ in range(per):
-                kw = dict(blend=mbs[nxt % R]) if name == "slab_inpaint" else {}
-                pool.submit(xs[nxt % R], steps=STEPS, order=2, **kw)
-                nxt += 1
-        for _ in range(STEPS + 2):          # fill: R / 20 requests per tick, then steady state (as many finish as arrive)
-            feed()
-            pool.step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(ticks):
-            feed()
-            pool.step()
-        t1 = time.perf_counter()
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        out[name] = dict(ticks=ticks, active=len(pool), host_us_per_tick=(t1 - t0) * 1e6 / ticks,
-                         wall_us_per_tick=(t2 - t0) * 1e6 / ticks)
-        del pool
-    return out
+               for _ in range(R)]
+        return dpm.request_pool(slots=R, inpaint=True), lambda n: dict(blend=mbs[n % R])
+    return T.wall(dev, dtype, R, ticks, {
+        "slab_inpaint": inpaint, "slab_plain": lambda td, g: (T.wall_solver(td).request_pool(slots=R), T.no_kwargs)})
 
 
 def main():

@@ -19,9 +19,11 @@ rows live in slabs as a slab pool lays them out (the duplicate store of a stage 
        one stage_kernel_table launch
 
 HIP events around `--ticks` back-to-back ticks after `--warmup` (mode a: a tenth of either, it is two orders slower),
-`--repeat` rounds over the modes, alternating.
+`--repeat` rounds over the modes, alternating.  `--wall` times whole pool ticks on the host instead: a SlabPool(rescale=True) of R
+rows whose requests each bring a guidance scale and a phi of their own against a plain classifier-free SlabPool of R rows.
 
     python tools/pool_table_rescale.py --dtype fp16 --out DIR/events.jsonl
+    python tools/pool_table_rescale.py --wall
 """
 import argparse
 import ctypes as C
@@ -40,10 +42,10 @@ RESCALE = L.TABLE_RESCALE
 SCALE, PHI = 7.5, 0.7
 
 
-def solver(td, phi=PHI):
+def solver(td, phi=PHI, net=lambda x, t, c: x):
     betas = np.linspace(0.00085 ** 0.5, 0.012 ** 0.5, 1000, dtype=np.float64) ** 2
     ns = D.NoiseScheduleVP("discrete", alphas_cumprod=torch.from_numpy(np.cumprod(1.0 - betas).astype(np.float32)))
-    fn = D.model_wrapper(lambda x, t, c: x, ns, guidance_type="classifier-free", guidance_scale=SCALE, condition=torch.ones(1),
+    fn = D.model_wrapper(net, ns, guidance_type="classifier-free", guidance_scale=SCALE, condition=torch.ones(1),
                          unconditional_condition=torch.zeros(1))
     return D.DPM_Solver(D.cfg_rescale(fn, phi), ns, algorithm_type="dpmsolver++", state_dtype=td)
 
@@ -151,6 +153,19 @@ def run(mode, ticks, lone, warmup, n_ticks, stream, plain=None):
     return dict(ticks=n_ticks, region_s=sec, us_per_tick=sec * 1e6 / n_ticks)
 
 
+def wall(dev, dtype, R, ticks):
+    """host wall time per tick, steady state: a SlabPool(rescale=True) of R rows on a classifier-free solver, every request
+    with a guidance scale (three in rotation) and a phi (0 and 0.7 in rotation) of its own, against the plain classifier-free
+    SlabPool of R rows under the wrapper's guidance"""
+    def pool(td, **kw):
+        return solver(td, 0.0, net=lambda x, t, c: x * 0.5).request_pool(slots=R, **kw)
+
+    def own(n):
+        return dict(guidance_scale=(1.5, 3.0, SCALE)[n % 3], guidance_rescale=(0.0, PHI)[n // 3 % 2])
+    return T.wall(dev, dtype, R, ticks, {"slab_rescale": lambda td, g: (pool(td, rescale=True), own),
+                                         "slab_plain": lambda td, g: (pool(td), T.no_kwargs)})
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--dtype", choices=sorted(T.DTYPES), default="fp16")
@@ -160,6 +175,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=600)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--wall", action="store_true")
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -170,18 +186,21 @@ def main():
     res = {"workload": "%d x [1,4,64,64] %s, 2M + CFG %.1f + guidance rescale %.1f, 20 steps, staggered, frozen outputs, %d slab sets"
                        % (a.requests, a.dtype, SCALE, PHI, a.sets),
            "label": a.label, "device": torch.cuda.get_device_name(0), "version": int(L.lib.dpm_version()), "ticks": a.ticks}
-    slabs = RescaleSlabs(dev, a.dtype, a.requests, a.sets)
-    ticks, lone, plain = slabs.ticks(), slabs.lone(), slabs.ticks(plain=True)
-    prefill(ticks, stream)
-    prefill(plain, stream, flag=0)
-    rows = []
-    for _ in range(a.repeat):
-        for m in a.modes:
-            rows.append(dict(mode=m, requests=a.requests, **run(m, ticks, lone, a.warmup, a.ticks, stream, plain)))
-    res["rows"] = rows
-    for m in sorted({r["mode"] for r in rows}):
-        v = [r["us_per_tick"] for r in rows if r["mode"] == m]
-        res["%s@%d" % (m, a.requests)] = dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
+    if a.wall:
+        res["wall"] = wall(dev, a.dtype, a.requests, min(a.ticks, 400))
+    else:
+        slabs = RescaleSlabs(dev, a.dtype, a.requests, a.sets)
+        ticks, lone, plain = slabs.ticks(), slabs.lone(), slabs.ticks(plain=True)
+        prefill(ticks, stream)
+        prefill(plain, stream, flag=0)
+        rows = []
+        for _ in range(a.repeat):
+            for m in a.modes:
+                rows.append(dict(mode=m, requests=a.requests, **run(m, ticks, lone, a.warmup, a.ticks, stream, plain)))
+        res["rows"] = rows
+        for m in sorted({r["mode"] for r in rows}):
+            v = [r["us_per_tick"] for r in rows if r["mode"] == m]
+            res["%s@%d" % (m, a.requests)] = dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v)))
     print(json.dumps(res))
     if a.out:
         with open(a.out, "a") as fh:

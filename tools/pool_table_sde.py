@@ -21,7 +21,6 @@ import argparse
 import ctypes as C
 import json
 import sys
-import time
 
 import numpy as np
 import torch
@@ -100,36 +99,11 @@ def run(mode, ticks, ode_ticks, warmup, n_ticks, stream):
 
 def wall(dev, dtype, R, ticks):
     """host wall time per tick, steady state: a SlabPool(sde=True) of R rows against a RequestPool of the same R SDE requests"""
-    td = T.DTYPES[dtype][0]
-    out = {}
-    for name in ("slab_sde", "request_pool"):
-        dpm = T.solver(td, net=lambda x, t: x * 0.5)
-        pool = dpm.request_pool(slots=R, sde=True) if name == "slab_sde" else dpm.request_pool()
-        g = torch.Generator(device=dev).manual_seed(1)
-        xs = [torch.randn((1,) + SHAPE, generator=g, device=dev).to(td) for _ in range(R)]
-        nxt = 0
-        per = max(1, R // STEPS)
-
-        def feed():
-            nonlocal nxt
-            for _ in range(per):
-                pool.submit(xs[nxt % R], steps=STEPS, order=2, sde=True, seed=nxt)
-                nxt += 1
-        for _ in range(STEPS + 2):          # fill: R / 20 requests per tick, then steady state (as many finish as arrive)
-            feed()
-            pool.step()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(ticks):
-            feed()
-            pool.step()
-        t1 = time.perf_counter()
-        torch.cuda.synchronize()
-        t2 = time.perf_counter()
-        out[name] = dict(ticks=ticks, active=len(pool), host_us_per_tick=(t1 - t0) * 1e6 / ticks,
-                         wall_us_per_tick=(t2 - t0) * 1e6 / ticks)
-        del pool
-    return out
+    def sde_kwargs(n):
+        return dict(sde=True, seed=n)
+    return T.wall(dev, dtype, R, ticks, {
+        "slab_sde": lambda td, g: (T.wall_solver(td).request_pool(slots=R, sde=True), sde_kwargs),
+        "request_pool": lambda td, g: (T.wall_solver(td).request_pool(), sde_kwargs)})
 
 
 def main():
