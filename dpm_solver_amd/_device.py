@@ -154,13 +154,30 @@ def _bind_rescale(st, phi):
     return st
 
 
+def _apg_fields(eta, r, beta, plain, flags):
+    """The fields of a classifier-free stage record that adaptive projected guidance takes, for a wrapper of
+    cfg_apg(fn, eta, r, beta) (scalars or numpy arrays, one entry per record): (cg_scale, thr_ratio, thr_max, flags).  The
+    record carries DPM_F_CFG_APG, eta in `cg_scale`, the norm threshold in `thr_ratio` and the momentum in `thr_max`, each as
+    fp32.  (1, 0, 0) is classifier-free guidance itself, as in cfg_apg: no flag, and the three fields are `plain`'s -- (cg_scale,
+    thr_ratio, thr_max) of the record without the flag, as the planner writes them; `flags`: the record's own.  The one
+    statement of that conversion: _bind_apg and the slab pool's per-request parameters both go through it."""
+    e = np.asarray(eta, dtype=np.float64).astype(np.float32)
+    rr = np.asarray(r, dtype=np.float64).astype(np.float32)
+    bt = np.asarray(beta, dtype=np.float64).astype(np.float32)
+    fl = np.asarray(flags, dtype=np.uint32)
+    on = ~((e == 1) & (rr == 0) & (bt == 0))
+    cg, ratio, mx = (np.where(on, v, np.asarray(p, dtype=np.float32)) for v, p in zip((e, rr, bt), plain))
+    return cg, ratio, mx, np.where(on, fl | np.uint32(L.F_CFG_APG), fl & ~np.uint32(L.F_CFG_APG))
+
+
 def _bind_apg(st, apg):
     """Adaptive projected guidance (dpm_solver_amd.cfg_apg) in a stage record: a classifier-free stage carries DPM_F_CFG_APG, eta
     in `cg_scale`, the norm threshold in `thr_ratio` and the momentum in `thr_max` -- fields nothing else reads under the flag.
-    apg = None leaves the record as it is.  (The running average travels in dpm_buffers.workspace: the caller binds it.)"""
+    apg = None leaves the record as it is.  (The running average travels in dpm_buffers.workspace, in a DPM_TABLE_APG call in
+    dpm_buffers.thr_hint: the caller binds it.)"""
     if apg is not None and st.guidance == L.GUIDE["classifier-free"]:
-        st.cg_scale, st.thr_ratio, st.thr_max = float(apg[0]), float(apg[1]), float(apg[2])
-        st.flags |= L.F_CFG_APG
+        cg, ratio, mx, fl = _apg_fields(apg[0], apg[1], apg[2], (st.cg_scale, st.thr_ratio, st.thr_max), st.flags)
+        st.cg_scale, st.thr_ratio, st.thr_max, st.flags = float(cg), float(ratio), float(mx), int(fl)
     return st
 
 

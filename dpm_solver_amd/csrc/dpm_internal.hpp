@@ -44,7 +44,8 @@ int dpm_launch_het_shapes(const dpm_stage* st, const dpm_buffers* bs, int n_req,
 // kernels' 80-byte stage scalars (TableRow, dpm_table_kernel.hpp)
 constexpr size_t DPM_TABLE_HEADER_BYTES = 16, DPM_TABLE_ROW_BYTES = 8 * 8 + 80;
 // Behind the rows: the noise records of a DPM_TABLE_NOISE call (DPM_TABLE_NOISE_BYTES each: KNoiseTab, dpm_stage_kernel.hpp),
-// behind those the blend records of a DPM_TABLE_BLEND call (DPM_TABLE_BLEND_BYTES each: KBlendTab, dpm_table_blend.hpp).
+// behind those the blend records of a DPM_TABLE_BLEND call (DPM_TABLE_BLEND_BYTES each: KBlendTab, dpm_table_blend.hpp),
+// behind those the APG records of a DPM_TABLE_APG call (DPM_TABLE_APG_BYTES each: KApgTab, dpm_table_kernel.hpp).
 // DPM_TABLE_FILL is host code without a dtype (table_fill_rows and
 // the record fills, called by dpm_kernels.hip itself); DPM_TABLE_LAUNCH is ONE launch per group, one launcher per row kind, all of
 // one signature: the group's run of rows and its records (null for a kind without records) in DEVICE memory.
@@ -68,6 +69,9 @@ int dpm_launch_sample(const dpm_stage* st, const dpm_buffers* b, void* stream, v
 // (unit E, DPM_TABLE_RESCALE) DPM_F_CFG_RESCALE rows -- rows like any other, no records --, one workgroup per sample
 template <typename TS, typename TE>
 int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (unit F, DPM_TABLE_APG) DPM_F_CFG_APG rows and their APG records, one workgroup per sample
+template <typename TS, typename TE>
+int dpm_table_launch_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

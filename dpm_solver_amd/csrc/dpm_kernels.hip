@@ -43,8 +43,8 @@ struct PairUnits {
   HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
-  // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows
-  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale;
+  // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows, unit F's adaptive-projected-guidance rows
+  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale, table_launch_apg;
   // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance
   SampleFn rescale, apg;
 };
@@ -52,8 +52,8 @@ struct PairUnits {
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
-   dpm_table_launch_rescale<TS, TE>, dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>,                         \
-   dpm_launch_sample<TS, TE, DPM_F_CFG_APG>},
+   dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>,                                         \
+   dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -88,15 +88,16 @@ struct SampleGuidance {
   const char* banned_text;                               // ... as the message lists them
   bool needs_x0;                                         // defined on the data prediction: DPM_F_TO_X0 is required
   const char* f64_text;                                  // the double state's refusal, in brackets
-  int (*scalars)(const dpm_stage*, const dpm_buffers*);  // the checks of the flag's own fields
+  // the checks of the flag's own fields; `hint`: the call carries DPM_TABLE_APG (an APG average is thr_hint there)
+  int (*scalars)(const dpm_stage*, const dpm_buffers*, bool hint);
   SampleFn PairUnits::*launch;
 };
-int check_rescale_scalars(const dpm_stage* st, const dpm_buffers*) {
+int check_rescale_scalars(const dpm_stage* st, const dpm_buffers*, bool) {
   if (!(st->cg_scale > 0.f && st->cg_scale <= 1.f))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_RESCALE with phi=%g (dpm_stage.cg_scale), which is not in (0, 1]", (double)st->cg_scale);
   return DPM_OK;
 }
-int check_apg_scalars(const dpm_stage* st, const dpm_buffers* b) {
+int check_apg_scalars(const dpm_stage* st, const dpm_buffers* b, bool hint) {
   const float eta = st->cg_scale, r = st->thr_ratio, beta = st->thr_max;
   if (!(eta >= 0.f && eta <= 1.f))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with eta=%g (dpm_stage.cg_scale), which is not in [0, 1]", (double)eta);
@@ -104,7 +105,9 @@ int check_apg_scalars(const dpm_stage* st, const dpm_buffers* b) {
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a norm threshold of %g (dpm_stage.thr_ratio), which is not >= 0", (double)r);
   if (!(beta > -1.f && beta < 1.f))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum of %g (dpm_stage.thr_max), which is not in (-1, 1)", (double)beta);
-  if (beta != 0.f && !b->workspace)
+  if (beta != 0.f && hint && !b->thr_hint)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: DPM_F_CFG_APG with a momentum in a DPM_TABLE_APG call needs the running average in dpm_buffers.thr_hint");
+  if (beta != 0.f && !hint && !b->workspace)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum needs the running average in dpm_buffers.workspace");
   return DPM_OK;
 }
@@ -123,7 +126,7 @@ const SampleGuidance* sample_guidance(unsigned flags) {
 }
 
 // the checks of a stage under g.flag, in the order they speak (b->batch >= 1, n a multiple of it)
-int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dpm_buffers* b) {
+int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dpm_buffers* b, bool hint) {
   auto fail = [&](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, g.name, args...); };
   const int64_t per = b->n / b->batch;
   if (st->guidance != DPM_GUIDE_CFG)
@@ -131,7 +134,7 @@ int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dp
   if (b->n > 0 && per < g.min_per)  // (an empty batch is DPM_OK, as for every stage; its record is still checked)
     return fail(DPM_ERR_ARG, "stage_launch: %s needs samples of at least %d element%s (got %lld)", g.min_per,
                 g.min_per == 1 ? "" : "s", (long long)per);
-  if (const int rc = g.scalars(st, b)) return rc;
+  if (const int rc = g.scalars(st, b, hint)) return rc;
   // (the kernel dispatches the form at run time and has no launcher per form to report it, as the flag-less path has)
   const bool known = st->form >= DPM_FORM_LIN1 && st->form <= DPM_FORM_UNIPC;
   if (g.needs_x0) {  // what the flag is defined on comes before what it is combined with
@@ -149,8 +152,9 @@ int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dp
 }
 
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
-// base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base)
-int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false) {
+// base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base);
+// apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace
+int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false, bool apg_hint = false) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
@@ -158,7 +162,7 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
     return fail(DPM_ERR_ARG, "stage_launch: noise_sample0=%d (honoured by the SDE rows of a DPM_TABLE_NOISE call only)",
                 b->noise_sample0);
   if (const SampleGuidance* g = sample_guidance(st->flags))
-    if (const int rc = check_sample_guidance(*g, st, b)) return rc;
+    if (const int rc = check_sample_guidance(*g, st, b, apg_hint)) return rc;
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -340,15 +344,17 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
 }
 
 // The table of a table-mode call (include/dpm_hip.h, "Table mode"): the header, n_req rows, then n_req noise records if and only
-// if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND) -- record i of either section beside row i.
+// if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND), then n_req APG records (DPM_TABLE_APG) --
+// record i of every section beside row i.
 struct TableSections {
-  char *rows, *noise, *blend;
+  char *rows, *noise, *blend, *apg;
 };
 TableSections table_sections(void* table, int64_t n_req, int flags) {
   TableSections t;
   t.rows = static_cast<char*>(table) + DPM_TABLE_HEADER_BYTES;
   t.noise = t.rows + n_req * (int64_t)DPM_TABLE_ROW_BYTES;
   t.blend = t.noise + ((flags & DPM_TABLE_NOISE) ? n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
+  t.apg = t.blend + ((flags & DPM_TABLE_BLEND) ? n_req * (int64_t)DPM_TABLE_BLEND_BYTES : 0);
   return t;
 }
 
@@ -382,6 +388,11 @@ const RowKind kRowKinds[] = {
     // guidance-rescale requests (DPM_F_CFG_RESCALE; dpm_table_rescale.hpp), from ONE member on: the alternative is a launch of
     // one workgroup per sample per request.  Any of LIN1 / TWO / MS3 / DENOISE, any phi and guidance scale in one group.
     {DPM_TABLE_RESCALE, rescale_row_ok, nullptr, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_rescale},
+    // adaptive-projected-guidance requests (DPM_F_CFG_APG; dpm_table_apg.hpp), from ONE member on, for the same reason.  Any of
+    // LIN1 / TWO / MS3 / DENOISE, any eta, r, beta -- rows with and without a momentum -- and guidance scale in one group; the
+    // record carries the running average (the request's thr_hint in such a call) and the three scalars.
+    {DPM_TABLE_APG, apg_row_ok, nullptr, false, true, 1, &TableSections::apg, DPM_TABLE_APG_BYTES, table_fill_apg,
+     &PairUnits::table_launch_apg},
     // every other fusable request, in every call: groups of 2..HET_MAX keep the kernarg records (stage_kernel_het needs no
     // dependent load in front of its tile's own), larger ones take the table.  An SDE group of a call without DPM_TABLE_NOISE
     // is gathered here too -- het_same_group keeps it apart from the ODE groups -- and owns no rows (stage_launch_multi_het).
@@ -402,6 +413,18 @@ bool owns_row(int flag, const dpm_stage& st, const dpm_buffers& b, int flags, bo
   return k && k->flag == flag;
 }
 
+// one request on its own inside a per-request-stage call that carries `flags`.  In a DPM_TABLE_APG call the running average of
+// a DPM_F_CFG_APG request is its thr_hint (bs[0].workspace is the table): it is launched with a copy of its buffers whose
+// workspace is that.
+int launch_alone(const dpm_stage* st, const dpm_buffers* b, int flags, void* stream) {
+  if ((flags & DPM_TABLE_APG) && (st->flags & DPM_F_CFG_APG) && st->thr_max != 0.f) {
+    dpm_buffers bb = *b;
+    bb.workspace = bb.thr_hint;
+    return dpm_stage_launch_ev(st, &bb, stream, nullptr, nullptr);
+  }
+  return dpm_stage_launch_ev(st, b, stream, nullptr, nullptr);
+}
+
 // dpm_stage_launch_multi with per_request_stages: check every request, fuse the compatible ones in groups of up to
 // HET_MAX (first come, first grouped; the first MS3 or UNIPC record to join a group closes it to the other form, whose
 // records wait for a later group), launch the rest one by one.  With fuse_shapes a group may hold several n: one whose members
@@ -415,11 +438,11 @@ bool owns_row(int flag, const dpm_stage& st, const dpm_buffers& b, int flags, bo
 // smaller group and every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this
 // one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
-  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE);
+  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG);
   const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0;
   table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
-    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows)) return rc;
+    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;
@@ -488,14 +511,14 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
         int rc = m < 2 ? MULTI_NOT_BUILT : mixed ? p.het_shapes(ms, mb, m, stream) : p.het(ms, mb, m, stream);
         if (rc == MULTI_NOT_BUILT) {
           rc = DPM_OK;
-          for (int k = 0; k < m && !rc; ++k) rc = dpm_stage_launch_ev(&ms[k], &mb[k], stream, nullptr, nullptr);
+          for (int k = 0; k < m && !rc; ++k) rc = launch_alone(&ms[k], &mb[k], flags, stream);
         }
         if (rc) return rc;
       }
       for (int k = 0; k < cnt; ++k) done[gi[k]] = 1;
     } else {
       if (!fill)
-        if (const int rc = dpm_stage_launch_ev(&st[r0], &bs[r0], stream, nullptr, nullptr)) return rc;
+        if (const int rc = launch_alone(&st[r0], &bs[r0], flags, stream)) return rc;
       done[r0] = 1;
     }
   }
@@ -509,10 +532,11 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE);
+  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
-                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND)", o->table_mode);
+                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND / DPM_TABLE_RESCALE / DPM_TABLE_APG)",
+                         o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");
   if (o->fuse_shapes == 1)
@@ -525,7 +549,8 @@ int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_bu
                     owns_row(DPM_TABLE_THRESH, st[0], bs[0], o->table_mode, tuning_for(o).multi_fuse != 0);
   if ((st[0].flags & DPM_F_THRESH) && !row0)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with DPM_F_THRESH in st[0] (bs[0].workspace is the table)");
-  if ((st[0].flags & DPM_F_CFG_APG) && st[0].thr_max != 0.f)  // (its running average would be that workspace)
+  // (its running average would be that workspace; in a DPM_TABLE_APG call it is thr_hint)
+  if ((st[0].flags & DPM_F_CFG_APG) && st[0].thr_max != 0.f && !(o->table_mode & DPM_TABLE_APG))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode with a DPM_F_CFG_APG momentum in st[0] (bs[0].workspace is the table)");
   return DPM_OK;
 }

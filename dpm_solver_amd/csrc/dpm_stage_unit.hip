@@ -13,7 +13,9 @@
 //               no other unit includes) and of the table's guidance-rescale rows (stage_rescale_kernel_table, DPM_TABLE_RESCALE;
 //               dpm_table_rescale.hpp) and nothing else -- units A to D compile to the code they compiled to before it existed
 //   unit F (5): the launch of an adaptive-projected-guidance stage (stage_apg_kernel, DPM_F_CFG_APG; dpm_apg_kernel.hpp, which
-//               no other unit includes) and nothing else -- units A to E compile to the code they compiled to before it existed
+//               no other unit includes) and of the table's adaptive-projected-guidance rows (stage_apg_kernel_table,
+//               DPM_TABLE_APG; dpm_table_apg.hpp) and nothing else -- units A to E compile to the code they compiled to before
+//               it existed
 // Units E and F are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
@@ -31,6 +33,7 @@
 #if DPM_UNIT == 5
 #include "dpm_sample_frame.hpp"
 #include "dpm_apg_kernel.hpp"
+#include "dpm_table_apg.hpp"
 #endif
 
 #include <tuple>
@@ -141,4 +144,13 @@ int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_r
   return launch_table_rescale_typed<TS, TE>(st, bs, n_req, rows, s);
 }
 template int dpm_table_launch_rescale<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+#endif
+
+#if DPM_UNIT == 5
+template <typename TS, typename TE>
+int dpm_table_launch_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_apg_typed<TS, TE>(st, bs, n_req, rows, recs, s);
+}
+template int dpm_table_launch_apg<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

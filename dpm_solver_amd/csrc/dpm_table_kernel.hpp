@@ -205,6 +205,36 @@ inline void table_fill_noise(const dpm_stage* st, const dpm_buffers* bs, int n_r
   }
 }
 
+// ---- The APG record of a DPM_TABLE_APG call (include/dpm_hip.h, "Table mode"; read by stage_apg_kernel_table,
+// dpm_table_apg.hpp): what a DPM_F_CFG_APG row needs beyond its row.  KParams does not carry cg_scale / thr_ratio / thr_max
+// under the flag, so eta, r and beta travel here, with the running average -- declared in the global address space as
+// KBlendTab's pointers are and for the same reason: a plain pointer loaded from the table would make every access to the
+// average a flat one.  Null: the row has no momentum.
+struct alignas(16) KApgTab {
+  DPM_GLOBAL_PTR float* avg;
+  float eta, r, beta;  // dpm_stage.cg_scale / thr_ratio / thr_max
+  uint32_t pad[3];     // (zero)
+};
+static_assert(sizeof(KApgTab) == DPM_TABLE_APG_BYTES && alignof(KApgTab) == 16,
+              "include/dpm_hip.h publishes the APG record's size: the average, 3 scalars, 3 zero words");
+
+// ---- DPM_TABLE_FILL | DPM_TABLE_APG: the APG records of one group of APG rows, beside its rows (same order).  The average
+// of such a call is the request's thr_hint (checked by the caller: not null where beta != 0).  Host memory, no HIP call.
+inline void table_fill_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* recs) {
+  KApgTab* out = static_cast<KApgTab*>(recs);
+  for (int r = 0; r < n_req; ++r) {
+    KApgTab a;
+    std::memset(&a, 0, sizeof a);
+    const void* const avg = st[r].thr_max != 0.f ? bs[r].thr_hint : nullptr;
+    static_assert(offsetof(KApgTab, eta) == sizeof avg, "an APG record starts with its pointer");
+    std::memcpy(&a, &avg, sizeof avg);
+    a.eta = st[r].cg_scale;
+    a.r = st[r].thr_ratio;
+    a.beta = st[r].thr_max;
+    std::memcpy(&out[r], &a, sizeof a);
+  }
+}
+
 // ---- DPM_TABLE_LAUNCH: the skeleton of the streaming table launchers (plain / UniPC, noise and blend rows; the thresholded
 // rows' launch has another shape, dpm_table_thresh.hpp).  The group's size against table_group_cap, the tuning, `row_ok(r)` for
 // every member -- the kind's own argument check: `bad_row` is its error --, the prologue every member allows, the het kernels'

@@ -102,6 +102,32 @@ in cfg_scale, DPM_F_CFG_RESCALE and phi in cg_scale -- phi 0 clears the flag: a 
 and a phi outside [0, 1] are ValueError; `guidance_rescale=` outside a `rescale=True` pool is NotImplementedError.
 Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
 guidance scale and `cfg_rescale(..., phi)`, for any b, whichever rows it landed in.
+
+`request_pool(slots=S, apg=True)` is the slab pool that admits adaptive-projected-guidance requests
+(`dpm_solver_amd.cfg_apg`): an effectively classifier-free wrapper on a data-prediction solver, with or without APG parameters
+of its own.  The tick's two calls carry DPM_TABLE_APG: every row whose record carries DPM_F_CFG_APG is a row of the table
+whatever their number -- ONE stage_apg_kernel_table launch, one workgroup per row, the kernel of the request's own launch --
+beside the plain family's, which rows of parameters (1, 0, 0) take; behind the rows the table has an APG record per row (the
+staging is sized for that section).  What APG has and no other kind has is state that persists per request: with a momentum a
+request carries an fp32 running average of the guidance direction from evaluation to evaluation.  The pool holds the averages
+in one fp32 slab `[S, *sample_shape]`, allocated with the other slabs; in a DPM_TABLE_APG call a request's average is
+dpm_buffers.thr_hint (bs[0].workspace is the table), so every tick writes thr_hint = slab + row * per_sample * 4 into the
+buffer records of the rows whose record has a momentum and 0 into the others, vectorised.  Admission zero-fills the rows it
+takes -- one zero_() per run of consecutive rows, on admitting ticks only, before the tick's launch: a request starts from a
+zero average whatever request used its rows before.  The DENOISE stage of denoise_to_zero is an APG row too and updates the
+average, as in `sample()`.  Per request: `submit(..., apg=(eta, norm_threshold, momentum))`, checked with `cfg_apg`'s ranges and
+texts; the default is the wrapper's.  The values are kept per row; every tick writes them over the gathered records as
+`_bind_apg` writes them for a wrapper of those parameters (`_device._apg_fields`): DPM_F_CFG_APG, eta in cg_scale, the norm
+threshold in thr_ratio, the momentum in thr_max -- (1.0, 0.0, 0.0) clears the flag and restores the plain classifier-free
+fields: a plain row, as `cfg_apg(fn, 1, 0, 0)` is plain.  `guidance_scale=` works as in every classifier-free pool.  At its
+first submit such a pool refuses a sample of fewer than 8 elements, one whose element count is no multiple of 8, and one whose
+row is no multiple of 16 bytes.  Refused with NotImplementedError: `apg=True` with `rescale=True`, `sde=True`,
+`thresholding=True` or `inpaint=True` (the APG kernel has none of those epilogues); `submit_unipc` on a solver whose wrapper
+carries APG parameters; `apg=` outside an `apg=True` pool.  `apg=` on a pool whose wrapper is not classifier-free is
+ValueError.  Without `apg=True` a slab pool refuses a `cfg_apg` solver as before.
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
+guidance scale and `cfg_apg(fn, *its parameters)`, for any b, whichever rows it landed in and whatever request used those rows
+before.
 """
 import ctypes as C
 import math
@@ -141,6 +167,11 @@ _ROW = (
     ("gon", np.bool_, False),    # does its request bring its own guidance (submit's guidance_scale= / guidance_rescale=)?
     ("gs", np.float32, 0),       # its guidance scale
     ("gphi", np.float32, 0),     # its phi
+    # adaptive projected guidance (see "adaptive projected guidance" below)
+    ("aon", np.bool_, False),    # does its request bring its own APG parameters (submit's apg=)?
+    ("aeta", np.float32, 1),     # its eta, norm threshold and momentum; (1, 0, 0): classifier-free guidance itself
+    ("ar", np.float32, 0),
+    ("abeta", np.float32, 0),
     # inpainting rows (see "inpainting requests" below)
     ("bslot", np.int64, -1),     # the first row of its inpainting request: where _brec holds its blend records (-1: none)
     ("bmask", np.uint64, 0),     # the mask of its sample
@@ -153,6 +184,7 @@ _GROUPS = "whole 8-element groups of 16-byte aligned buffers; use request_pool()
 _ROW_CHECKS = (
     ("_sde", 0, math.inf, "slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is " + _GROUPS),
     ("_rsc", 8, math.inf, "slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is " + _GROUPS),
+    ("_apg", 8, math.inf, "slab pool: apg=True with a sample of %d elements -- an APG row of the table is " + _GROUPS),
     ("_thr", 0, L.THR_ROW_MAX, "slab pool: thresholding=True with a sample of %%d elements -- a thresholded row of the table is "
                                "at most %d elements (one workgroup's LDS), " % L.THR_ROW_MAX + _GROUPS),
 )
@@ -175,7 +207,7 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide", "apg")
 
 
 class _Blend:
@@ -192,7 +224,7 @@ class _Slot:
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False):
+    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False, apg=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
@@ -201,9 +233,11 @@ class SlabPool:
         self._thr = bool(thresholding)   # a thresholding solver's pool: the tick's calls carry DPM_TABLE_THRESH
         self._inp = bool(inpaint)        # inpainting requests admitted: the tick's calls carry DPM_TABLE_BLEND
         self._rsc = bool(rescale)        # guidance-rescale requests admitted: the tick's calls carry DPM_TABLE_RESCALE
+        self._apg = bool(apg)            # adaptive-projected-guidance requests admitted: the tick's calls carry DPM_TABLE_APG
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
                         | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
-                        | (L.TABLE_RESCALE if self._rsc else 0))
+                        | (L.TABLE_RESCALE if self._rsc else 0) | (L.TABLE_APG if self._apg else 0))
+        self._avg = None                 # (an apg=True pool) the running averages: one fp32 slab [S, *sample_shape]
         self._cols = []                  # the per-row arrays of _ROW (self._req, self._pos, ...), each with its idle value
         for name, dtype, idle in _ROW:
             setattr(self, "_" + name, np.full(slots, idle, dtype=dtype))
@@ -255,6 +289,35 @@ class SlabPool:
         if not self._rsc:
             s._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built with "
                              "request_pool(slots=..., rescale=True) only")
+        if not self._apg:
+            s._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance stages take the table in a pool built "
+                         "with request_pool(slots=..., apg=True) only")
+
+    def _apg_params(self, apg):
+        """the request's own (eta, norm threshold, momentum) of submit's apg=, checked as cfg_apg checks them; None: the
+        wrapper's"""
+        if apg is None:
+            return None
+        w = self._s._wrapped
+        if w is None or w.effective_guidance != "classifier-free":
+            raise ValueError("slab pool: apg= belongs to a classifier-free wrapper (with an unconditional condition and a "
+                             "guidance scale other than 1)")
+        if not isinstance(apg, (tuple, list)) or len(apg) != 3:
+            raise ValueError("slab pool: apg= takes (eta, norm_threshold, momentum), got %r" % (apg,))
+        eta, r, beta = apg
+        for name, v in (("eta", eta), ("norm_threshold", r), ("momentum", beta)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
+                raise ValueError("cfg_apg: %s must be a real number, got %r" % (name, v))
+        if not 0.0 <= float(eta) <= 1.0:
+            raise ValueError("cfg_apg: eta must be in [0, 1], got %r" % (eta,))
+        if not (0.0 <= float(r) < float("inf")):
+            raise ValueError("cfg_apg: norm_threshold must be a finite number >= 0 (0 = off), got %r" % (r,))
+        if not -1.0 < float(beta) < 1.0:
+            raise ValueError("cfg_apg: momentum must be in (-1, 1), got %r" % (beta,))
+        if not self._apg:
+            raise NotImplementedError("slab pool: apg= -- projected-guidance stages take the table in a pool built with "
+                                      "request_pool(slots=..., apg=True) only")
+        return float(eta), float(r), float(beta)
 
     def _guidance(self, scale, phi):
         """the request's own (guidance scale, phi) of submit's guidance_scale= / guidance_rescale=, checked; None: the wrapper's"""
@@ -306,7 +369,7 @@ class SlabPool:
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
                condition=None, unconditional_condition=None, seed=None, generator=None, blend=None, guidance_scale=None,
-               guidance_rescale=None):
+               guidance_rescale=None, apg=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -320,9 +383,13 @@ class SlabPool:
         built with correcting_xt_fn=mb; see the module docstring for the forms of `MaskBlend` admitted.
         `guidance_scale=g` (a classifier-free pool): the request's own guidance scale -- the result of `sample()` on a solver
         whose wrapper has that scale; g = 1.0 is refused.  `guidance_rescale=phi` (a pool built with rescale=True): the request's
-        own phi in [0, 1] -- the result of `sample()` under `cfg_rescale(model_fn, phi)`.  Default for both: the wrapper's."""
+        own phi in [0, 1] -- the result of `sample()` under `cfg_rescale(model_fn, phi)`.  Default for both: the wrapper's.
+        `apg=(eta, norm_threshold, momentum)` (a pool built with apg=True): the request's own adaptive projected guidance --
+        the result of `sample()` under `cfg_apg(model_fn, eta, norm_threshold, momentum)`; (1.0, 0.0, 0.0) is classifier-free
+        guidance itself.  Default: the wrapper's."""
         s = self._s
         guide = self._guidance(guidance_scale, guidance_rescale)
+        apg = self._apg_params(apg)
         if blend is not None:
             if not self._inp:
                 raise NotImplementedError("slab pool: blend= -- mask-blend stages take the table in a pool built with "
@@ -350,7 +417,7 @@ class SlabPool:
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   solver_type, sde=bool(sde))
-        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide)
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide, apg)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
@@ -446,7 +513,7 @@ class SlabPool:
         q.keep += list(ops.values())
         return q
 
-    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None):
+    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None, apg=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
@@ -459,7 +526,7 @@ class SlabPool:
         q = _Waiting()
         q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
         q.blend = None if blend is None else self._blend_of(blend, x, plan, sd)
-        q.guide = guide
+        q.guide, q.apg = guide, apg
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -479,6 +546,8 @@ class SlabPool:
         self._x = [torch.zeros((nS,) + shape, dtype=sd, device=dev) for _ in range(2)]
         self._hist = [torch.zeros((S,) + shape, dtype=sd, device=dev) for _ in range(3)]
         self._hbase = np.array([t.data_ptr() for t in self._hist], dtype=np.uint64)
+        if self._apg:
+            self._avg = torch.zeros((S,) + shape, dtype=torch.float32, device=dev)
         self._cur = 0
         self._cslab = None
         if cond is not None:
@@ -524,6 +593,8 @@ class SlabPool:
             ra = np.array([r for _, rows in taken for r in rows], dtype=np.int64)
             for col, idle in self._cols:
                 col[ra] = idle
+            if self._apg:
+                self._apg_reset(ra)
         blends = []
         for q, rows in taken:
             self._load_rows(q, rows)
@@ -534,6 +605,8 @@ class SlabPool:
                 self._sde_admit(q, ra)
             if q.guide is not None:
                 self._guide_admit(q, ra)
+            if self._apg:
+                self._apg_admit(q, ra)
             if q.blend is not None:
                 self._blend_admit(q, rows, ra)
                 blends.append((rows, q.blend))
@@ -619,6 +692,42 @@ class SlabPool:
         st["cfg_scale"] = np.where(on, cs, rec["cfg_scale"])
         st["cg_scale"] = np.where(on, cg, rec["cg_scale"])
         st["flags"] = np.where(on, fl, rec["flags"])
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # adaptive projected guidance (an apg=True pool).  Row fields: aon, aeta, ar, abeta.  Checked at submit: _apg_params.
+    # Kept by the pool: _avg, the running averages, row by row.
+    # ------------------------------------------------------------------------------------------------------------------
+    def _apg_reset(self, ra):
+        """a request starts from a zero average, whoever used its rows before: one zero_() per run of consecutive rows among
+        the rows this tick admits"""
+        for r0, cnt in _runs(sorted(ra.tolist())):
+            self._avg[r0:r0 + cnt].zero_()
+
+    def _apg_admit(self, q, ra):
+        """the request's own parameters, or the wrapper's ((1, 0, 0): it has none)"""
+        own = q.apg if q.apg is not None else self._s._apg_params()
+        self._aon[ra] = q.apg is not None
+        self._aeta[ra], self._ar[ra], self._abeta[ra] = own if own is not None else (1.0, 0.0, 0.0)
+
+    def _apg_tick(self, st, rows, rec):
+        """rows whose request brought its own parameters or its own guidance scale: what _bind_apg writes for a wrapper of the
+        row's parameters over the plain record of the row's scale ((1, 0, 0): no flag, a plain row), over the gathered records.
+        Every other row keeps what _prep_stage bound."""
+        on = (self._aon[rows] | self._gon[rows]) & (rec["guidance"] == L.GUIDE["classifier-free"])
+        s = self._s                      # (the plain record: the planner's cg_scale of the row's scale, the solver's two fields)
+        plain = (st["cfg_scale"] * rec["sigma_e"], np.float32(s.dynamic_thresholding_ratio), np.float32(s.thresholding_max_val))
+        cg, ratio, mx, fl = DV._apg_fields(self._aeta[rows], self._ar[rows], self._abeta[rows], plain, st["flags"])
+        st["cg_scale"] = np.where(on, cg, st["cg_scale"])
+        st["thr_ratio"] = np.where(on, ratio, st["thr_ratio"])
+        st["thr_max"] = np.where(on, mx, st["thr_max"])
+        st["flags"] = np.where(on, fl, st["flags"])
+
+    def _apg_buffers(self, st, b, rows):
+        """the running average of a DPM_TABLE_APG call is thr_hint: the row's slice of the slab where its record has a
+        momentum, 0 elsewhere"""
+        mom = ((st["flags"] & np.uint32(L.F_CFG_APG)) != 0) & (st["thr_max"] != 0)
+        b["thr_hint"] = np.where(mom, np.uint64(self._avg.data_ptr()) + rows.astype(np.uint64) * np.uint64(self._per * 4),
+                                 np.uint64(0))
 
     # ------------------------------------------------------------------------------------------------------------------
     # inpainting requests.  Row fields: bslot, bmask, bper (and samp).  Kept per request: _blends (built at submit: _blend_of)
@@ -709,7 +818,11 @@ class SlabPool:
             st[:] = rec
             if self._cfg:
                 self._guide_tick(st, rows, rec)
+            if self._apg:
+                self._apg_tick(st, rows, rec)
             self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed)
+            if self._apg:
+                self._apg_buffers(st, b, rows)
             self._call_opts(b)
             if self._sde:
                 self._sde_tick(b, rows, rec)

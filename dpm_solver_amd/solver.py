@@ -770,7 +770,8 @@ class DPM_Solver:
             self._group = None
 
 
-    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False):
+    def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False,
+                     apg=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -791,6 +792,12 @@ class DPM_Solver:
         table-driven launch too (DPM_TABLE_RESCALE: one stage_rescale_kernel_table launch, one workgroup per row); samples of
         whole 8-element groups.  Not together with sde / thresholding / inpaint (the rescale kernel has none of those
         epilogues); without the flag a slab pool refuses a `cfg_rescale` solver.
+        `slots=S, apg=True`: the slab pool of a classifier-free wrapper that admits adaptive-projected-guidance requests --
+        the wrapper's own parameters (`cfg_apg`) or the request's (`submit(x, ..., apg=(eta, norm_threshold, momentum))`),
+        their stages in the table-driven launch too (DPM_TABLE_APG: one stage_apg_kernel_table launch, one workgroup per row;
+        the pool holds the running averages in a slab of its own, zeroed at admission); samples of whole 8-element groups, a
+        data-prediction solver.  Not together with rescale / sde / thresholding / inpaint (the APG kernel has none of those
+        epilogues); without the flag a slab pool refuses a `cfg_apg` solver.
         Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
@@ -815,19 +822,41 @@ class DPM_Solver:
             if self._wrapped is None or self._wrapped.effective_guidance != "classifier-free":
                 raise ValueError("request_pool: rescale=True needs a classifier-free wrapper (an unconditional condition and a "
                                  "guidance scale other than 1): guidance rescale rescales the guided output")
+        if apg:
+            if slots is None:
+                raise ValueError("request_pool: apg=True belongs to a slab pool (slots=...); a RequestPool takes a "
+                                 "cfg_apg solver as it is")
+            for on, name, why in ((rescale, "rescale", "the APG kernel has no guidance rescale"),
+                                  (sde, "sde", "the APG kernel has no noise epilogue"),
+                                  (thresholding, "thresholding", "the APG kernel has no thresholding"),
+                                  (inpaint, "inpaint", "the APG kernel has no mask-blend epilogue")):
+                if on:
+                    raise NotImplementedError("request_pool: apg=True with %s=True -- %s (a follow-up)" % (name, why))
+            if self._wrapped is None or self._wrapped.effective_guidance != "classifier-free":
+                raise ValueError("request_pool: apg=True needs a classifier-free wrapper (an unconditional condition and a "
+                                 "guidance scale other than 1): adaptive projected guidance projects the guidance direction")
+            if self.algorithm_type != "dpmsolver++":
+                raise NotImplementedError("request_pool: apg=True with algorithm_type='dpmsolver' -- adaptive projected guidance "
+                                          "is defined on the data prediction (algorithm_type='dpmsolver++')")
+            if self._thresholding or self._rescale_phi():
+                raise NotImplementedError("request_pool: apg=True on a solver with %s -- the APG kernel has none of those "
+                                          "epilogues (a follow-up)"
+                                          % ("correcting_x0_fn='dynamic_thresholding'" if self._thresholding else "cfg_rescale"))
         if thresholding and not self._thresholding:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
-            self._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance rows in the table are a follow-up; "
-                            "a RequestPool (no slots) takes a cfg_apg solver as it is")
+            if not apg:
+                self._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance stages take the table in a pool "
+                                "built with request_pool(slots=..., apg=True) only; a RequestPool (no slots) takes a cfg_apg "
+                                "solver as it is")
             if not rescale:
                 self._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built "
                                     "with request_pool(slots=..., rescale=True) only")
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale)
+            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -89,11 +89,15 @@ extern "C" {
    ONE stage launch -- a kernel that owns a whole sample, splits the guidance direction of the two data predictions into its
    components parallel and orthogonal to the conditional one, damps the parallel one, caps the direction's norm and optionally
    carries a running average of it from stage to stage (see DPM_F_CFG_APG; no entry point added, no struct changed).
+   215 DPM_TABLE_APG (a flag on table_mode), DPM_TABLE_APG_BYTES / DPM_SIZEOF_TABLE_APG: adaptive-projected-guidance stages in
+   the table -- every qualifying DPM_F_CFG_APG request owns a row and an APG record behind the rows, a group of them is ONE
+   stage_apg_kernel_table launch, one workgroup per sample; in such a call a request's running average is dpm_buffers.thr_hint
+   (see "Table mode"; no entry point added, no struct changed size).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 214
+#define DPM_HIP_VERSION 215
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -223,7 +227,9 @@ enum {
                                else reads under it: dpm_stage.cg_scale carries eta in [0, 1], dpm_stage.thr_ratio the norm
                                threshold r >= 0 (0 = off), dpm_stage.thr_max the momentum beta in (-1, 1) (0 = off), and with
                                beta != 0 dpm_buffers.workspace the RUNNING AVERAGE: n fp32 values in the state's flat order, read
-                               and written in place (the caller zero-fills it where a trajectory starts).  For each sample of
+                               and written in place (the caller zero-fills it where a trajectory starts).  In a table call that
+                               carries DPM_TABLE_APG (version 215) the running average is dpm_buffers.thr_hint instead, for EVERY
+                               request of the call, and workspace is not read for it: see "Table mode".  For each sample of
                                the launch, P = n / batch elements, s = cfg_scale:
                                  c = x0 of the conditional output e0, u = x0 of the unconditional output e1: the noise
                                      prediction of the raw output on xe (x_start / v / score conversion), then
@@ -242,7 +248,7 @@ enum {
                                A degenerate sample (S_cc == 0) gets what IEEE gives.  With eta = 1, r = 0 and beta = 0 the result
                                is classifier-free guidance up to rounding.
                                DPM_ERR_ARG: the flag without DPM_GUIDE_CFG; eta, r or beta out of range or NaN; beta != 0 with a
-                               null workspace; an unknown form; P < 1 (an empty batch, n == 0, is DPM_OK and launches nothing).
+                               null workspace (a null thr_hint in a DPM_TABLE_APG call); an unknown form; P < 1 (an empty batch, n == 0, is DPM_OK and launches nothing).
                                DPM_ERR_UNSUPPORTED (this version): the flag without DPM_F_TO_X0 (it is defined on the data
                                prediction); together with DPM_F_CFG_RESCALE, DPM_F_THRESH, DPM_F_BLEND or DPM_F_NOISE;
                                DPM_FORM_UNIPC; a double state; eps_stride other than 0 or P; device-resident coefficients.  No
@@ -333,9 +339,15 @@ enum { DPM_TABLE_BLEND = 32 }; /* version 211: a flag OR-ed onto DPM_TABLE_FILL 
 enum { DPM_TABLE_RESCALE = 128 }; /* version 213: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the three
                                      flags above: DPM_F_CFG_RESCALE stages take rows too, rows like any other.  (Bits 16 and 64
                                      are unassigned: table_mode 16 .. 31 and 64 .. 127 stay DPM_ERR_ARG.) */
+enum { DPM_TABLE_APG = 512 }; /* version 215: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the four flags
+                                 above: DPM_F_CFG_APG stages take rows too, each with an APG record behind the rows, and the
+                                 running average of every DPM_F_CFG_APG request of the call is its dpm_buffers.thr_hint.  (Bits
+                                 16, 64 and 256 are unassigned: table_mode 16 .. 31, 64 .. 127 and 256 .. 511 stay DPM_ERR_ARG,
+                                 and so does every mode from 512 on that has one of those bits.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 #define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
+#define DPM_TABLE_APG_BYTES 32      /* one APG record (= dpm_sizeof(DPM_SIZEOF_TABLE_APG)) */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -349,7 +361,8 @@ typedef struct dpm_buffers {
   void* x_out;      /* result of the update                                  [n] state dtype     */
   void* m_out;      /* new model value (only if DPM_F_STORE_M)               [n] state dtype     */
   void* workspace;  /* thresholding scratch, dpm_threshold_workspace_bytes() bytes (may be NULL);
-                       DPM_F_CFG_APG with a momentum: the running average, n fp32 values             */
+                       DPM_F_CFG_APG with a momentum: the running average, n fp32 values -- outside a
+                       DPM_TABLE_APG call, where thr_hint holds it                                   */
   int64_t n;          /* total elements = batch * per_sample                                     */
   int64_t batch;      /* number of independent samples                                           */
   int32_t state_dtype; /* DPM_DTYPE_* of x, xe, h1, h2, x_out, m_out                             */
@@ -381,7 +394,11 @@ typedef struct dpm_buffers {
                           stage's select bound (a correct prediction saves the bound search and shrinks the exchange; a
                           wrong one is detected and costs one extra exchange, never exactness); [2]: route taken
                           (diagnostics: 1 predicted, 2 prediction rejected, 3 single exchange, 4 general); [3]: entries of
-                          the last union gathered (diagnostics)                                                      */
+                          the last union gathered (diagnostics).
+                          DPM_F_CFG_APG with a momentum in a call that carries DPM_TABLE_APG (version 215; the flag excludes
+                          DPM_F_THRESH, so no APG stage reads a hint): the RUNNING AVERAGE, n fp32 values in the state's flat
+                          order, read and written in place -- private state that persists over one trajectory, as the hint
+                          is; the caller zero-fills it where a trajectory starts.  NULL with beta != 0: DPM_ERR_ARG      */
   const dpm_launch_opts* opts; /* per-call options, NULL = defaults (version 200; dpm_stage_launch_multi reads bs[0].opts) */
   const dpm_stage_f64* coef64; /* DPM_DTYPE_F64 launches: the stage's scalars in double (NULL: the dpm_stage's floats, exactly) */
 } dpm_buffers;
@@ -540,7 +557,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC and DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE) and DPM_F_CFG_APG (without DPM_TABLE_APG) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -618,8 +635,44 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    buffer, a separate evaluation state ...) goes, in the same call, as its own dpm_stage_launch, which rescales too: the same
    bits, one more launch.  Without the flag every call is version 212's.  Every sample gets the bits of its request's own
    dpm_stage_launch.
+   APG rows (version 215): DPM_TABLE_APG OR-ed onto either mode, alone or with any of the four flags above, makes the same tick
+   with adaptive-projected-guidance stages (DPM_F_CFG_APG) in the table (stage_apg_kernel_table: the kernel of the request's
+   own launch, one workgroup of 512 threads per sample, with pointers and stage scalars read from the sample's row and its
+   record; no cluster, no workspace, no wait on another workgroup).
+   Where the running average lives in such a call: bs[0].workspace is the table, and in a pool any request may be request 0, so
+   in a call that carries DPM_TABLE_APG -- FILL or LAUNCH -- the running average of EVERY DPM_F_CFG_APG request with beta != 0 is
+   its dpm_buffers.thr_hint (n fp32 values, as workspace holds them elsewhere), whether the request owns a row or goes as its
+   own launch in the same call; workspace is not read for it.  A request launched on its own inside such a call is launched
+   with a copy of its buffers whose workspace is its thr_hint.  beta != 0 with a null thr_hint is DPM_ERR_ARG: nothing is
+   launched, no byte written.  The refusal of a DPM_F_CFG_APG momentum in st[0] does not apply to such a call.  Without the flag
+   every rule of version 214 stands: workspace is the average, and the refusal applies.
+   A DPM_F_CFG_APG request owns a row when dpm_stage_launch accepts the flag on it -- classifier-free guidance and DPM_F_TO_X0,
+   eta in [0, 1], r >= 0, beta in (-1, 1), no DPM_F_THRESH / DPM_F_BLEND / DPM_F_NOISE / DPM_F_CFG_RESCALE, no DPM_FORM_UNIPC, a
+   2- or 4-byte dtype pair, a dense network output -- and its form is LIN1, TWO, MS3 or DPM_FORM_DENOISE, its evaluation state
+   is its state, its SAMPLE, n / batch elements, is whole 8-element groups (a multiple of 16 bytes in either dtype), and every
+   buffer, x_out2 included and with beta != 0 the average too, is 16-byte aligned.  Such requests form groups of their own that
+   agree on dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the four forms, eta, r, beta (rows with and without a
+   momentum), the guidance scale, DPM_F_STORE_M and the duplicate store share a group: each is the row's own.  Every group,
+   from ONE member on, is one run of rows and ONE launch (below 2^31 samples), the runs in the order the groups open, among
+   those of the other families.  Behind the rows -- behind the n_req noise records a DPM_TABLE_NOISE call has room for and
+   behind the n_req blend records of a DPM_TABLE_BLEND call -- the table holds one APG record per row: the record of table row
+   i (counted over all runs) is the DPM_TABLE_APG_BYTES bytes at
+     dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * dpm_sizeof(DPM_SIZEOF_TABLE_ROW)
+       + (DPM_TABLE_NOISE set ? n_req * DPM_TABLE_NOISE_BYTES : 0) + (DPM_TABLE_BLEND set ? n_req * DPM_TABLE_BLEND_BYTES : 0)
+       + DPM_TABLE_APG_BYTES * i
+   so the record sections never overlap and each keeps its own index; the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req
+   * (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + [DPM_TABLE_NOISE_BYTES] + [DPM_TABLE_BLEND_BYTES] + [DPM_TABLE_APG_BYTES]) bytes.  A
+   record is one device pointer -- the running average, thr_hint of the request's dpm_buffers, NULL when beta == 0 --, the bits
+   of eta, r and beta (st[r].cg_scale / thr_ratio / thr_max: the row's stage scalars do not carry them under the flag), and
+   three zero words.  Each sample of a row advances its own slice of the row's average (sample k: the P values from k * P on).
+   FILL writes the records of APG rows only and leaves every other byte of the section untouched; LAUNCH reads them in place
+   (scalar loads) and writes nothing to the table.  A DPM_F_CFG_APG request that does not qualify (a sample of 12 elements, a
+   misaligned buffer or average, a separate evaluation state ...) goes, in the same call, as its own dpm_stage_launch, which
+   projects too: the same bits, one more launch.  Every sample gets the bits of its request's own dpm_stage_launch (with the
+   average in workspace).
    Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND,
-   DPM_TABLE_RESCALE: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, and each of those plus 128), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   DPM_TABLE_RESCALE, DPM_TABLE_APG: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, each of those plus 128, and each
+   of all these plus 512; bit 256 is unassigned), a non-zero one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
@@ -763,7 +816,8 @@ enum { DPM_SIZEOF_STAGE = 0, DPM_SIZEOF_BUFFERS = 1, DPM_SIZEOF_PLAN_DESC = 2, D
        DPM_SIZEOF_ADAPTIVE_DESC = 4, DPM_SIZEOF_LAUNCH_OPTS = 5, DPM_SIZEOF_STAGE_F64 = 6,
        DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */,
        DPM_SIZEOF_TABLE_NOISE = 10 /* version 209: a noise record of a DPM_TABLE_NOISE table (9 is unassigned: 0) */,
-       DPM_SIZEOF_TABLE_BLEND = 12 /* version 211: a blend record of a DPM_TABLE_BLEND table (11 is unassigned: 0) */ };
+       DPM_SIZEOF_TABLE_BLEND = 12 /* version 211: a blend record of a DPM_TABLE_BLEND table (11 is unassigned: 0) */,
+       DPM_SIZEOF_TABLE_APG = 14 /* version 215: an APG record of a DPM_TABLE_APG table (13 is unassigned: 0) */ };
 DPM_API size_t dpm_sizeof(int which);
 DPM_API const char* dpm_last_error(void); /* thread-local text of the last non-zero return */
 DPM_API int dpm_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len);
