@@ -181,6 +181,14 @@ def _bind_apg(st, apg):
     return st
 
 
+def _bind_zstar(st):
+    """CFG-Zero* (dpm_solver_amd.cfg_zero_star) in a stage record: a classifier-free stage carries DPM_F_CFG_ZSTAR and nothing
+    else -- the flag reads cfg_scale alone.  Every other record stays as it is."""
+    if st.guidance == L.GUIDE["classifier-free"]:
+        st.flags |= L.F_CFG_ZSTAR
+    return st
+
+
 def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=None, opts=None, coef64=None):
     """One `dpm_stage_launch` on the current stream.  Allocates x_out (and m_out when the stage stores
     its model value) through torch's caching allocator; returns (x_out, m_out).

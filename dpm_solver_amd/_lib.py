@@ -39,6 +39,7 @@ F_NOISE = 64
 F_UNIPC_DP, F_UNIPC_P2, F_STORE_XC = 128, 256, 512
 F_CFG_RESCALE = 1024                      # guidance rescale under classifier-free guidance; dpm_stage.cg_scale carries phi (version 212)
 F_CFG_APG = 2048                          # adaptive projected guidance; cg_scale / thr_ratio / thr_max carry eta / r / beta (version 214)
+F_CFG_ZSTAR = 4096                        # CFG-Zero*: the unconditional output scaled by its per-sample fit; no field of its own (version 216)
 SRC_STATE, SRC_TMP = 0, 1
 # knobs of the LAB build (include/dpm_lab.h: dpm_tuning_set / dpm_tuning_get; the product library has none)
 TUNE_UNROLL, TUNE_NONTEMPORAL, TUNE_BLOCKS_PER_CU, TUNE_ASSUME_RESIDENT = 0, 1, 2, 3
@@ -303,8 +304,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 215:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 215 -- stale library, rebuild"
+if lib.dpm_version() < 216:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 216 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16

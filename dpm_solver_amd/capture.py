@@ -67,6 +67,7 @@ def auto_captured(self, x, kw, return_intermediate):
     key = (tuple(sorted((k, (float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)) for k, v in kw.items())),
            tuple(x.shape), x.dtype, x.stride(), dev.index, torch.cuda.current_stream(dev).cuda_stream,
            bool(self.cluster_in_graph), int(self.thr_spin_limit), self._model_codes(), self._rescale_phi(), self._apg_params(),
+           self._zero_star(),
            self._thresholding,
            float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val), self.algorithm_type, self._state_dtype,
            self._sdtype(x), bool(self.adaptive_on_device), int(self.adaptive_lookahead), self.adaptive_max_iterations,

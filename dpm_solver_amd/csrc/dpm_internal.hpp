@@ -20,7 +20,8 @@
 // The single-request launchers of one dtype pair are spread over two translation units (compile time: the build is the
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
 // pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones, unit D (3) the
-// table-driven launch's mask-blend rows, unit E (4) the guidance-rescale stage, unit F (5) the adaptive-projected-guidance stage.
+// table-driven launch's mask-blend rows, unit E (4) the guidance-rescale stage, unit F (5) the adaptive-projected-guidance stage,
+// unit G (6) the CFG-Zero* stage.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -63,7 +64,8 @@ template <typename TS, typename TE>
 int dpm_table_launch_blend(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // one classifier-free stage under a per-sample guidance FLAG, one workgroup per sample: DPM_F_CFG_RESCALE (unit E, guidance
-// rescale, stage_rescale_kernel) or DPM_F_CFG_APG (unit F, adaptive projected guidance, stage_apg_kernel)
+// rescale, stage_rescale_kernel), DPM_F_CFG_APG (unit F, adaptive projected guidance, stage_apg_kernel) or DPM_F_CFG_ZSTAR
+// (unit G, CFG-Zero*, stage_zstar_kernel)
 template <typename TS, typename TE, unsigned FLAG>
 int dpm_launch_sample(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
 // (unit E, DPM_TABLE_RESCALE) DPM_F_CFG_RESCALE rows -- rows like any other, no records --, one workgroup per sample

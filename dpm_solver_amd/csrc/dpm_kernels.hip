@@ -45,15 +45,17 @@ struct PairUnits {
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
   // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows, unit F's adaptive-projected-guidance rows
   TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale, table_launch_apg;
-  // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance
-  SampleFn rescale, apg;
+  // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance, unit G's
+  // CFG-Zero*
+  SampleFn rescale, apg, zstar;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
    dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>,                                         \
-   dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>},
+   dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
+   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -111,8 +113,14 @@ int check_apg_scalars(const dpm_stage* st, const dpm_buffers* b, bool hint) {
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG_APG with a momentum needs the running average in dpm_buffers.workspace");
   return DPM_OK;
 }
-// DPM_F_CFG_APG first: a record that sets both flags (eta shares cg_scale with phi) is reported by that flag's checks
+int check_no_scalars(const dpm_stage*, const dpm_buffers*, bool) { return DPM_OK; }  // (DPM_F_CFG_ZSTAR reads cfg_scale alone)
+// DPM_F_CFG_ZSTAR first: a record that sets it together with one of the two older flags is reported by its checks, and a record
+// without it meets the rows it always met.  Then DPM_F_CFG_APG: a record that sets both older flags (eta shares cg_scale with
+// phi) is reported by that flag's checks
 constexpr SampleGuidance kSampleGuidance[] = {
+    {DPM_F_CFG_ZSTAR, "DPM_F_CFG_ZSTAR", 1, DPM_F_CFG_RESCALE | DPM_F_CFG_APG | DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE,
+     "guidance rescale, adaptive projected guidance, thresholding, mask blend or noise", false, "no double kernel",
+     check_no_scalars, &PairUnits::zstar},
     {DPM_F_CFG_APG, "DPM_F_CFG_APG", 1, DPM_F_CFG_RESCALE | DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE,
      "guidance rescale, thresholding, mask blend or noise", true, "no double kernel", check_apg_scalars, &PairUnits::apg},
     {DPM_F_CFG_RESCALE, "DPM_F_CFG_RESCALE", 2, DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE, "thresholding, mask blend or noise", false,
@@ -120,6 +128,8 @@ constexpr SampleGuidance kSampleGuidance[] = {
 };
 // the row of a stage's per-sample guidance flag; nullptr: it has none
 const SampleGuidance* sample_guidance(unsigned flags) {
+  // (a request without any of them -- every request of a plain tick -- is decided by one test, whatever the number of rows)
+  if (!(flags & (DPM_F_CFG_ZSTAR | DPM_F_CFG_APG | DPM_F_CFG_RESCALE))) return nullptr;
   for (const SampleGuidance& g : kSampleGuidance)
     if (flags & g.flag) return &g;
   return nullptr;

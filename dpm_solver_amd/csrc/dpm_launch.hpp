@@ -180,8 +180,8 @@ inline bool plain_request(const dpm_buffers& b) {
 // join any ODE group; MS3 and UNIPC records never share one (no kernel dispatches both): the first record of either form
 // to join decides which of the two the group takes, records of the other form wait for a later group.
 inline bool fusable_request(const dpm_stage& st, const dpm_buffers& b) {
-  // (rescale, adaptive projected guidance: a kernel per sample, never fused)
-  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_CFG_RESCALE | DPM_F_CFG_APG)) return false;
+  // (rescale, adaptive projected guidance, CFG-Zero*: a kernel per sample, never fused)
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_CFG_RESCALE | DPM_F_CFG_APG | DPM_F_CFG_ZSTAR)) return false;
   if (st.guidance != DPM_GUIDE_NONE && st.guidance != DPM_GUIDE_CFG) return false;
   const bool ms3_ok = !(st.flags & DPM_F_NOISE);
   const bool unipc_ok = !(st.flags & (DPM_F_NOISE | DPM_F_STORE_XC));

@@ -1,5 +1,5 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled thirty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5> (__graft_entry__.py).
+// translation unit: compiled thirty-five times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5|6> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
@@ -16,10 +16,12 @@
 //               no other unit includes) and of the table's adaptive-projected-guidance rows (stage_apg_kernel_table,
 //               DPM_TABLE_APG; dpm_table_apg.hpp) and nothing else -- units A to E compile to the code they compiled to before
 //               it existed
-// Units E and F are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
+//   unit G (6): the launch of a CFG-Zero* stage (stage_zstar_kernel, DPM_F_CFG_ZSTAR; dpm_zstar_kernel.hpp, which no other unit
+//               includes) and nothing else -- units A to F compile to the code they compiled to before it existed
+// Units E, F and G are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5|6>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -34,6 +36,10 @@
 #include "dpm_sample_frame.hpp"
 #include "dpm_apg_kernel.hpp"
 #include "dpm_table_apg.hpp"
+#endif
+#if DPM_UNIT == 6
+#include "dpm_sample_frame.hpp"
+#include "dpm_zstar_kernel.hpp"
 #endif
 
 #include <tuple>
@@ -127,14 +133,14 @@ template int dpm_table_launch_blend<State, Eps>(const dpm_stage*, const dpm_buff
 #endif
 
 // The launch of a per-sample guidance stage (dpm_kernels.hip: kSampleGuidance), FLAG the unit's own.
-#if DPM_UNIT == 4 || DPM_UNIT == 5
+#if DPM_UNIT == 4 || DPM_UNIT == 5 || DPM_UNIT == 6
 template <typename TS, typename TE, unsigned FLAG>
 int dpm_launch_sample(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
   const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
   return launch_sample_typed<TS, TE>(st, b, s);  // (the one of the unit's kernel header)
 }
-template int dpm_launch_sample<State, Eps, DPM_UNIT == 4 ? DPM_F_CFG_RESCALE : DPM_F_CFG_APG>(const dpm_stage*, const dpm_buffers*,
-                                                                                             void*, void*, void*);
+template int dpm_launch_sample<State, Eps, DPM_UNIT == 4 ? DPM_F_CFG_RESCALE : DPM_UNIT == 5 ? DPM_F_CFG_APG : DPM_F_CFG_ZSTAR>(
+    const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 #endif
 
 #if DPM_UNIT == 4

@@ -156,6 +156,7 @@ class RequestPool:
         sd = s._sdtype(x)
         s._check_rescale(sd=sd)             # (a pool's requests do not pass run_plan)
         s._check_apg(sd=sd)
+        s._check_zero_star(sd=sd)
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
             raise NotImplementedError("request pool: denoise_to_zero with a half-precision state on a continuous schedule "
@@ -183,7 +184,7 @@ class RequestPool:
         if q.plan.sde:
             q.mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
         q.key = (id(q.plan), tuple(q.x.shape), q.sd, idx, stream, cfg, q.mf, bool(s.cluster_in_graph), int(s.thr_spin_limit),
-                 s._rescale_phi(), s._apg_params())
+                 s._rescale_phi(), s._apg_params(), s._zero_star())
         free = self._free.get(q.key)
         q.fr = free.pop() if free else _FastRun(s, q.plan, q.x.shape, q.sd, q.x.device, cfg, q.mf)
         if q.fr.apg_avg is not None:

@@ -47,6 +47,7 @@ def check_solver(self, order):
                                   "use algorithm_type='dpmsolver++'")
     self._check_rescale("sample_sde -- the SDE stage kernels have no rescale (a follow-up)")
     self._check_apg("sample_sde -- the SDE stage kernels have no projected guidance (a follow-up)")
+    self._check_zero_star("sample_sde -- the SDE stage kernels have no CFG-Zero* projection (a follow-up)")
     if self._thresholding:
         raise NotImplementedError("sample_sde: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernel has no noise "
                                   "epilogue")

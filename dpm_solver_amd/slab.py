@@ -292,6 +292,8 @@ class SlabPool:
         if not self._apg:
             s._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance stages take the table in a pool built "
                          "with request_pool(slots=..., apg=True) only")
+        s._check_zero_star("the slab pool (request_pool(slots=...)) -- CFG-Zero* stages have no table row kind yet (a follow-up); "
+                           "a RequestPool (no slots) takes a cfg_zero_star solver as it is")
 
     def _apg_params(self, apg):
         """the request's own (eta, norm threshold, momentum) of submit's apg=, checked as cfg_apg checks them; None: the

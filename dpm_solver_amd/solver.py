@@ -221,6 +221,28 @@ class DPM_Solver:
             raise NotImplementedError("adaptive projected guidance (cfg_apg): double-precision states (there is no double "
                                       "kernel)")
 
+    def _zero_star(self):
+        """does the wrapper ask for the CFG-Zero* projection (dpm_solver_amd.cfg_zero_star)?  False: every launch as without it"""
+        return bool(self._wrapped.zero_star) if self._wrapped is not None else False
+
+    def _check_zero_star(self, what=None, sd=None, blend=False):
+        """the combinations CFG-Zero* is not built with, as _check_rescale: `what` names a sampler or a
+        mode that has none; else the solver's other remedies, the run's corrector and state dtype; a thresholded stage is
+        refused where it is bound (_prep_stage)"""
+        if not self._zero_star():
+            return
+        if what is not None:
+            raise NotImplementedError("CFG-Zero* (cfg_zero_star): %s" % what)
+        if self._rescale_phi() or self._apg_params() is not None:
+            raise NotImplementedError("CFG-Zero* (cfg_zero_star): together with %s -- the remedies are not built together"
+                                      % ("guidance rescale (cfg_rescale)" if self._rescale_phi()
+                                         else "adaptive projected guidance (cfg_apg)"))
+        if blend:
+            raise NotImplementedError("CFG-Zero* (cfg_zero_star): a MaskBlend corrector -- its kernel has no mask-blend "
+                                      "epilogue (a follow-up)")
+        if sd is torch.float64:
+            raise NotImplementedError("CFG-Zero* (cfg_zero_star): double-precision states (there is no double kernel)")
+
     def _sdtype(self, x):
         if self._state_dtype is not None:
             return self._state_dtype
@@ -409,6 +431,12 @@ class DPM_Solver:
         if apg is not None:
             self._check_apg()
             DV._bind_apg(st, apg)
+        if self._zero_star():
+            self._check_zero_star()
+            if st.flags & L.F_THRESH:
+                raise NotImplementedError("CFG-Zero* (cfg_zero_star): correcting_x0_fn='dynamic_thresholding' -- the "
+                                          "thresholding kernels have no CFG-Zero* projection (a follow-up)")
+            DV._bind_zstar(st)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
@@ -416,11 +444,12 @@ class DPM_Solver:
         stage: prologue kernel -> user function (opaque torch) -> combination kernel."""
         self._check_rescale(sd=sd)          # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
         self._check_apg(sd=sd)
+        self._check_zero_star(sd=sd)
         e0, e1, g = outs if sd is not torch.float64 else self._cfg_pre(outs, sd)
         if self._user_x0 is not None and (st.flags & L.F_TO_X0):
             s1 = st.copy()
             s1.form = L.FORM_DENOISE
-            s1.flags = L.F_TO_X0 | (st.flags & (L.F_CFG_RESCALE | L.F_CFG_APG))
+            s1.flags = L.F_TO_X0 | (st.flags & (L.F_CFG_RESCALE | L.F_CFG_APG | L.F_CFG_ZSTAR))
             avg = ext.get("apg_avg") if ext is not None else None
             x0, _ = DV._launch_stage(s1, None, xe if xe is not None else x, e0, e1, g, None, None, sd, want_m=False,
                                   ext={"apg_avg": avg} if avg is not None else None, opts=self._opts_ptr(), coef64=coef64)
@@ -853,6 +882,8 @@ class DPM_Solver:
             if not rescale:
                 self._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built "
                                     "with request_pool(slots=..., rescale=True) only")
+            self._check_zero_star("the slab pool (request_pool(slots=...)) -- CFG-Zero* stages have no table row kind yet (a "
+                                  "follow-up); a RequestPool (no slots) takes a cfg_zero_star solver as it is")
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")

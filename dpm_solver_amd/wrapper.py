@@ -20,6 +20,9 @@ class WrappedModel:
     # adaptive projected guidance (Sadat et al. 2024; diffusers' APG guider): (eta, norm threshold, momentum), set through
     # dpm_solver_amd.cfg_apg.  None = off: every bit as without it.
     guidance_apg = None
+    # CFG-Zero* (Fan et al. 2025; diffusers' ClassifierFreeZeroStarGuidance): set through dpm_solver_amd.cfg_zero_star.
+    # False = off: every bit as without it.
+    guidance_zero_star = False
 
     def __init__(self, model, noise_schedule, model_type, model_kwargs, guidance_type, condition,
                  unconditional_condition, guidance_scale, classifier_fn, classifier_kwargs):
@@ -56,6 +59,11 @@ class WrappedModel:
         """(eta, norm threshold, momentum) of the adaptive projected guidance this wrapper asks the stage kernels for; None =
         none (never set, or no classifier-free blend)"""
         return self.guidance_apg if self.guidance_apg is not None and self.effective_guidance == "classifier-free" else None
+
+    @property
+    def zero_star(self):
+        """does this wrapper ask the stage kernels for the CFG-Zero* projection?  False: never set, or no classifier-free blend"""
+        return bool(self.guidance_zero_star) and self.effective_guidance == "classifier-free"
 
     def apg_x0(self, x, t_continuous, average=None):
         """The guided DATA prediction under adaptive projected guidance, in torch (include/dpm_hip.h, DPM_F_CFG_APG, in the
@@ -150,7 +158,8 @@ class WrappedModel:
         included, no host synchronisation (the schedule is evaluated on the device, NoiseScheduleVP.device_alpha_sigma).
         Under adaptive projected guidance (cfg_apg) the result is the noise prediction equivalent to the guided data
         prediction, (x - alpha * x0) / sigma; a direct call has no history: it is a FIRST step, with a running average of
-        zero, whatever the momentum."""
+        zero, whatever the momentum.  Under CFG-Zero* (cfg_zero_star) the unconditional RAW output is scaled by its
+        per-sample least-squares fit to the conditional one before the blend (include/dpm_hip.h, DPM_F_CFG_ZSTAR)."""
         from .utils import expand_dims
         from ._device import _require_gpu
         _require_gpu(x)
@@ -189,6 +198,20 @@ class WrappedModel:
             axes = list(range(1, dims))
             f = (e0.double().std(dim=axes, keepdim=True) / g.double().std(dim=axes, keepdim=True)).to(g.dtype)
             return to_noise(phi * (g * f) + (1. - phi) * g)
+        if eff == "classifier-free" and self.zero_star:
+            # CFG-Zero*: projection and blend on the RAW outputs, the conversion afterwards (include/dpm_hip.h, DPM_F_CFG_ZSTAR):
+            # half outputs are widened to fp32 first, as the stage kernel widens them, and nothing after that is rounded to
+            # half; the two per-sample sums in float64, their quotient rounded once to the outputs' dtype
+            if e0.dtype in (torch.float16, torch.bfloat16):
+                e0, e1 = e0.float(), e1.float()
+            axes = list(range(1, dims))
+            c64, u64 = e0.double(), e1.double()
+            s_cu = (c64 * u64).sum(dim=axes, keepdim=True)
+            s_uu = (u64 * u64).sum(dim=axes, keepdim=True)
+            a = (s_cu / (s_uu + 1e-8)).to(e0.dtype)
+            u = a * e1
+            s = float(torch.tensor(float(self.guidance_scale), dtype=torch.float32)) if e0.dtype is torch.float32 else self.guidance_scale
+            return to_noise(u + s * (e0 - u))
         if eff == "classifier-free":                              # ref :326-330
             nu, nc = to_noise(e1), to_noise(e0)
             return nu + self.guidance_scale * (nc - nu)
@@ -208,6 +231,8 @@ def cfg_rescale(model_fn, phi):
         raise ValueError("cfg_rescale: phi must be a real number in [0, 1], got %r" % (phi,))
     if phi and model_fn.guidance_apg is not None:
         raise NotImplementedError("cfg_rescale on top of cfg_apg: the two remedies are not built together")
+    if phi and model_fn.guidance_zero_star:
+        raise NotImplementedError("cfg_rescale on top of cfg_zero_star: the two remedies are not built together")
     out = copy.copy(model_fn)
     out.guidance_rescale = float(phi)
     return out
@@ -236,8 +261,31 @@ def cfg_apg(model_fn, eta=0.0, norm_threshold=0.0, momentum=0.0):
     params = (float(eta), float(norm_threshold), float(momentum))
     if params != (1.0, 0.0, 0.0) and float(model_fn.guidance_rescale) != 0.0:
         raise NotImplementedError("cfg_apg on top of cfg_rescale: the two remedies are not built together")
+    if params != (1.0, 0.0, 0.0) and model_fn.guidance_zero_star:
+        raise NotImplementedError("cfg_apg on top of cfg_zero_star: the two remedies are not built together")
     out = copy.copy(model_fn)
     out.guidance_apg = None if params == (1.0, 0.0, 0.0) else params
+    return out
+
+
+def cfg_zero_star(model_fn):
+    """(extension) A copy of the classifier-free wrapper `model_fn` with the CFG-Zero* projection (Fan et al. 2025, "CFG-Zero*:
+    Improved Classifier-Free Guidance for Flow Matching Models"; diffusers' `ClassifierFreeZeroStarGuidance`, ComfyUI's
+    `CFGZeroStar`, which applies it to noise-prediction checkpoints as well): before the blend the unconditional output is
+    scaled by its per-sample least-squares fit to the conditional one, a = <o_c, o_u> / ||o_u||^2, and the guided output is
+    a * o_u + s * (o_c - a * o_u).  It carries no parameter.  DPM_Solver runs it inside the stage kernel (DPM_F_CFG_ZSTAR), for
+    both algorithm types; at guidance scale 1 or without an unconditional condition it changes nothing.  The paper's
+    "zero-init" -- a zero velocity in the first steps -- is NOT part of it: that is defined for flow-matching velocities and
+    has no counterpart for a VP noise prediction."""
+    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
+        raise ValueError("cfg_zero_star: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
+                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
+    if float(model_fn.guidance_rescale) != 0.0:
+        raise NotImplementedError("cfg_zero_star on top of cfg_rescale: the two remedies are not built together")
+    if model_fn.guidance_apg is not None:
+        raise NotImplementedError("cfg_zero_star on top of cfg_apg: the two remedies are not built together")
+    out = copy.copy(model_fn)
+    out.guidance_zero_star = True
     return out
 
 

@@ -93,11 +93,15 @@ extern "C" {
    the table -- every qualifying DPM_F_CFG_APG request owns a row and an APG record behind the rows, a group of them is ONE
    stage_apg_kernel_table launch, one workgroup per sample; in such a call a request's running average is dpm_buffers.thr_hint
    (see "Table mode"; no entry point added, no struct changed size).
+   216 DPM_F_CFG_ZSTAR: classifier-free guidance with the CFG-Zero* projection (Fan et al. 2025; diffusers'
+   ClassifierFreeZeroStarGuidance, ComfyUI's CFGZeroStar) in ONE stage launch -- a kernel that owns a whole sample, takes the
+   per-sample least-squares fit of the unconditional output to the conditional one, scales the unconditional output by it, then
+   runs the usual blend, conversion, update and stores (see DPM_F_CFG_ZSTAR; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 215
+#define DPM_HIP_VERSION 216
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -256,6 +260,35 @@ enum {
                                sample (stage_apg_kernel); such a stage runs on its own in a multi-request launch, in every mode
                                of dpm_stage_launch_multi (in a table call it cannot be st[0] with beta != 0: bs[0].workspace is
                                the table there -- DPM_ERR_ARG) */
+
+#define DPM_F_CFG_ZSTAR 4096u /* version 216, with guidance == DPM_GUIDE_CFG only (else DPM_ERR_ARG); never set by the planner.
+                                 CFG-Zero* (Fan et al. 2025): before the blend, the unconditional output is scaled by its
+                                 per-sample least-squares fit to the conditional one.  The flag reads no field beyond cfg_scale.
+                                 For each sample of the launch, with P = n / batch elements and s = cfg_scale:
+                                   o_c, o_u = e0, e1 of the sample widened to fp32     (the RAW outputs, before any conversion --
+                                                                                        as under DPM_F_CFG_RESCALE)
+                                   S_cu = sum (double)o_c * (double)o_u     products exact in double; sums in double, any order
+                                   S_uu = sum (double)o_u * (double)o_u
+                                   a    = (float)(S_cu / (S_uu + 1e-8))     one double addition, one double division, one rounding
+                                                                            to fp32
+                                   u    = a * o_u                           fp32, one rounding per operation, no fused multiply-add
+                                   g    = u + s * (o_c - u)                 fp32, one rounding per operation, no fused multiply-add
+                                   eps  = noise prediction of the raw output g (x_start / v / score conversion), then
+                                          DPM_F_TO_X0, the update form, DPM_F_STORE_M, x_out2 and the stores as without the flag,
+                                          all fp32
+                                 g is an fp32 value whatever the network's dtype: nothing after the loads is rounded to the
+                                 network's dtype, not even for a 2-byte noise-prediction network.  S_uu == 0 gives a = 0 and
+                                 g = s * o_c: defined behaviour, not an IEEE accident.  The paper's "zero-init" (a zero velocity
+                                 in the first steps) is not part of the flag: it is defined for flow-matching velocities and has
+                                 no counterpart for a VP noise prediction.  Both algorithm types, with or without DPM_F_TO_X0.
+                                 DPM_ERR_ARG: the flag without DPM_GUIDE_CFG; P < 1 (an empty batch, n == 0, is DPM_OK and
+                                 launches nothing); an unknown form.
+                                 DPM_ERR_UNSUPPORTED (this version): together with DPM_F_CFG_RESCALE, DPM_F_CFG_APG, DPM_F_THRESH,
+                                 DPM_F_BLEND or DPM_F_NOISE (a record that sets the flag and one of the two other guidance flags
+                                 is reported by this flag's checks); DPM_FORM_UNIPC; a double state; eps_stride other than 0 or
+                                 P; device-resident coefficients.  No output byte is written in any error case.  One workgroup
+                                 per sample (stage_zstar_kernel); such a stage runs on its own in a multi-request launch, in
+                                 every mode of dpm_stage_launch_multi */
 
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
@@ -557,7 +590,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE) and DPM_F_CFG_APG (without DPM_TABLE_APG) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE), DPM_F_CFG_APG (without DPM_TABLE_APG) and DPM_F_CFG_ZSTAR (version 216; in every call) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
