@@ -103,7 +103,10 @@ class GuardedLaunch:
     data; noise_seed / per_request_stages: the launch options.  `like`: another GuardedLaunch whose pristine payloads are copied (the same case on another device)."""
 
     def __init__(self, family, st, n, sd, ed, batch=1, device="cpu", offset=0, dup=False, stride=0, blend=None, sep_xe=False,
-                 ws_bytes=None, seed=0, req=0, noise_seed=None, per_request_stages=False, like=None):
+                 ws_bytes=None, seed=0, req=0, noise_seed=None, per_request_stages=False, like=None, coef64=None):
+        # coef64: the L.StageF64 of a double-precision plan (dpm_buffers.coef64), kept alive by the case; None: the record's
+        # fp32 scalars, converted exactly
+        self.coef64 = coef64 if coef64 is not None or like is None else getattr(like, "coef64", None)
         self.family, self.st, self.n, self.batch, self.sd, self.ed, self.req = family, st, int(n), int(batch), sd, ed, req
         self.offset, self.stride, self.blend, self.device = offset, int(stride), blend, device
         self.kw = dict(batch=batch, offset=offset, dup=dup, stride=stride, blend=blend, sep_xe=sep_xe, ws_bytes=ws_bytes, seed=seed,
@@ -153,7 +156,7 @@ class GuardedLaunch:
 
     def on(self, device):
         """the same case, pristine, on `device`"""
-        return GuardedLaunch(self.family, self.st, self.n, self.sd, self.ed, device=device, like=self, **self.kw)
+        return GuardedLaunch(self.family, self.st, self.n, self.sd, self.ed, device=device, like=self, coef64=self.coef64, **self.kw)
 
     def buffers(self):
         b = L.Buffers()
@@ -166,6 +169,8 @@ class GuardedLaunch:
         if self.blend is not None:
             b.mask_period = self.blend[0]
         b.opts = C.pointer(self.opts)
+        if self.coef64 is not None:
+            b.coef64 = C.pointer(self.coef64)
         return b
 
     # -------------------------------------------------------------------------------------------
