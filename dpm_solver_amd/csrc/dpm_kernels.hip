@@ -267,7 +267,7 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   // stage keeps stage_kernel_noise (the fused noise kernels serve dpm_stage_launch_multi).
   if (!dyn && !(st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE))) {
     const int big = tuning_for(bb.opts).big_tiles;
-    if (big > 0 && (bb.n / EPT + 255) / 256 >= big) {
+    if (lone_takes_fused_shape(bb.n, big)) {
       const int rc = launch_fused(*p, st, &bb, 1, stream, ev_start, ev_stop);
       if (rc != MULTI_NOT_BUILT) return rc;
     }
@@ -660,9 +660,8 @@ extern "C" int dpm_add_noise_launch(const dpm_schedule* s, const float* t_host, 
     return DPM_OK;
   }
   const DeviceInfo& di = device_info();
-  int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)(di.n_cu > 0 ? di.n_cu : 256) * 16;
-  if (blocks > cap) blocks = cap;
+  const int n_cu = di.n_cu > 0 ? di.n_cu : 256;
+  const int64_t blocks = aux_grid_blocks(n, n_cu, false);
   const bool v2 = n % EPT == 0;
   const int rc = with_elem_type(dtype, "add_noise", [&](auto t) {
     using T = decltype(t);
@@ -676,8 +675,7 @@ extern "C" int dpm_add_noise_launch(const dpm_schedule* s, const float* t_host, 
       T* op = (T*)out + off;
       const size_t al = sizeof(T) * EPT;
       if (v2 && aligned(xp, al) && aligned(np_, al) && aligned(op, al)) {
-        int64_t bl = (n / EPT + 255) / 256;
-        if (bl > cap) bl = cap;
+        const int64_t bl = aux_grid_blocks(n, n_cu, true);
         hipLaunchKernelGGL((add_noise_kernel<T, true>), dim3((unsigned)bl), dim3(256), 0, st, xp, np_, op, n, a, sg);
       } else {
         hipLaunchKernelGGL((add_noise_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, st, xp, np_, op, n, a, sg);
@@ -694,9 +692,7 @@ extern "C" int dpm_blend_launch(const void* x, const void* mask, const void* a, 
   if (dtype == DPM_DTYPE_F64) return dpm_blend_f64(x, mask, a, b, (double)alpha, (double)sigma, out, n, mask_period, stream);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const DeviceInfo& di = device_info();
-  int64_t blocks = (n + 255) / 256;
-  const int64_t cap = (int64_t)(di.n_cu > 0 ? di.n_cu : 256) * 16;
-  if (blocks > cap) blocks = cap;
+  const int64_t blocks = aux_grid_blocks(n, di.n_cu > 0 ? di.n_cu : 256, false);
   KExt ext;
   std::memset(&ext, 0, sizeof ext);
   ext.mask_period = mask_period;

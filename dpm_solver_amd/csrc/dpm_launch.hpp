@@ -1,8 +1,10 @@
 // dpm_launch.hpp -- launch plumbing of the stage kernels: device info, cluster shape, tuning, variant dispatch,
 // the fused multi-request launcher, the catch-all kernel handles (part of dpm_device.hpp; include that)
 #pragma once
+#include "dpm_grid_plan.hpp"
 
 namespace {
+static_assert(GRID_GROUP_ELEMS == EPT && GRID_MAX_THREADS == STAGE_MAX_THREADS, "dpm_grid_plan.hpp restates the kernels' constants");
 
 // ------------------------------------------------------------------------------------------------
 // launch plumbing
@@ -314,7 +316,7 @@ bool ext_vec_ok(const Operands<TS, TE>& op, const dpm_buffers* b) {
 }
 
 // grid of the one-element-per-lane catch-all kernels (256 threads per workgroup, grid-stride loop)
-inline dim3 scalar_grid(int64_t n, int n_cu) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)n_cu * 16)); }
+inline dim3 scalar_grid(int64_t n, int n_cu) { return dim3((unsigned)scalar_grid_blocks(n, n_cu)); }
 
 struct Shape {
   dim3 grid, block;
@@ -326,13 +328,8 @@ struct Shape {
 // CFG + duplicate store 6.87-6.98 us against 7.00-7.02, the plain fp16 kernel 4.81-4.86 against 4.66-4.84;
 // profiles/r04_block_threads.md.)
 inline Shape stream_grid(int64_t n, int u, int n_cu, const Tuning& tn) {
-  const int64_t iters = ((n / EPT + 255) / 256 + u - 1) / u;
-  int bt = 256;
-  if (tn.block_threads > 0) bt = tn.block_threads;
-  else if (iters >= 4 * (int64_t)n_cu) bt = STAGE_MAX_THREADS;
-  const int64_t per = bt / 256;
-  const int64_t blocks = std::min((iters + per - 1) / per, std::max<int64_t>(1, (int64_t)n_cu * tn.blocks_per_cu / per));
-  return Shape{dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3((unsigned)bt)};
+  const StreamGridPlan g = stream_grid_plan(n, u, n_cu, tn.blocks_per_cu, tn.block_threads);
+  return Shape{dim3((unsigned)g.blocks), dim3((unsigned)g.threads)};
 }
 
 // ---- a thresholded stage (stage_thresh_kernel): the plan (thr_launch_plan, dpm_thresh_plan.hpp: cluster shape, select
@@ -553,7 +550,7 @@ int launch_stream(const dpm_stage* st, const dpm_buffers* b, const LaunchCtx& st
     const Tuning tn = tuning_for(b->opts);
     const bool noise = SPEC_BUILT && !stream.dyn && !tn.force_generic && x0_prologue_ok(*st);
     const int spec = noise ? SPEC_NOISE_X0 : SPEC_GENERIC;
-    const bool big = (b->n / EPT + 255) / 256 >= 4 * (int64_t)n_cu;  // two tiles per iteration only when there is work for it
+    const bool big = stream_big(b->n, n_cu);  // two tiles per iteration only when there is work for it
 #define DPM_LAUNCH(SPEC_, U_, NT_, EXT_)                                                                               \
   do {                                                                                                                 \
     const Shape sh_ = stream_grid(b->n, U_, n_cu, tn);                                                                 \

@@ -100,10 +100,11 @@ class GuardedLaunch:
     elements every payload sits past its 16-byte boundary; dup: name x_out2 (duplicate store, or the corrected state with
     DPM_F_STORE_XC); stride: eps_stride in elements (0 = dense); blend = (mask_period, with blend_b); sep_xe: a separate
     evaluation state; ws_bytes: thresholding workspace (None: no workspace pointer); seed: of the
-    data; noise_seed / per_request_stages: the launch options.  `like`: another GuardedLaunch whose pristine payloads are copied (the same case on another device)."""
+    data; noise_seed / per_request_stages: the launch options; resident: dpm_buffers.inputs_resident (the previous launch wrote
+    the inputs).  `like`: another GuardedLaunch whose pristine payloads are copied (the same case on another device)."""
 
     def __init__(self, family, st, n, sd, ed, batch=1, device="cpu", offset=0, dup=False, stride=0, blend=None, sep_xe=False,
-                 ws_bytes=None, seed=0, req=0, noise_seed=None, per_request_stages=False, like=None, coef64=None):
+                 ws_bytes=None, seed=0, req=0, noise_seed=None, per_request_stages=False, like=None, coef64=None, resident=False):
         # coef64: the L.StageF64 of a double-precision plan (dpm_buffers.coef64), kept alive by the case; None: the record's
         # fp32 scalars, converted exactly
         self.coef64 = coef64 if coef64 is not None or like is None else getattr(like, "coef64", None)
@@ -111,6 +112,7 @@ class GuardedLaunch:
         self.offset, self.stride, self.blend, self.device = offset, int(stride), blend, device
         self.kw = dict(batch=batch, offset=offset, dup=dup, stride=stride, blend=blend, sep_xe=sep_xe, ws_bytes=ws_bytes, seed=seed,
                        req=req, noise_seed=noise_seed, per_request_stages=per_request_stages)
+        self.resident = bool(resident or getattr(like, "resident", False))   # dpm_buffers.inputs_resident
         per = self.n // self.batch
         cfg = st.guidance == L.GUIDE["classifier-free"]
         unipc = st.form == L.FORM_UNIPC
@@ -156,7 +158,8 @@ class GuardedLaunch:
 
     def on(self, device):
         """the same case, pristine, on `device`"""
-        return GuardedLaunch(self.family, self.st, self.n, self.sd, self.ed, device=device, like=self, coef64=self.coef64, **self.kw)
+        return GuardedLaunch(self.family, self.st, self.n, self.sd, self.ed, device=device, like=self, coef64=self.coef64,
+                             resident=self.resident, **self.kw)
 
     def buffers(self):
         b = L.Buffers()
@@ -169,6 +172,8 @@ class GuardedLaunch:
         if self.blend is not None:
             b.mask_period = self.blend[0]
         b.opts = C.pointer(self.opts)
+        if self.resident:
+            b.inputs_resident = 1
         if self.coef64 is not None:
             b.coef64 = C.pointer(self.coef64)
         return b
