@@ -136,7 +136,7 @@ def _cfg_fields(scale, phi, sigma_e, flags):
     (scalars or numpy arrays, one entry per record; `sigma_e`, `flags`: the record's own): (cfg_scale, cg_scale, flags).
     cfg_scale is the scale as fp32 and, without rescale, cg_scale its fp32 product with sigma_e (the planner: a field no
     classifier-free kernel reads); with phi != 0 the record carries DPM_F_CFG_RESCALE and phi in `cg_scale`.  The one statement
-    of that conversion: _bind_rescale and the slab pool's per-request guidance both go through it."""
+    of that conversion: remedies._bind_rescale and the slab pool's per-request guidance both go through it."""
     cs = np.asarray(scale, dtype=np.float64).astype(np.float32)
     ph = np.asarray(phi, dtype=np.float64).astype(np.float32)
     fl = np.asarray(flags, dtype=np.uint32)
@@ -145,22 +145,13 @@ def _cfg_fields(scale, phi, sigma_e, flags):
     return cs, cg, np.where(on, fl | np.uint32(L.F_CFG_RESCALE), fl & ~np.uint32(L.F_CFG_RESCALE))
 
 
-def _bind_rescale(st, phi):
-    """Guidance rescale (dpm_solver_amd.cfg_rescale) in a stage record: a classifier-free stage carries DPM_F_CFG_RESCALE and phi
-    in `cg_scale` -- a field the planner writes and no classifier-free kernel reads.  phi = 0 leaves the record as it is."""
-    if phi and st.guidance == L.GUIDE["classifier-free"]:
-        _, cg, fl = _cfg_fields(st.cfg_scale, phi, st.sigma_e, st.flags)
-        st.cg_scale, st.flags = float(cg), int(fl)
-    return st
-
-
 def _apg_fields(eta, r, beta, plain, flags):
     """The fields of a classifier-free stage record that adaptive projected guidance takes, for a wrapper of
     cfg_apg(fn, eta, r, beta) (scalars or numpy arrays, one entry per record): (cg_scale, thr_ratio, thr_max, flags).  The
     record carries DPM_F_CFG_APG, eta in `cg_scale`, the norm threshold in `thr_ratio` and the momentum in `thr_max`, each as
     fp32.  (1, 0, 0) is classifier-free guidance itself, as in cfg_apg: no flag, and the three fields are `plain`'s -- (cg_scale,
     thr_ratio, thr_max) of the record without the flag, as the planner writes them; `flags`: the record's own.  The one
-    statement of that conversion: _bind_apg and the slab pool's per-request parameters both go through it."""
+    statement of that conversion: remedies._bind_apg and the slab pool's per-request parameters both go through it."""
     e = np.asarray(eta, dtype=np.float64).astype(np.float32)
     rr = np.asarray(r, dtype=np.float64).astype(np.float32)
     bt = np.asarray(beta, dtype=np.float64).astype(np.float32)
@@ -168,25 +159,6 @@ def _apg_fields(eta, r, beta, plain, flags):
     on = ~((e == 1) & (rr == 0) & (bt == 0))
     cg, ratio, mx = (np.where(on, v, np.asarray(p, dtype=np.float32)) for v, p in zip((e, rr, bt), plain))
     return cg, ratio, mx, np.where(on, fl | np.uint32(L.F_CFG_APG), fl & ~np.uint32(L.F_CFG_APG))
-
-
-def _bind_apg(st, apg):
-    """Adaptive projected guidance (dpm_solver_amd.cfg_apg) in a stage record: a classifier-free stage carries DPM_F_CFG_APG, eta
-    in `cg_scale`, the norm threshold in `thr_ratio` and the momentum in `thr_max` -- fields nothing else reads under the flag.
-    apg = None leaves the record as it is.  (The running average travels in dpm_buffers.workspace, in a DPM_TABLE_APG call in
-    dpm_buffers.thr_hint: the caller binds it.)"""
-    if apg is not None and st.guidance == L.GUIDE["classifier-free"]:
-        cg, ratio, mx, fl = _apg_fields(apg[0], apg[1], apg[2], (st.cg_scale, st.thr_ratio, st.thr_max), st.flags)
-        st.cg_scale, st.thr_ratio, st.thr_max, st.flags = float(cg), float(ratio), float(mx), int(fl)
-    return st
-
-
-def _bind_zstar(st):
-    """CFG-Zero* (dpm_solver_amd.cfg_zero_star) in a stage record: a classifier-free stage carries DPM_F_CFG_ZSTAR and nothing
-    else -- the flag reads cfg_scale alone.  Every other record stays as it is."""
-    if st.guidance == L.GUIDE["classifier-free"]:
-        st.flags |= L.F_CFG_ZSTAR
-    return st
 
 
 def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=None, opts=None, coef64=None):

@@ -224,12 +224,8 @@ def runs_on_device(self, x):
 def solve(self, x, order, t_T, t_0, h_init=0.05, atol=0.0078, rtol=0.05, theta=0.9, t_err=1e-5,
                         solver_type='dpmsolver'):
     DV._require_gpu(x)
-    self._check_rescale("method='adaptive' -- its stages take device-resident coefficients, which the rescale kernel does not "
-                        "read (a follow-up)")
-    self._check_apg("method='adaptive' -- its stages take device-resident coefficients, which the projected-guidance kernel "
-                    "does not read (a follow-up)")
-    self._check_zero_star("method='adaptive' -- its stages take device-resident coefficients, which the CFG-Zero* kernel does "
-                          "not read (a follow-up)")
+    self._check_remedies("method='adaptive' -- its stages take device-resident coefficients, which the {stages} kernel does "
+                         "not read (a follow-up)")
     if order not in (2, 3):
         raise ValueError("For adaptive step size solver, order must be 2 or 3, got {}".format(order))
     if solver_type not in ['dpmsolver', 'taylor']:

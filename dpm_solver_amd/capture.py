@@ -57,7 +57,8 @@ def auto_captured(self, x, kw, return_intermediate):
     if (return_intermediate or self.correcting_xt_fn is not None or self._user_x0 is not None or not x.is_cuda or x.dim() == 0
             or x.numel() == 0 or (kw["method"] == "adaptive" and not self._adaptive_runs_on_device(x))):
         return None                           # Python callbacks / a host-side adaptive loop: never captured
-    if self._apg_params() is not None and self._apg_params()[2] != 0.0:
+    apg = self._remedy_setting("cfg_apg")
+    if apg is not None and apg[2] != 0.0:
         return None                           # a running average carried from stage to stage: capture() refuses it, stays eager
     dev = x.device
     # everything a replay bakes in: the call's arguments, the tensor's geometry, the stream -- and every solver / wrapper
@@ -66,8 +67,7 @@ def auto_captured(self, x, kw, return_intermediate):
     w = self._wrapped
     key = (tuple(sorted((k, (float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)) for k, v in kw.items())),
            tuple(x.shape), x.dtype, x.stride(), dev.index, torch.cuda.current_stream(dev).cuda_stream,
-           bool(self.cluster_in_graph), int(self.thr_spin_limit), self._model_codes(), self._rescale_phi(), self._apg_params(),
-           self._zero_star(),
+           bool(self.cluster_in_graph), int(self.thr_spin_limit), self._model_codes(), self._remedy_key(),
            self._thresholding,
            float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val), self.algorithm_type, self._state_dtype,
            self._sdtype(x), bool(self.adaptive_on_device), int(self.adaptive_lookahead), self.adaptive_max_iterations,

@@ -47,7 +47,7 @@ def run_plan_group(self, plan, xs, sd, cfg):
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._rescale_phi(), self._apg_params(), self._zero_star())
+           self._remedy_key())
     grp = None if capturing else self._fast_groups.get(key)
     if grp is None:
         runs = [_FastRun(self, plan, shape, sd, device, cfg, mf) for _ in range(R)]
@@ -146,7 +146,7 @@ def run_plan_fast(self, plan, x, sd, cfg):
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._rescale_phi(), self._apg_params(), self._zero_star())
+           self._remedy_key())
     fr = None if capturing else self._fast.get(key)      # a captured graph bakes its buffers in: give it its own
     if fr is None:
         fr = _FastRun(self, plan, x.shape, sd, device, cfg, mf)
@@ -203,9 +203,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     device = x.device
     sd = self._sdtype(x)
     cfg = self._wrapped is not None and self._wrapped.effective_guidance == "classifier-free"
-    self._check_rescale(sd=sd, blend=isinstance(cxt, MaskBlend))    # the one check of a run (its loops do not repeat it)
-    self._check_apg(sd=sd, blend=isinstance(cxt, MaskBlend))
-    self._check_zero_star(sd=sd, blend=isinstance(cxt, MaskBlend))
+    self._check_remedies(sd=sd, blend=isinstance(cxt, MaskBlend))   # the one check of a run (its loops do not repeat it)
     # denoise_to_zero evaluates the data prediction at a (1,)-shaped time (ref :1236: `torch.ones((1,)) * t_0`): on a
     # continuous schedule its alpha_t / sigma_t are then dimensioned fp32 tensors and the RESULT of a half-precision run
     # is fp32 (on a discrete schedule every run is fp32 anyway).  That last stage runs in fp32 in the general loop below.

@@ -154,9 +154,7 @@ class RequestPool:
         """a checked request with its plan joins the pool (seed: an SDE request's); returns its handle"""
         s = self._s
         sd = s._sdtype(x)
-        s._check_rescale(sd=sd)             # (a pool's requests do not pass run_plan)
-        s._check_apg(sd=sd)
-        s._check_zero_star(sd=sd)
+        s._check_remedies(sd=sd)            # (a pool's requests do not pass run_plan)
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
             raise NotImplementedError("request pool: denoise_to_zero with a half-precision state on a continuous schedule "
@@ -184,7 +182,7 @@ class RequestPool:
         if q.plan.sde:
             q.mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
         q.key = (id(q.plan), tuple(q.x.shape), q.sd, idx, stream, cfg, q.mf, bool(s.cluster_in_graph), int(s.thr_spin_limit),
-                 s._rescale_phi(), s._apg_params(), s._zero_star())
+                 s._remedy_key())
         free = self._free.get(q.key)
         q.fr = free.pop() if free else _FastRun(s, q.plan, q.x.shape, q.sd, q.x.device, cfg, q.mf)
         if q.fr.apg_avg is not None:

@@ -45,9 +45,7 @@ def check_solver(self, order):
     if self.algorithm_type != "dpmsolver++":
         raise NotImplementedError("sample_sde: algorithm_type='dpmsolver' (the noise-prediction SDE variant) is not built; "
                                   "use algorithm_type='dpmsolver++'")
-    self._check_rescale("sample_sde -- the SDE stage kernels have no rescale (a follow-up)")
-    self._check_apg("sample_sde -- the SDE stage kernels have no projected guidance (a follow-up)")
-    self._check_zero_star("sample_sde -- the SDE stage kernels have no CFG-Zero* projection (a follow-up)")
+    self._check_remedies("sample_sde -- the SDE stage kernels have no {noun} (a follow-up)")
     if self._thresholding:
         raise NotImplementedError("sample_sde: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernel has no noise "
                                   "epilogue")

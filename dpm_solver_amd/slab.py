@@ -138,9 +138,11 @@ import torch
 
 from . import _device as DV
 from . import _lib as L
+from . import remedies as _rem
 from . import sde as _sde
 from . import unipc as _unipc
 from .correctors import MaskBlend
+from .wrapper import apg_params
 
 _RING = 4
 _STAGE = np.dtype(L.Stage)
@@ -286,14 +288,7 @@ class SlabPool:
                                       "sample()")
         if return_intermediate:
             raise NotImplementedError("slab pool: return_intermediate is not supported; sample it with sample()")
-        if not self._rsc:
-            s._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built with "
-                             "request_pool(slots=..., rescale=True) only")
-        if not self._apg:
-            s._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance stages take the table in a pool built "
-                         "with request_pool(slots=..., apg=True) only")
-        s._check_zero_star("the slab pool (request_pool(slots=...)) -- CFG-Zero* stages have no table row kind yet (a follow-up); "
-                           "a RequestPool (no slots) takes a cfg_zero_star solver as it is")
+        _rem.check_slab(s, {"rescale": self._rsc, "apg": self._apg})
 
     def _apg_params(self, apg):
         """the request's own (eta, norm threshold, momentum) of submit's apg=, checked as cfg_apg checks them; None: the
@@ -306,20 +301,11 @@ class SlabPool:
                              "guidance scale other than 1)")
         if not isinstance(apg, (tuple, list)) or len(apg) != 3:
             raise ValueError("slab pool: apg= takes (eta, norm_threshold, momentum), got %r" % (apg,))
-        eta, r, beta = apg
-        for name, v in (("eta", eta), ("norm_threshold", r), ("momentum", beta)):
-            if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
-                raise ValueError("cfg_apg: %s must be a real number, got %r" % (name, v))
-        if not 0.0 <= float(eta) <= 1.0:
-            raise ValueError("cfg_apg: eta must be in [0, 1], got %r" % (eta,))
-        if not (0.0 <= float(r) < float("inf")):
-            raise ValueError("cfg_apg: norm_threshold must be a finite number >= 0 (0 = off), got %r" % (r,))
-        if not -1.0 < float(beta) < 1.0:
-            raise ValueError("cfg_apg: momentum must be in (-1, 1), got %r" % (beta,))
+        apg = apg_params(*apg)
         if not self._apg:
             raise NotImplementedError("slab pool: apg= -- projected-guidance stages take the table in a pool built with "
                                       "request_pool(slots=..., apg=True) only")
-        return float(eta), float(r), float(beta)
+        return apg
 
     def _guidance(self, scale, phi):
         """the request's own (guidance scale, phi) of submit's guidance_scale= / guidance_rescale=, checked; None: the wrapper's"""
@@ -341,7 +327,7 @@ class SlabPool:
             raise NotImplementedError("slab pool: guidance_rescale= -- rescale stages take the table in a pool built with "
                                       "request_pool(slots=..., rescale=True) only")
         return (float(w.guidance_scale) if scale is None else float(scale),
-                float(self._s._rescale_phi()) if phi is None else float(phi))
+                float(self._s._remedy_setting("cfg_rescale") or 0.0) if phi is None else float(phi))
 
     def _check_state(self, x):
         """the refusals that depend on x's dtype, then the device requirement and the pool's own checks"""
@@ -707,7 +693,7 @@ class SlabPool:
 
     def _apg_admit(self, q, ra):
         """the request's own parameters, or the wrapper's ((1, 0, 0): it has none)"""
-        own = q.apg if q.apg is not None else self._s._apg_params()
+        own = q.apg if q.apg is not None else self._s._remedy_setting("cfg_apg")
         self._aon[ra] = q.apg is not None
         self._aeta[ra], self._ar[ra], self._abeta[ra] = own if own is not None else (1.0, 0.0, 0.0)
 

@@ -20,6 +20,8 @@ The class and its reference-named methods live here; what they run on is split b
   adaptive.py     the adaptive solver: device-side controller, host loop, the predicate that chooses
   capture.py      hipGraph capture (`GraphedSample`) and auto_capture
   pool.py         `RequestPool`: continuous batching, one fused launch per tick for requests at any stage
+  remedies.py     the classifier-free remedies (cfg_rescale, cfg_apg, cfg_zero_star) as one table: a kind's setting, binder,
+                  refusals and pool switch are a row; `_remedies`, `_remedy_key` and `_check_remedies` read it
 
 `ref :NNN` = line in the reference's dpm_solver_pytorch.py.
 """
@@ -39,6 +41,7 @@ from . import capture as _capture
 from . import loops as _loops
 from . import plan_cache as _plan_cache
 from . import pool as _pool
+from . import remedies as _rem
 from . import slab as _slab
 from . import sde as _sde
 from . import unipc as _unipc
@@ -165,83 +168,19 @@ class DPM_Solver:
             return L.MODEL[w.model_type], L.GUIDE[w.effective_guidance], float(w.guidance_scale)
         return L.MODEL["noise"], L.GUIDE["uncond"], 1.0
 
-    def _rescale_phi(self):
-        """phi of the wrapper's guidance rescale (dpm_solver_amd.cfg_rescale); 0.0: none, every launch as without it"""
-        return self._wrapped.rescale_phi if self._wrapped is not None else 0.0
-
-    def _check_rescale(self, what=None, sd=None, blend=False):
-        """the combinations guidance rescale is not built with: `what` names a sampler that has none; else
-        the run's corrector and state dtype.  Called where a run starts (run_plan, the pool's _admit, the samplers' own
-        checks) and by _run_stage, whose state dtype may have been promoted by the first evaluation; a thresholded stage is
-        refused where it is bound (_prep_stage)."""
-        if not self._rescale_phi():
-            return
-        if what is not None:
-            raise NotImplementedError("guidance rescale (cfg_rescale): %s" % what)
-        if blend:
-            raise NotImplementedError("guidance rescale (cfg_rescale): a MaskBlend corrector -- the rescale kernel has no "
-                                      "mask-blend epilogue (a follow-up)")
-        if sd is torch.float64:
-            raise NotImplementedError("guidance rescale (cfg_rescale): double-precision states (there is no double rescale "
-                                      "kernel)")
-
-    def _apg_params(self):
-        """(eta, norm threshold, momentum) of the wrapper's adaptive projected guidance (dpm_solver_amd.cfg_apg); None: none,
-        every launch as without it"""
-        return self._wrapped.apg if self._wrapped is not None else None
+    # the classifier-free remedies (cfg_rescale, cfg_apg, cfg_zero_star): one table, one face (dpm_solver_amd/remedies.py)
+    _remedies = _rem.active
+    _remedy_setting = _rem.setting
+    _remedy_key = _rem.key
+    _check_remedies = _rem.check
 
     def _apg_average(self, shape, device):
         """a zeroed running average for one run under adaptive projected guidance with a momentum (fp32, the state's shape);
         None where the run carries none"""
-        apg = self._apg_params()
+        apg = self._remedy_setting("cfg_apg")
         if apg is None or apg[2] == 0.0:
             return None
         return torch.zeros(tuple(shape), dtype=torch.float32, device=device)
-
-    def _check_apg(self, what=None, sd=None, blend=False):
-        """the combinations adaptive projected guidance is not built with, as _check_rescale: `what` names a
-        sampler or a mode that has none; else the solver's algorithm and correctors, the run's corrector and state dtype"""
-        if self._apg_params() is None:
-            return
-        if what is not None:
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): %s" % what)
-        if self._rescale_phi():
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): together with guidance rescale (cfg_rescale) -- "
-                                      "the two remedies are not built together")
-        if self.algorithm_type != "dpmsolver++":
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): algorithm_type='dpmsolver' -- it is defined on "
-                                      "the data prediction (algorithm_type='dpmsolver++')")
-        if self._thresholding:
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): correcting_x0_fn='dynamic_thresholding' -- the "
-                                      "thresholding kernels have no projected guidance (a follow-up)")
-        if blend:
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): a MaskBlend corrector -- its kernel has no "
-                                      "mask-blend epilogue (a follow-up)")
-        if sd is torch.float64:
-            raise NotImplementedError("adaptive projected guidance (cfg_apg): double-precision states (there is no double "
-                                      "kernel)")
-
-    def _zero_star(self):
-        """does the wrapper ask for the CFG-Zero* projection (dpm_solver_amd.cfg_zero_star)?  False: every launch as without it"""
-        return bool(self._wrapped.zero_star) if self._wrapped is not None else False
-
-    def _check_zero_star(self, what=None, sd=None, blend=False):
-        """the combinations CFG-Zero* is not built with, as _check_rescale: `what` names a sampler or a
-        mode that has none; else the solver's other remedies, the run's corrector and state dtype; a thresholded stage is
-        refused where it is bound (_prep_stage)"""
-        if not self._zero_star():
-            return
-        if what is not None:
-            raise NotImplementedError("CFG-Zero* (cfg_zero_star): %s" % what)
-        if self._rescale_phi() or self._apg_params() is not None:
-            raise NotImplementedError("CFG-Zero* (cfg_zero_star): together with %s -- the remedies are not built together"
-                                      % ("guidance rescale (cfg_rescale)" if self._rescale_phi()
-                                         else "adaptive projected guidance (cfg_apg)"))
-        if blend:
-            raise NotImplementedError("CFG-Zero* (cfg_zero_star): a MaskBlend corrector -- its kernel has no mask-blend "
-                                      "epilogue (a follow-up)")
-        if sd is torch.float64:
-            raise NotImplementedError("CFG-Zero* (cfg_zero_star): double-precision states (there is no double kernel)")
 
     def _sdtype(self, x):
         if self._state_dtype is not None:
@@ -415,41 +354,29 @@ class DPM_Solver:
         return out
 
     def _prep_stage(self, st):
-        """stage flags that depend on this solver's correctors"""
+        """stage flags and fields that depend on this solver's correctors and on its wrapper's remedy: per active kind its
+        check, its refusal of a thresholded stage, its bind"""
         if st.flags & L.F_TO_X0:
             if self._thresholding:
                 st.flags |= L.F_THRESH
                 st.thr_ratio = float(self.dynamic_thresholding_ratio)
                 st.thr_max = float(self.thresholding_max_val)
-        phi = self._rescale_phi()
-        if phi:
+        for r, v in self._remedies():
+            self._check_remedies(only=r.name)
             if st.flags & L.F_THRESH:
-                raise NotImplementedError("guidance rescale (cfg_rescale): correcting_x0_fn='dynamic_thresholding' -- the "
-                                          "thresholding kernels have no rescale (a follow-up)")
-            DV._bind_rescale(st, phi)
-        apg = self._apg_params()
-        if apg is not None:
-            self._check_apg()
-            DV._bind_apg(st, apg)
-        if self._zero_star():
-            self._check_zero_star()
-            if st.flags & L.F_THRESH:
-                raise NotImplementedError("CFG-Zero* (cfg_zero_star): correcting_x0_fn='dynamic_thresholding' -- the "
-                                          "thresholding kernels have no CFG-Zero* projection (a follow-up)")
-            DV._bind_zstar(st)
+                raise _rem.thresholded(r)
+            r.bind(st, v)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
         """outs = (e0, e1, g) fresh network outputs.  Handles a *callable* correcting_x0_fn by splitting the
         stage: prologue kernel -> user function (opaque torch) -> combination kernel."""
-        self._check_rescale(sd=sd)          # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
-        self._check_apg(sd=sd)
-        self._check_zero_star(sd=sd)
+        self._check_remedies(sd=sd)         # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
         e0, e1, g = outs if sd is not torch.float64 else self._cfg_pre(outs, sd)
         if self._user_x0 is not None and (st.flags & L.F_TO_X0):
             s1 = st.copy()
             s1.form = L.FORM_DENOISE
-            s1.flags = L.F_TO_X0 | (st.flags & (L.F_CFG_RESCALE | L.F_CFG_APG | L.F_CFG_ZSTAR))
+            s1.flags = L.F_TO_X0 | (st.flags & _rem.F_CFG_REMEDIES)
             avg = ext.get("apg_avg") if ext is not None else None
             x0, _ = DV._launch_stage(s1, None, xe if xe is not None else x, e0, e1, g, None, None, sd, want_m=False,
                                   ext={"apg_avg": avg} if avg is not None else None, opts=self._opts_ptr(), coef64=coef64)
@@ -839,51 +766,13 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
-        if rescale:
-            if slots is None:
-                raise ValueError("request_pool: rescale=True belongs to a slab pool (slots=...); a RequestPool takes a "
-                                 "cfg_rescale solver as it is")
-            for on, name, why in ((sde, "sde", "the SDE stage kernels have no rescale"),
-                                  (thresholding, "thresholding", "the thresholding kernels have no rescale"),
-                                  (inpaint, "inpaint", "the rescale kernel has no mask-blend epilogue")):
-                if on:
-                    raise NotImplementedError("request_pool: rescale=True with %s=True -- %s (a follow-up)" % (name, why))
-            if self._wrapped is None or self._wrapped.effective_guidance != "classifier-free":
-                raise ValueError("request_pool: rescale=True needs a classifier-free wrapper (an unconditional condition and a "
-                                 "guidance scale other than 1): guidance rescale rescales the guided output")
-        if apg:
-            if slots is None:
-                raise ValueError("request_pool: apg=True belongs to a slab pool (slots=...); a RequestPool takes a "
-                                 "cfg_apg solver as it is")
-            for on, name, why in ((rescale, "rescale", "the APG kernel has no guidance rescale"),
-                                  (sde, "sde", "the APG kernel has no noise epilogue"),
-                                  (thresholding, "thresholding", "the APG kernel has no thresholding"),
-                                  (inpaint, "inpaint", "the APG kernel has no mask-blend epilogue")):
-                if on:
-                    raise NotImplementedError("request_pool: apg=True with %s=True -- %s (a follow-up)" % (name, why))
-            if self._wrapped is None or self._wrapped.effective_guidance != "classifier-free":
-                raise ValueError("request_pool: apg=True needs a classifier-free wrapper (an unconditional condition and a "
-                                 "guidance scale other than 1): adaptive projected guidance projects the guidance direction")
-            if self.algorithm_type != "dpmsolver++":
-                raise NotImplementedError("request_pool: apg=True with algorithm_type='dpmsolver' -- adaptive projected guidance "
-                                          "is defined on the data prediction (algorithm_type='dpmsolver++')")
-            if self._thresholding or self._rescale_phi():
-                raise NotImplementedError("request_pool: apg=True on a solver with %s -- the APG kernel has none of those "
-                                          "epilogues (a follow-up)"
-                                          % ("correcting_x0_fn='dynamic_thresholding'" if self._thresholding else "cfg_rescale"))
+        on = dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg)
+        _rem.check_switches(self, slots, on)
         if thresholding and not self._thresholding:
             raise ValueError("request_pool: thresholding=True on a solver built without "
                              "correcting_x0_fn='dynamic_thresholding'")
         if slots is not None:
-            if not apg:
-                self._check_apg("the slab pool (request_pool(slots=...)) -- projected-guidance stages take the table in a pool "
-                                "built with request_pool(slots=..., apg=True) only; a RequestPool (no slots) takes a cfg_apg "
-                                "solver as it is")
-            if not rescale:
-                self._check_rescale("the slab pool (request_pool(slots=...)) -- rescale stages take the table in a pool built "
-                                    "with request_pool(slots=..., rescale=True) only")
-            self._check_zero_star("the slab pool (request_pool(slots=...)) -- CFG-Zero* stages have no table row kind yet (a "
-                                  "follow-up); a RequestPool (no slots) takes a cfg_zero_star solver as it is")
+            _rem.check_slab(self, on)
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
@@ -903,10 +792,10 @@ class DPM_Solver:
         synchronisation, no data-dependent control flow), shapes are frozen, and the returned tensors are static
         buffers that the next replay overwrites.  method='adaptive' is captured with its device-side controller: exactly
         `adaptive_max_iterations` (default 64) iterations are recorded, those after t_end is reached do nothing."""
-        apg = self._apg_params()
+        apg = self._remedy_setting("cfg_apg")
         if apg is not None and apg[2] != 0.0:
-            self._check_apg("capture with a momentum -- a replayed graph would carry the running average of one run into the "
-                            "next; capture with momentum=0, or sample() eagerly")
+            self._check_remedies("capture with a momentum -- a replayed graph would carry the running average of one run into "
+                                 "the next; capture with momentum=0, or sample() eagerly", only="cfg_apg")
         if sample_kwargs.get("method", "multistep") == "adaptive" and not self._adaptive_runs_on_device(x):
             raise NotImplementedError("the host-side adaptive control loop synchronises every iteration; it cannot be "
                                       "captured into a graph (the device-side controller can: adaptive_on_device = True, no "

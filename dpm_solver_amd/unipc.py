@@ -24,9 +24,7 @@ def check_solver(self, order, variant):
     if self.algorithm_type != "dpmsolver++":
         raise NotImplementedError("sample_unipc: algorithm_type='dpmsolver' (the noise-prediction UniPC) is not built; "
                                   "use algorithm_type='dpmsolver++'")
-    self._check_rescale("sample_unipc -- the UniPC stage kernels have no rescale (a follow-up)")
-    self._check_apg("sample_unipc -- the UniPC stage kernels have no projected guidance (a follow-up)")
-    self._check_zero_star("sample_unipc -- the UniPC stage kernels have no CFG-Zero* projection (a follow-up)")
+    self._check_remedies("sample_unipc -- the UniPC stage kernels have no {noun} (a follow-up)")
     if self._thresholding:
         raise NotImplementedError("sample_unipc: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernel has no "
                                   "UniPC form")

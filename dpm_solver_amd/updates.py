@@ -11,10 +11,10 @@ from . import _lib as L
 
 def eval_model(self, x, t, to_x0):
     DV._require_gpu(x)
-    if self._apg_params() is not None:
+    if self._remedy_setting("cfg_apg") is not None:
         # adaptive projected guidance: a direct evaluation has no history -- a first step, on the wrapper's torch path
         # (WrappedModel.apg_x0; the noise prediction is the one equivalent to the guided data prediction)
-        self._check_apg()
+        self._check_remedies(only="cfg_apg")
         tb = (t if torch.is_tensor(t) else self._tt(self._tf(t), x.device)).reshape(-1).expand(x.shape[0] if x.dim() > 0 else 1)
         return self._wrapped.apg_x0(x, tb) if to_x0 else self._wrapped(x, tb)
     mt, gd, sc = self._model_codes()

@@ -12,6 +12,8 @@ import numbers
 
 import torch
 
+from .remedies import REMEDIES
+
 
 class WrappedModel:
     # guidance rescale (Lin et al. 2023, section 3.4; diffusers' `guidance_rescale`): phi in [0, 1], set through
@@ -218,22 +220,45 @@ class WrappedModel:
         return to_noise(e0)
 
 
+def _classifier_free(helper, model_fn):
+    """what every remedy helper asks first: `model_fn` is the result of model_wrapper(..., guidance_type='classifier-free')"""
+    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
+        raise ValueError("%s: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
+                         % (helper, getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
+
+
+def _alone(helper, model_fn):
+    """... and last, unless called with its identity setting: no other row's attribute is set; returns the copy to set its own on"""
+    for r in REMEDIES:
+        if r.name != helper and getattr(model_fn, r.raw):
+            raise NotImplementedError("%s on top of %s: the two remedies are not built together" % (helper, r.name))
+    return copy.copy(model_fn)
+
+
+def apg_params(eta, norm_threshold, momentum):
+    """cfg_apg's arguments, checked (its ranges and texts: a slab pool's submit(apg=...) goes through here too), as floats"""
+    for name, v in (("eta", eta), ("norm_threshold", norm_threshold), ("momentum", momentum)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
+            raise ValueError("cfg_apg: %s must be a real number, got %r" % (name, v))
+    if not 0.0 <= float(eta) <= 1.0:
+        raise ValueError("cfg_apg: eta must be in [0, 1], got %r" % (eta,))
+    if not (0.0 <= float(norm_threshold) < float("inf")):
+        raise ValueError("cfg_apg: norm_threshold must be a finite number >= 0 (0 = off), got %r" % (norm_threshold,))
+    if not -1.0 < float(momentum) < 1.0:
+        raise ValueError("cfg_apg: momentum must be in (-1, 1), got %r" % (momentum,))
+    return float(eta), float(norm_threshold), float(momentum)
+
+
 def cfg_rescale(model_fn, phi):
     """(extension) A copy of the classifier-free wrapper `model_fn` with guidance rescale phi (Lin et al. 2023, "Common
     Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4; the `guidance_rescale` of diffusers pipelines): the
     guided output is rescaled so that its per-sample standard deviation matches the conditional output's, and blended with the
     un-rescaled one -- phi * rescaled + (1 - phi) * guided.  What v-prediction / zero-terminal-SNR checkpoints need at the
     usual guidance scales.  DPM_Solver runs it inside the stage kernel (DPM_F_CFG_RESCALE); phi = 0 changes nothing."""
-    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
-        raise ValueError("cfg_rescale: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
-                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
+    _classifier_free("cfg_rescale", model_fn)
     if isinstance(phi, bool) or not isinstance(phi, numbers.Real) or not (0.0 <= float(phi) <= 1.0):
         raise ValueError("cfg_rescale: phi must be a real number in [0, 1], got %r" % (phi,))
-    if phi and model_fn.guidance_apg is not None:
-        raise NotImplementedError("cfg_rescale on top of cfg_apg: the two remedies are not built together")
-    if phi and model_fn.guidance_zero_star:
-        raise NotImplementedError("cfg_rescale on top of cfg_zero_star: the two remedies are not built together")
-    out = copy.copy(model_fn)
+    out = _alone("cfg_rescale", model_fn) if phi else copy.copy(model_fn)
     out.guidance_rescale = float(phi)
     return out
 
@@ -246,25 +271,12 @@ def cfg_apg(model_fn, eta=0.0, norm_threshold=0.0, momentum=0.0):
     `eta` in [0, 1], and with `momentum` in (-1, 1) replaced by its running average over the network evaluations of a run
     (a = d + momentum * a; the paper uses negative values).  DPM_Solver runs it inside the stage kernel (DPM_F_CFG_APG) of the
     data-prediction samplers.  cfg_apg(fn, 1.0, 0.0, 0.0) is classifier-free guidance itself and changes nothing."""
-    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
-        raise ValueError("cfg_apg: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
-                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
-    for name, v in (("eta", eta), ("norm_threshold", norm_threshold), ("momentum", momentum)):
-        if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v:
-            raise ValueError("cfg_apg: %s must be a real number, got %r" % (name, v))
-    if not 0.0 <= float(eta) <= 1.0:
-        raise ValueError("cfg_apg: eta must be in [0, 1], got %r" % (eta,))
-    if not (0.0 <= float(norm_threshold) < float("inf")):
-        raise ValueError("cfg_apg: norm_threshold must be a finite number >= 0 (0 = off), got %r" % (norm_threshold,))
-    if not -1.0 < float(momentum) < 1.0:
-        raise ValueError("cfg_apg: momentum must be in (-1, 1), got %r" % (momentum,))
-    params = (float(eta), float(norm_threshold), float(momentum))
-    if params != (1.0, 0.0, 0.0) and float(model_fn.guidance_rescale) != 0.0:
-        raise NotImplementedError("cfg_apg on top of cfg_rescale: the two remedies are not built together")
-    if params != (1.0, 0.0, 0.0) and model_fn.guidance_zero_star:
-        raise NotImplementedError("cfg_apg on top of cfg_zero_star: the two remedies are not built together")
-    out = copy.copy(model_fn)
-    out.guidance_apg = None if params == (1.0, 0.0, 0.0) else params
+    _classifier_free("cfg_apg", model_fn)
+    params = apg_params(eta, norm_threshold, momentum)
+    if params == (1.0, 0.0, 0.0):
+        params = None                                        # classifier-free guidance itself
+    out = _alone("cfg_apg", model_fn) if params else copy.copy(model_fn)
+    out.guidance_apg = params
     return out
 
 
@@ -277,14 +289,8 @@ def cfg_zero_star(model_fn):
     both algorithm types; at guidance scale 1 or without an unconditional condition it changes nothing.  The paper's
     "zero-init" -- a zero velocity in the first steps -- is NOT part of it: that is defined for flow-matching velocities and
     has no counterpart for a VP noise prediction."""
-    if not isinstance(model_fn, WrappedModel) or model_fn.guidance_type != "classifier-free":
-        raise ValueError("cfg_zero_star: takes the result of model_wrapper(..., guidance_type='classifier-free'), got %s"
-                         % (getattr(model_fn, "guidance_type", None) or type(model_fn).__name__))
-    if float(model_fn.guidance_rescale) != 0.0:
-        raise NotImplementedError("cfg_zero_star on top of cfg_rescale: the two remedies are not built together")
-    if model_fn.guidance_apg is not None:
-        raise NotImplementedError("cfg_zero_star on top of cfg_apg: the two remedies are not built together")
-    out = copy.copy(model_fn)
+    _classifier_free("cfg_zero_star", model_fn)
+    out = _alone("cfg_zero_star", model_fn)
     out.guidance_zero_star = True
     return out
 
