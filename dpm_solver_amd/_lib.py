@@ -56,6 +56,8 @@ TABLE_BLEND = 32                          # ... another: DPM_F_BLEND stages take
 TABLE_RESCALE = 128                       # ... another: DPM_F_CFG_RESCALE stages take rows too, no records (version 213)
 TABLE_APG = 512                           # ... another: DPM_F_CFG_APG stages take rows and APG records too, and their running
                                           # average is dpm_buffers.thr_hint (version 215; bit 256 is unassigned)
+TABLE_ZSTAR = 4096                        # ... another: DPM_F_CFG_ZSTAR stages take rows too, no records (version 217; bits
+                                          # 1024 and 2048 are unassigned)
 THR_ROW_MAX = 12288                       # elements of the largest sample a thresholded row holds (THR_CHUNK_MAX, csrc)
 TABLE_MAGIC = 0x4c425444
 SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
@@ -304,8 +306,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 216:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 216 -- stale library, rebuild"
+if lib.dpm_version() < 217:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 217 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16
@@ -316,7 +318,7 @@ TABLE_APG_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_APG))            # (TABLE_APG)
 
 def table_bytes(n_req, flags=0):
     """The bytes of the table of a table-mode call of n_req requests whose table_mode carries `flags` (TABLE_NOISE / TABLE_THRESH /
-    TABLE_BLEND / TABLE_RESCALE / TABLE_APG; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
+    TABLE_BLEND / TABLE_RESCALE / TABLE_APG / TABLE_ZSTAR; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
     Not rounded."""
     return (TABLE_HEADER_BYTES + n_req * (TABLE_ROW_BYTES + (TABLE_NOISE_BYTES if flags & TABLE_NOISE else 0)
                                           + (TABLE_BLEND_BYTES if flags & TABLE_BLEND else 0)

@@ -74,6 +74,9 @@ int dpm_table_launch_rescale(const dpm_stage* st, const dpm_buffers* bs, int n_r
 // (unit F, DPM_TABLE_APG) DPM_F_CFG_APG rows and their APG records, one workgroup per sample
 template <typename TS, typename TE>
 int dpm_table_launch_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (unit G, DPM_TABLE_ZSTAR) DPM_F_CFG_ZSTAR rows -- rows like any other, no records --, one workgroup per sample
+template <typename TS, typename TE>
+int dpm_table_launch_zstar(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -43,8 +43,10 @@ struct PairUnits {
   HetFn het;         // unit B's heterogeneous fused launcher (per-request stage records)
   HetFn het_shapes;  // ... and its mixed-shape sibling (dpm_launch_opts.fuse_shapes)
   // the table-driven launch (dpm_launch_opts.table_mode), one slot per row kind (kRowKinds): unit C's plain / UniPC, SDE and
-  // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows, unit F's adaptive-projected-guidance rows
-  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale, table_launch_apg;
+  // thresholded rows, unit D's mask-blend rows, unit E's guidance-rescale rows, unit F's adaptive-projected-guidance rows,
+  // unit G's CFG-Zero* rows
+  TableLaunchFn table_launch, table_launch_noise, table_launch_thresh, table_launch_blend, table_launch_rescale, table_launch_apg,
+      table_launch_zstar;
   // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance, unit G's
   // CFG-Zero*
   SampleFn rescale, apg, zstar;
@@ -53,7 +55,7 @@ struct PairUnits {
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
    dpm_launch_het<TS, TE>, dpm_launch_het_shapes<TS, TE>, dpm_table_launch<TS, TE>,                        \
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
-   dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>,                                         \
+   dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>, dpm_table_launch_zstar<TS, TE>,         \
    dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
    dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
@@ -403,6 +405,9 @@ const RowKind kRowKinds[] = {
     // record carries the running average (the request's thr_hint in such a call) and the three scalars.
     {DPM_TABLE_APG, apg_row_ok, nullptr, false, true, 1, &TableSections::apg, DPM_TABLE_APG_BYTES, table_fill_apg,
      &PairUnits::table_launch_apg},
+    // CFG-Zero* requests (DPM_F_CFG_ZSTAR; dpm_table_zstar.hpp), from ONE member on, for the same reason.  Any of LIN1 / TWO /
+    // MS3 / DENOISE and any guidance scale in one group; the flag has no parameter and no state, so a row is all there is.
+    {DPM_TABLE_ZSTAR, zstar_row_ok, nullptr, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_zstar},
     // every other fusable request, in every call: groups of 2..HET_MAX keep the kernarg records (stage_kernel_het needs no
     // dependent load in front of its tile's own), larger ones take the table.  An SDE group of a call without DPM_TABLE_NOISE
     // is gathered here too -- het_same_group keeps it apart from the ODE groups -- and owns no rows (stage_launch_multi_het).
@@ -448,7 +453,8 @@ int launch_alone(const dpm_stage* st, const dpm_buffers* b, int flags, void* str
 // smaller group and every lone request goes as in mode 0 (LAUNCH) or nowhere (FILL).  Both modes walk the requests in this
 // one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
-  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG);
+  const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
+                                  DPM_TABLE_ZSTAR);
   const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0;
   table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
@@ -542,10 +548,12 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
-  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG);
+  const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
+                                     DPM_TABLE_ZSTAR);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
-                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND / DPM_TABLE_RESCALE / DPM_TABLE_APG)",
+                         "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND / DPM_TABLE_RESCALE / DPM_TABLE_APG / "
+                         "DPM_TABLE_ZSTAR)",
                          o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");

@@ -236,6 +236,25 @@ inline bool apg_row_ok(const dpm_stage& st, const dpm_buffers& b) {
   return buffers_aligned(b, 16, 16) && aligned(b.x_out2, 16);
 }
 
+// May a CFG-Zero* request own a table row (DPM_TABLE_ZSTAR; stage_zstar_kernel_table, dpm_table_zstar.hpp)?  What
+// dpm_stage_launch asks of the flag (check_stage_buffers: classifier-free guidance, no thresholding / blend / noise / rescale /
+// adaptive projected guidance / UniPC, 2- and 4-byte dtypes, a dense network output; the flag has no field of its own) and what
+// a row asks: form LIN1 / TWO / MS3 / DENOISE, a plain request, a SAMPLE (n / batch) of whole 8-element groups -- 16 bytes or a
+// multiple in either dtype: the kernel works per sample and takes the 16-byte accesses only --, every buffer 16-byte aligned,
+// x_out2 too.  For a request with batch >= 1 and n a multiple of it.
+inline bool zstar_row_ok(const dpm_stage& st, const dpm_buffers& b) {
+  if (!(st.flags & DPM_F_CFG_ZSTAR)) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_CFG_RESCALE | DPM_F_CFG_APG)) return false;
+  if (st.guidance != DPM_GUIDE_CFG) return false;
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3 && st.form != DPM_FORM_DENOISE) return false;
+  if (b.state_dtype == DPM_DTYPE_F64 || b.eps_dtype == DPM_DTYPE_F64) return false;
+  if (b.n <= 0 || !plain_request(b) || !b.e0 || !b.e1 || !b.x_out) return false;
+  const int64_t per = b.n / b.batch;
+  const int64_t bs = per * (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2), be = per * (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2);
+  if (per < EPT || per % EPT != 0 || bs % 16 != 0 || be % 16 != 0) return false;
+  return buffers_aligned(b, 16, 16) && aligned(b.x_out2, 16);
+}
+
 // the generator's parameters of one request's SDE stage: the seed from the request's own dpm_launch_opts (none: seed 0),
 // the Philox counter word = the stage index, the scale = the stage's c2
 inline KNoise noise_of(const dpm_stage& st, const dpm_buffers& b) {

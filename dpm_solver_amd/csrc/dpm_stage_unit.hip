@@ -17,7 +17,8 @@
 //               DPM_TABLE_APG; dpm_table_apg.hpp) and nothing else -- units A to E compile to the code they compiled to before
 //               it existed
 //   unit G (6): the launch of a CFG-Zero* stage (stage_zstar_kernel, DPM_F_CFG_ZSTAR; dpm_zstar_kernel.hpp, which no other unit
-//               includes) and nothing else -- units A to F compile to the code they compiled to before it existed
+//               includes) and of the table's CFG-Zero* rows (stage_zstar_kernel_table, DPM_TABLE_ZSTAR; dpm_table_zstar.hpp) and
+//               nothing else -- units A to F compile to the code they compiled to before it existed
 // Units E, F and G are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
@@ -40,6 +41,7 @@
 #if DPM_UNIT == 6
 #include "dpm_sample_frame.hpp"
 #include "dpm_zstar_kernel.hpp"
+#include "dpm_table_zstar.hpp"
 #endif
 
 #include <tuple>
@@ -159,4 +161,13 @@ int dpm_table_launch_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req, 
   return launch_table_apg_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
 template int dpm_table_launch_apg<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+#endif
+
+#if DPM_UNIT == 6
+template <typename TS, typename TE>
+int dpm_table_launch_zstar(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void*, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_zstar_typed<TS, TE>(st, bs, n_req, rows, s);
+}
+template int dpm_table_launch_zstar<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

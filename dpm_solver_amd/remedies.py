@@ -37,7 +37,7 @@ def _bind_zstar(st, on):
 # reads its setting -- falsy = off (0.0, None, False: never set, or no classifier-free blend);  raw: the attribute the helper
 # sets;  bind(stage record, setting);  needs_x0: defined on the data prediction alone;  noun: what a kernel family without the
 # kind "has no";  stages: the adjective of its stages;  blend / double / together / slab: its clause for a MaskBlend corrector, a
-# double state, a second kind, a slab pool;  switch: the request_pool(slots=...) switch that admits it, None: none yet
+# double state, a second kind, a slab pool;  switch: the request_pool(slots=...) switch that admits it
 Remedy = namedtuple("Remedy", "name title label flag attr raw bind needs_x0 noun stages blend double together slab switch")
 # name: the keyword;  excludes: (another switch, why);  needs: why a classifier-free wrapper;  kernel: what has no other epilogue
 Switch = namedtuple("Switch", "name excludes needs kernel")
@@ -74,7 +74,12 @@ REMEDIES = (
          together="the remedies are not built together",
          slab="CFG-Zero* stages have no table row kind yet (a follow-up); a RequestPool (no slots) takes a cfg_zero_star "
               "solver as it is",
-         switch=None),
+         switch=Switch("zero_star", (("rescale", "the CFG-Zero* kernel has no guidance rescale"),
+                                     ("apg", "the CFG-Zero* kernel has no projected guidance"),
+                                     ("sde", "the CFG-Zero* kernel has no noise epilogue"),
+                                     ("thresholding", "the CFG-Zero* kernel has no thresholding"),
+                                     ("inpaint", "the CFG-Zero* kernel has no mask-blend epilogue")),
+                       "CFG-Zero* projects the unconditional output onto the conditional one", "the CFG-Zero* kernel")),
 )
 F_CFG_REMEDIES = sum(r.flag for r in REMEDIES)     # (distinct bits: their OR) what the prologue half of a split stage keeps
 

@@ -128,6 +128,24 @@ ValueError.  Without `apg=True` a slab pool refuses a `cfg_apg` solver as before
 Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
 guidance scale and `cfg_apg(fn, *its parameters)`, for any b, whichever rows it landed in and whatever request used those rows
 before.
+
+`request_pool(slots=S, zero_star=True)` is the slab pool that admits CFG-Zero* requests (`dpm_solver_amd.cfg_zero_star`): an
+effectively classifier-free wrapper, with or without the setting of its own.  The tick's two calls carry DPM_TABLE_ZSTAR: every
+row whose record carries DPM_F_CFG_ZSTAR is a row of the table whatever their number -- ONE stage_zstar_kernel_table launch, one
+workgroup per row, the kernel of the request's own launch -- beside the plain family's, which rows without the flag take; a
+tick stays one network call, one copy and one launch per family present.  A CFG-Zero* row is a row and nothing else: the kind
+has no parameter and no state, so there is no record section and nothing to reset at admission.  The DENOISE stage of
+denoise_to_zero is a CFG-Zero* row too.  Per request: `submit(..., zero_star=True | False)`; the default is the wrapper's.  The
+choice is kept per row; every tick writes it over the gathered records as `_bind_zstar` writes it: DPM_F_CFG_ZSTAR set or
+cleared on classifier-free rows -- cleared: a plain row.  `guidance_scale=` works as in every classifier-free pool.  At its
+first submit such a pool refuses a sample of fewer than 8 elements, one whose element count is no multiple of 8, and one whose
+row is no multiple of 16 bytes (the row could not take the table).  Refused with NotImplementedError: `zero_star=True` with
+`rescale=True`, `apg=True`, `sde=True`, `thresholding=True` or `inpaint=True` (the CFG-Zero* kernel has none of those
+epilogues); `submit_unipc` on a solver whose wrapper carries the setting; `zero_star=True` outside a `zero_star=True` pool.
+`zero_star=` on a pool whose wrapper is not classifier-free, and a value that is no bool, are ValueError.  Without
+`zero_star=True` a slab pool refuses a `cfg_zero_star` solver as before.
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
+guidance scale and `cfg_zero_star` (or not), for any b, whichever rows it landed in.
 """
 import ctypes as C
 import math
@@ -174,6 +192,9 @@ _ROW = (
     ("aeta", np.float32, 1),     # its eta, norm threshold and momentum; (1, 0, 0): classifier-free guidance itself
     ("ar", np.float32, 0),
     ("abeta", np.float32, 0),
+    # CFG-Zero* (see "CFG-Zero*" below)
+    ("zon", np.bool_, False),    # does its request bring its own choice (submit's zero_star=)?
+    ("zsel", np.bool_, False),   # its choice: the CFG-Zero* projection, or plain classifier-free guidance
     # inpainting rows (see "inpainting requests" below)
     ("bslot", np.int64, -1),     # the first row of its inpainting request: where _brec holds its blend records (-1: none)
     ("bmask", np.uint64, 0),     # the mask of its sample
@@ -187,6 +208,7 @@ _ROW_CHECKS = (
     ("_sde", 0, math.inf, "slab pool: sde=True with a sample of %d elements -- a row of the table noise kernel is " + _GROUPS),
     ("_rsc", 8, math.inf, "slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is " + _GROUPS),
     ("_apg", 8, math.inf, "slab pool: apg=True with a sample of %d elements -- an APG row of the table is " + _GROUPS),
+    ("_zst", 8, math.inf, "slab pool: zero_star=True with a sample of %d elements -- a CFG-Zero* row of the table is " + _GROUPS),
     ("_thr", 0, L.THR_ROW_MAX, "slab pool: thresholding=True with a sample of %%d elements -- a thresholded row of the table is "
                                "at most %d elements (one workgroup's LDS), " % L.THR_ROW_MAX + _GROUPS),
 )
@@ -209,7 +231,7 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide", "apg")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide", "apg", "zstar")
 
 
 class _Blend:
@@ -226,7 +248,8 @@ class _Slot:
 class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
-    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False, apg=False):
+    def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False, apg=False,
+                 zero_star=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
@@ -236,9 +259,11 @@ class SlabPool:
         self._inp = bool(inpaint)        # inpainting requests admitted: the tick's calls carry DPM_TABLE_BLEND
         self._rsc = bool(rescale)        # guidance-rescale requests admitted: the tick's calls carry DPM_TABLE_RESCALE
         self._apg = bool(apg)            # adaptive-projected-guidance requests admitted: the tick's calls carry DPM_TABLE_APG
+        self._zst = bool(zero_star)      # CFG-Zero* requests admitted: the tick's calls carry DPM_TABLE_ZSTAR
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
                         | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
-                        | (L.TABLE_RESCALE if self._rsc else 0) | (L.TABLE_APG if self._apg else 0))
+                        | (L.TABLE_RESCALE if self._rsc else 0) | (L.TABLE_APG if self._apg else 0)
+                        | (L.TABLE_ZSTAR if self._zst else 0))
         self._avg = None                 # (an apg=True pool) the running averages: one fp32 slab [S, *sample_shape]
         self._cols = []                  # the per-row arrays of _ROW (self._req, self._pos, ...), each with its idle value
         for name, dtype, idle in _ROW:
@@ -288,7 +313,7 @@ class SlabPool:
                                       "sample()")
         if return_intermediate:
             raise NotImplementedError("slab pool: return_intermediate is not supported; sample it with sample()")
-        _rem.check_slab(s, {"rescale": self._rsc, "apg": self._apg})
+        _rem.check_slab(s, {"rescale": self._rsc, "apg": self._apg, "zero_star": self._zst})
 
     def _apg_params(self, apg):
         """the request's own (eta, norm threshold, momentum) of submit's apg=, checked as cfg_apg checks them; None: the
@@ -306,6 +331,21 @@ class SlabPool:
             raise NotImplementedError("slab pool: apg= -- projected-guidance stages take the table in a pool built with "
                                       "request_pool(slots=..., apg=True) only")
         return apg
+
+    def _zstar_choice(self, on):
+        """the request's own choice of submit's zero_star=, checked; None: the wrapper's"""
+        if on is None:
+            return None
+        w = self._s._wrapped
+        if w is None or w.effective_guidance != "classifier-free":
+            raise ValueError("slab pool: zero_star= belongs to a classifier-free wrapper (with an unconditional condition and a "
+                             "guidance scale other than 1)")
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError("slab pool: zero_star= takes True or False, got %r" % (on,))
+        if on and not self._zst:
+            raise NotImplementedError("slab pool: zero_star= -- CFG-Zero* stages take the table in a pool built with "
+                                      "request_pool(slots=..., zero_star=True) only")
+        return bool(on)
 
     def _guidance(self, scale, phi):
         """the request's own (guidance scale, phi) of submit's guidance_scale= / guidance_rescale=, checked; None: the wrapper's"""
@@ -357,7 +397,7 @@ class SlabPool:
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
                condition=None, unconditional_condition=None, seed=None, generator=None, blend=None, guidance_scale=None,
-               guidance_rescale=None, apg=None):
+               guidance_rescale=None, apg=None, zero_star=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -374,10 +414,14 @@ class SlabPool:
         own phi in [0, 1] -- the result of `sample()` under `cfg_rescale(model_fn, phi)`.  Default for both: the wrapper's.
         `apg=(eta, norm_threshold, momentum)` (a pool built with apg=True): the request's own adaptive projected guidance --
         the result of `sample()` under `cfg_apg(model_fn, eta, norm_threshold, momentum)`; (1.0, 0.0, 0.0) is classifier-free
-        guidance itself.  Default: the wrapper's."""
+        guidance itself.  Default: the wrapper's.
+        `zero_star=True | False` (True: a pool built with zero_star=True): the request's own choice of the CFG-Zero*
+        projection -- the result of `sample()` under `cfg_zero_star(model_fn)`, or under the bare wrapper.  Default: the
+        wrapper's."""
         s = self._s
         guide = self._guidance(guidance_scale, guidance_rescale)
         apg = self._apg_params(apg)
+        zero_star = self._zstar_choice(zero_star)
         if blend is not None:
             if not self._inp:
                 raise NotImplementedError("slab pool: blend= -- mask-blend stages take the table in a pool built with "
@@ -405,7 +449,7 @@ class SlabPool:
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   solver_type, sde=bool(sde))
-        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide, apg)
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide, apg, zero_star)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
@@ -501,7 +545,7 @@ class SlabPool:
         q.keep += list(ops.values())
         return q
 
-    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None, apg=None):
+    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None, apg=None, zstar=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
@@ -514,7 +558,7 @@ class SlabPool:
         q = _Waiting()
         q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
         q.blend = None if blend is None else self._blend_of(blend, x, plan, sd)
-        q.guide, q.apg = guide, apg
+        q.guide, q.apg, q.zstar = guide, apg, zstar
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -595,6 +639,8 @@ class SlabPool:
                 self._guide_admit(q, ra)
             if self._apg:
                 self._apg_admit(q, ra)
+            if q.zstar is not None:
+                self._zstar_admit(q, ra)
             if q.blend is not None:
                 self._blend_admit(q, rows, ra)
                 blends.append((rows, q.blend))
@@ -718,6 +764,21 @@ class SlabPool:
                                  np.uint64(0))
 
     # ------------------------------------------------------------------------------------------------------------------
+    # CFG-Zero* (a zero_star=True pool).  Row fields: zon, zsel.  Checked at submit: _zstar_choice.  Nothing is kept by the
+    # pool: the kind has no parameter and no state.
+    # ------------------------------------------------------------------------------------------------------------------
+    def _zstar_admit(self, q, ra):
+        self._zon[ra], self._zsel[ra] = True, q.zstar
+
+    def _zstar_tick(self, st, rows, rec):
+        """rows whose request brought its own choice: what _bind_zstar writes for a wrapper with the setting (DPM_F_CFG_ZSTAR
+        on a classifier-free record) or leaves for one without (no flag, a plain row), over the gathered records.  Every
+        other row keeps what _prep_stage bound."""
+        on = self._zon[rows] & (rec["guidance"] == L.GUIDE["classifier-free"])
+        z = np.uint32(L.F_CFG_ZSTAR)
+        st["flags"] = np.where(on, np.where(self._zsel[rows], st["flags"] | z, st["flags"] & ~z), st["flags"])
+
+    # ------------------------------------------------------------------------------------------------------------------
     # inpainting requests.  Row fields: bslot, bmask, bper (and samp).  Kept per request: _blends (built at submit: _blend_of)
     # and its records in _brec.
     # ------------------------------------------------------------------------------------------------------------------
@@ -808,6 +869,8 @@ class SlabPool:
                 self._guide_tick(st, rows, rec)
             if self._apg:
                 self._apg_tick(st, rows, rec)
+            if self._zst:
+                self._zstar_tick(st, rows, rec)
             self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed)
             if self._apg:
                 self._apg_buffers(st, b, rows)

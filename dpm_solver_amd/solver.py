@@ -727,7 +727,7 @@ class DPM_Solver:
 
 
     def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False,
-                     apg=False):
+                     apg=False, zero_star=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -754,6 +754,11 @@ class DPM_Solver:
         the pool holds the running averages in a slab of its own, zeroed at admission); samples of whole 8-element groups, a
         data-prediction solver.  Not together with rescale / sde / thresholding / inpaint (the APG kernel has none of those
         epilogues); without the flag a slab pool refuses a `cfg_apg` solver.
+        `slots=S, zero_star=True`: the slab pool of a classifier-free wrapper that admits CFG-Zero* requests -- the wrapper's
+        own setting (`cfg_zero_star`) or the request's (`submit(x, ..., zero_star=True | False)`), their stages in the
+        table-driven launch too (DPM_TABLE_ZSTAR: one stage_zstar_kernel_table launch, one workgroup per row; no record, no
+        state); samples of whole 8-element groups.  Not together with rescale / apg / sde / thresholding / inpaint (the
+        CFG-Zero* kernel has none of those epilogues); without the flag a slab pool refuses a `cfg_zero_star` solver.
         Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
@@ -766,7 +771,7 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
-        on = dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg)
+        on = dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg, zero_star=zero_star)
         _rem.check_switches(self, slots, on)
         if thresholding and not self._thresholding:
             raise ValueError("request_pool: thresholding=True on a solver built without "
@@ -776,7 +781,8 @@ class DPM_Solver:
             if mixed_shapes:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
-            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg)
+            return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg,
+                                  zero_star=zero_star)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -97,11 +97,14 @@ extern "C" {
    ClassifierFreeZeroStarGuidance, ComfyUI's CFGZeroStar) in ONE stage launch -- a kernel that owns a whole sample, takes the
    per-sample least-squares fit of the unconditional output to the conditional one, scales the unconditional output by it, then
    runs the usual blend, conversion, update and stores (see DPM_F_CFG_ZSTAR; no entry point added, no struct changed).
+   217 DPM_TABLE_ZSTAR (a flag on table_mode): CFG-Zero* stages in the table -- every qualifying DPM_F_CFG_ZSTAR request owns a
+   row, a group of them is ONE stage_zstar_kernel_table launch, one workgroup per sample (see "Table mode"; no entry point
+   added, no struct changed, rows and records as in version 215: the kind has no record section).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 216
+#define DPM_HIP_VERSION 217
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -377,6 +380,11 @@ enum { DPM_TABLE_APG = 512 }; /* version 215: a flag OR-ed onto DPM_TABLE_FILL /
                                  running average of every DPM_F_CFG_APG request of the call is its dpm_buffers.thr_hint.  (Bits
                                  16, 64 and 256 are unassigned: table_mode 16 .. 31, 64 .. 127 and 256 .. 511 stay DPM_ERR_ARG,
                                  and so does every mode from 512 on that has one of those bits.) */
+enum { DPM_TABLE_ZSTAR = 4096 }; /* version 217: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the five
+                                    flags above: DPM_F_CFG_ZSTAR stages take rows too, rows like any other, no records.  (4096 is
+                                    the lowest free bit: 16, 64, 256 and 1024 are unassigned, and so is 2048 -- table_mode 2048 |
+                                    513 is pinned as DPM_ERR_ARG since version 215.  Every mode with one of the bits 16, 64, 256,
+                                    1024, 2048, or a bit from 8192 on, stays DPM_ERR_ARG.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 #define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
@@ -590,7 +598,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE), DPM_F_CFG_APG (without DPM_TABLE_APG) and DPM_F_CFG_ZSTAR (version 216; in every call) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE), DPM_F_CFG_APG (without DPM_TABLE_APG) and DPM_F_CFG_ZSTAR (without DPM_TABLE_ZSTAR) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -703,9 +711,28 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    misaligned buffer or average, a separate evaluation state ...) goes, in the same call, as its own dpm_stage_launch, which
    projects too: the same bits, one more launch.  Every sample gets the bits of its request's own dpm_stage_launch (with the
    average in workspace).
+   CFG-Zero* rows (version 217): DPM_TABLE_ZSTAR OR-ed onto either mode, alone or with any of the five flags above, makes the
+   same tick with CFG-Zero* stages (DPM_F_CFG_ZSTAR) in the table (stage_zstar_kernel_table: the kernel of the request's own
+   launch, one workgroup of 512 threads per sample, with pointers and stage scalars read from the sample's row; no cluster, no
+   workspace, no wait on another workgroup).  A DPM_F_CFG_ZSTAR request owns a row when dpm_stage_launch accepts the flag on it
+   -- classifier-free guidance, no DPM_F_THRESH / DPM_F_BLEND / DPM_F_NOISE / DPM_F_CFG_RESCALE / DPM_F_CFG_APG, no
+   DPM_FORM_UNIPC, a 2- or 4-byte dtype pair, a dense network output -- and its form is LIN1, TWO, MS3 or DPM_FORM_DENOISE (the
+   last stage of denoise_to_zero, its buffers checked as LIN1's), its evaluation state is its state, its SAMPLE, n / batch
+   elements, is whole 8-element groups (so a multiple of 16 bytes in either dtype: the kernel works per sample, in 16-byte
+   accesses), and every buffer, x_out2 included, is 16-byte aligned.  Such requests form groups of their own that agree on
+   dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the four forms, every guidance scale (cfg_scale),
+   DPM_F_STORE_M and the duplicate store share a group: each is the row's own.  Every group, from ONE member on, is one run of
+   rows and ONE launch (below 2^31 samples), the runs in the order the groups open, among those of the other families.  A
+   CFG-Zero* row is a row like any other -- the 8 pointers and the 20 words of stage scalars, whose flags word carries
+   DPM_F_CFG_ZSTAR as the stage record does; rows of other requests, the row size and the record sections are byte for byte
+   those of version 215, there is no further section, and the size of the table does not depend on the flag.  A
+   DPM_F_CFG_ZSTAR request that does not qualify (a sample of 12 elements, a misaligned buffer, a separate evaluation state ...)
+   goes, in the same call, as its own dpm_stage_launch, which projects too: the same bits, one more launch.  Without the flag
+   every call is version 216's.  Every sample gets the bits of its request's own dpm_stage_launch.
    Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND,
-   DPM_TABLE_RESCALE, DPM_TABLE_APG: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, each of those plus 128, and each
-   of all these plus 512; bit 256 is unassigned), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   DPM_TABLE_RESCALE, DPM_TABLE_APG, DPM_TABLE_ZSTAR: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, each of those
+   plus 128, each of all these plus 512 -- the 64 modes of version 215 --, and each of those 64 plus 4096; bits 16, 64, 256,
+   1024 and 2048 are unassigned), a non-zero one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
