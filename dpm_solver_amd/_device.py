@@ -186,7 +186,9 @@ def _launch_stage(st, x, xe, e0, e1, g, h1, h2, state_dtype, want_m=None, ext=No
     if g is not None and g.dtype is not ed and sd is torch.float32:
         ed = torch.float32  # an fp32 classifier gradient next to a half network output: widen the output (see _bind_outputs)
     eps_stride = 0
-    if mf is None and e0.dtype == ed and not e0.is_contiguous() and _sample_strided(e0) and e0.shape == ref_t.shape and (
+    # (guidance over two conditions reads three dense outputs: its kernel takes no channel slice)
+    if st.guidance != L.GUIDE["classifier-free-2"] and mf is None and e0.dtype == ed and not e0.is_contiguous() \
+            and _sample_strided(e0) and e0.shape == ref_t.shape and (
             e1 is None or (e1.dtype == ed and _sample_strided(e1) and e1.stride(0) == e0.stride(0))):
         eps_stride = int(e0.stride(0))          # read the slice in place: no .contiguous() copy
         g = _conv(g, ed)

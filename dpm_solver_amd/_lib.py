@@ -30,7 +30,8 @@ UNIPC_VARIANT = {"bh1": 2, "bh2": 3}      # dpm_plan_desc.solver_type of a DPM_A
 METHOD = {"multistep": 0, "singlestep": 1, "singlestep_fixed": 2}
 SKIP = {"time_uniform": 0, "logSNR": 1, "time_quadratic": 2}
 MODEL = {"noise": 0, "x_start": 1, "v": 2, "score": 3}
-GUIDE = {"uncond": 0, "classifier-free": 1, "classifier": 2}
+GUIDE = {"uncond": 0, "classifier-free": 1, "classifier": 2,
+         "classifier-free-2": 3}          # guidance over two conditions: e0 / e1 / g blended by cfg_scale and cg_scale (version 218)
 DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_F64 = 0, 1, 2, 3
 EVAL_LOG_ALPHA, EVAL_ALPHA, EVAL_STD, EVAL_LAMBDA, EVAL_INV_LAMBDA = 0, 1, 2, 3, 4
 FORM_LIN1, FORM_TWO, FORM_MS3, FORM_SS3T, FORM_DENOISE, FORM_UNIPC = 0, 1, 2, 3, 4, 5
@@ -306,8 +307,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 217:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 217 -- stale library, rebuild"
+if lib.dpm_version() < 218:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 218 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16

@@ -226,6 +226,8 @@ def solve(self, x, order, t_T, t_0, h_init=0.05, atol=0.0078, rtol=0.05, theta=0
     DV._require_gpu(x)
     self._check_remedies("method='adaptive' -- its stages take device-resident coefficients, which the {stages} kernel does "
                          "not read (a follow-up)")
+    self._check_pair("method='adaptive' -- its stages take device-resident coefficients, which stage_pair_kernel does not read "
+                     "(a follow-up)")
     if order not in (2, 3):
         raise ValueError("For adaptive step size solver, order must be 2 or 3, got {}".format(order))
     if solver_type not in ['dpmsolver', 'taylor']:

@@ -67,7 +67,7 @@ def auto_captured(self, x, kw, return_intermediate):
     w = self._wrapped
     key = (tuple(sorted((k, (float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)) for k, v in kw.items())),
            tuple(x.shape), x.dtype, x.stride(), dev.index, torch.cuda.current_stream(dev).cuda_stream,
-           bool(self.cluster_in_graph), int(self.thr_spin_limit), self._model_codes(), self._remedy_key(),
+           bool(self.cluster_in_graph), int(self.thr_spin_limit), self._model_codes(), self._remedy_key(), self._pair_key(),
            self._thresholding,
            float(self.dynamic_thresholding_ratio), float(self.thresholding_max_val), self.algorithm_type, self._state_dtype,
            self._sdtype(x), bool(self.adaptive_on_device), int(self.adaptive_lookahead), self.adaptive_max_iterations,

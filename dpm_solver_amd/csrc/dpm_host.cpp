@@ -437,8 +437,9 @@ int check_enum(int v, int lo, int hi, const char* what) {
 extern "C" int dpm_coef_prologue(const dpm_schedule* s, float t_eval, int model_type, int guidance,
                                  double guidance_scale, dpm_stage* st) {
   if (!s || !st) return dpm_set_error(DPM_ERR_ARG, "null pointer");
-  if (check_enum(model_type, 0, 3, "model_type") || check_enum(guidance, 0, 2, "guidance")) return DPM_ERR_ARG;
+  if (check_enum(model_type, 0, 3, "model_type") || check_enum(guidance, 0, 3, "guidance")) return DPM_ERR_ARG;
   set_prologue(s, t_eval, model_type, guidance, guidance_scale, st);
+  if (guidance == DPM_GUIDE_CFG2) st->cg_scale = 0.f;  // s2: the caller's (include/dpm_hip.h, DPM_GUIDE_CFG2)
   return DPM_OK;
 }
 
@@ -494,10 +495,11 @@ void split_stage64(const dpmc::Stage64& q, dpm_stage* st, dpm_stage_f64* d64);
 extern "C" int dpm_coef_prologue_f64(const dpm_schedule* s, double t_eval, int time_f64, int model_type, int guidance,
                                      double guidance_scale, dpm_stage* st, dpm_stage_f64* st64) {
   if (!s || !st || !st64) return dpm_set_error(DPM_ERR_ARG, "null pointer");
-  if (check_enum(model_type, 0, 3, "model_type") || check_enum(guidance, 0, 2, "guidance")) return DPM_ERR_ARG;
+  if (check_enum(model_type, 0, 3, "model_type") || check_enum(guidance, 0, 3, "guidance")) return DPM_ERR_ARG;
   const dpmc::SchedView64 v = s->view64();
   dpmc::Stage64 q{};
   set_prologue(&v, t_eval, model_type, guidance, guidance_scale, &q, !time_f64);
+  if (guidance == DPM_GUIDE_CFG2) q.cg_scale = 0.;  // s2: the caller's
   st->t_eval = (float)q.t_eval; st->t_input = (float)q.t_input; st->alpha_e = (float)q.alpha_e; st->sigma_e = (float)q.sigma_e;
   st->model_type = model_type; st->guidance = guidance; st->cfg_scale = (float)q.cfg_scale; st->cg_scale = (float)q.cg_scale;
   st64->t_eval = q.t_eval; st64->t_input = q.t_input; st64->alpha_e = q.alpha_e; st64->sigma_e = q.sigma_e;
@@ -584,6 +586,7 @@ int plan_build(const S* s, const dpm_plan_desc* d, std::vector<ST>& stages, std:
     st.thr_ratio = (decltype(st.thr_ratio))d->thr_ratio;
     st.thr_max = (decltype(st.thr_max))d->thr_max;
     set_prologue(s, t_eval, d->model_type, d->guidance, d->guidance_scale, &st, !(tf64 & 1));
+    if (d->guidance == DPM_GUIDE_CFG2) st.cg_scale = 0;  // s2: the caller's (include/dpm_hip.h, DPM_GUIDE_CFG2)
     stages.push_back(st);
     time_f64.push_back(tf64);
   };
@@ -816,7 +819,7 @@ void unipc_scalars(const dpm_schedule* s, bool bh1, const std::vector<float>& gr
 extern "C" int dpm_plan_create(const dpm_schedule* s, const dpm_plan_desc* d, dpm_plan** out) {
   if (!s || !d || !out) return dpm_set_error(DPM_ERR_ARG, "null pointer");
   if (check_enum(d->algorithm_type, 0, 3, "algorithm_type") || check_enum(d->model_type, 0, 3, "model_type") ||
-      check_enum(d->guidance, 0, 2, "guidance_type"))
+      check_enum(d->guidance, 0, 3, "guidance_type"))
     return DPM_ERR_ARG;
   if (d->method < 0 || d->method > 2) return dpm_set_error(DPM_ERR_ARG, "Got wrong method %d", d->method);
   if (d->skip_type < 0 || d->skip_type > 2)

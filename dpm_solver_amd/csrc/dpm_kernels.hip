@@ -50,6 +50,8 @@ struct PairUnits {
   // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance, unit G's
   // CFG-Zero*
   SampleFn rescale, apg, zstar;
+  // unit H's stage under guidance over two conditions (DPM_GUIDE_CFG2): a streaming kernel of its own
+  SampleFn pair;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
@@ -57,7 +59,7 @@ struct PairUnits {
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
    dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>, dpm_table_launch_zstar<TS, TE>,         \
    dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
-   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>},
+   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -163,6 +165,28 @@ int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dp
   return DPM_OK;
 }
 
+// What dpm_stage_launch asks of a stage under guidance over two conditions (DPM_GUIDE_CFG2, include/dpm_hip.h) before anything
+// else of the record is read: its two scales, then what stage_pair_kernel has no path for (b->batch >= 1, n a multiple of it).
+// A remedy flag has been reported by check_sample_guidance ("valid under classifier-free guidance only").
+int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b) {
+  auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
+  if (!std::isfinite(st->cfg_scale) || !std::isfinite(st->cg_scale))
+    return fail(DPM_ERR_ARG, "stage_launch: DPM_GUIDE_CFG2 with s1=%g (dpm_stage.cfg_scale), s2=%g (dpm_stage.cg_scale): both must be finite",
+                (double)st->cfg_scale, (double)st->cg_scale);
+  if (st->flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_USER_X0))
+    return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with thresholding, mask blend, noise or a split stage (flags %u)", st->flags);
+  if (st->form == DPM_FORM_UNIPC) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 on a DPM_FORM_UNIPC stage");
+  if (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_UNIPC) return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
+  if (st->flags & (DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC))
+    return fail(DPM_ERR_ARG, "stage_launch: DPM_F_UNIPC_* / DPM_F_STORE_XC are valid on DPM_FORM_UNIPC stages only (form %d)", st->form);
+  if (b->x_out2) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)");
+  if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
+    return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with a double state (no double kernel)");
+  if (b->eps_stride != 0 && b->eps_stride != b->n / b->batch)
+    return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with eps_stride=%lld (a channel slice of a wider output)", (long long)b->eps_stride);
+  return DPM_OK;
+}
+
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
 // base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base);
 // apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace
@@ -175,6 +199,8 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
                 b->noise_sample0);
   if (const SampleGuidance* g = sample_guidance(st->flags))
     if (const int rc = check_sample_guidance(*g, st, b, apg_hint)) return rc;
+  if (st->guidance == DPM_GUIDE_CFG2)
+    if (const int rc = check_pair_guidance(st, b)) return rc;
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -189,6 +215,7 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
   if ((st->flags & DPM_F_STORE_M) && !b->m_out) return fail(DPM_ERR_ARG, "stage_launch: STORE_M without m_out");
   if (st->guidance == DPM_GUIDE_CFG && !b->e1) return fail(DPM_ERR_ARG, "stage_launch: CFG needs e1");
   if (st->guidance == DPM_GUIDE_CLASSIFIER && !b->g) return fail(DPM_ERR_ARG, "stage_launch: classifier guidance needs g");
+  if (st->guidance == DPM_GUIDE_CFG2 && (!b->e1 || !b->g)) return fail(DPM_ERR_ARG, "stage_launch: DPM_GUIDE_CFG2 needs e1 and g");
   if (st->flags & DPM_F_BLEND) {
     if (!b->mask || !b->blend_a || b->mask_period < 1)
       return fail(DPM_ERR_ARG, "stage_launch: DPM_F_BLEND needs mask, blend_a and mask_period >= 1");
@@ -250,6 +277,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_FORM_UNIPC with device-resident coefficients");
   const SampleGuidance* const g = sample_guidance(st->flags);
   if (dyn && g) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: %s with device-resident coefficients", g->name);
+  if (dyn && st->guidance == DPM_GUIDE_CFG2)
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with device-resident coefficients");
   dpm_buffers bb = *b;
   if (!bb.x) bb.x = bb.xe;  // DENOISE form: only the evaluation state exists
   const int sd = bb.state_dtype, ed = bb.eps_dtype;
@@ -261,6 +290,7 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   const PairUnits* p = pair_of(sd, ed);
   if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
   if (g) return (p->*g->launch)(st, &bb, stream, ev_start, ev_stop);
+  if (st->guidance == DPM_GUIDE_CFG2) return p->pair(st, &bb, stream, ev_start, ev_stop);  // (before the fused-shape test)
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused

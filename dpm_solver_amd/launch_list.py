@@ -8,12 +8,13 @@ import torch
 from . import _device as DV
 from . import _lib as L
 
-def _bind_outputs(b, e0, e1, g, sd, shape, mf=None):
+def _bind_outputs(b, e0, e1, g, sd, shape, mf=None, pair=False):
     """Point a launch record at the fresh network outputs (e0 / e1 / g): choose the eps dtype the kernels have
     ((fp32 state, any eps) and equal low-precision pairs), read channel slices of a wider output in place
     (eps_stride), convert / copy only when there is no kernel for the layout.  `mf`: the memory format the run's
     buffers are in (None: default-contiguous; channels_last when the network works in NHWC, see DV._mf_of) -- outputs in
-    that format are bound as they are.  Returns the tensors to keep alive."""
+    that format are bound as they are.  `pair`: a record of guidance over two conditions (DPM_GUIDE_CFG2) -- its kernel reads
+    three DENSE outputs and takes no channel slice (as in DV._launch_stage).  Returns the tensors to keep alive."""
     ed = e0.dtype
     if ed is not sd and (sd is not torch.float32 or ed not in DV._DT):
         ed = sd
@@ -30,7 +31,7 @@ def _bind_outputs(b, e0, e1, g, sd, shape, mf=None):
     elif e0.dtype is ed and e0.is_contiguous() and (e1 is None or (e1.dtype is ed and e1.is_contiguous())) \
             and (g is None or (g.dtype is ed and g.is_contiguous())):
         pass
-    elif e0.dtype is ed and not e0.is_contiguous() and DV._sample_strided(e0) and e0.shape == shape and (
+    elif not pair and e0.dtype is ed and not e0.is_contiguous() and DV._sample_strided(e0) and e0.shape == shape and (
             e1 is None or (e1.dtype is ed and DV._sample_strided(e1) and e1.stride(0) == e0.stride(0))):
         stride = int(e0.stride(0))      # channel slice of a wider output: read in place
         g = DV._conv(g, ed)
@@ -74,7 +75,7 @@ class _FastRun:
         esz = torch.empty((), dtype=sd).element_size()
         self.last = nstg - 1
         for i, ps in enumerate(plan.stages):
-            st = solver._prep_stage(ps.copy())
+            st = solver._unguided64(solver._prep_stage(ps.copy()), sd)
             b = L.Buffers()
             xi, xei, oi = plan.roles[i]
             if xi > 0:

@@ -26,28 +26,28 @@ def run_plan_group(self, plan, xs, sd, cfg):
     stream, idx, capturing, other = DV._launch_ctx(device)
     R, shape = len(xs), xs[0].shape
     V = self._time_views(plan, device, shape[0], cfg)
-    tb, ti, t2 = V["t_eval_b"], V["t_input_b"], V["t_input_2b"]
+    tb, ti, t2 = V["t_eval_b"], V["t_input_b"], V["t_input_2b"]      # (t2: under classifier-free guidance, over one or two conditions)
     if self.fresh_time_tensors:
-        tb, ti, t2 = _Cloning(tb), _Cloning(ti), (_Cloning(t2) if cfg else None)
+        tb, ti, t2 = _Cloning(tb), _Cloning(ti), (_Cloning(t2) if t2 is not None else None)
     wrapped, model_fn = self._wrapped, self._model_fn
 
     def net(x_t, i, x2=None):
         if wrapped is not None:
-            return wrapped.raw_outputs(x_t, tb[i], ti[i], t2[i] if cfg else None, x_in2=x2)
+            return wrapped.raw_outputs(x_t, tb[i], ti[i], t2[i] if t2 is not None else None, x_in2=x2)
         return model_fn(x_t, tb[i]), None, None
     first0 = net(xs[0], 0)                   # on the callers' x_T (ref :1179, :1222); decides the state dtype
     if not self.fresh_time_tensors and plan.written(V):
         # the network edits its time argument in place and the requests of a stage share one row: clones from here on
         self.fresh_time_tensors = True
         V = self._time_views(plan, device, shape[0], cfg)
-        tb, ti, t2 = _Cloning(V["t_eval_b"]), _Cloning(V["t_input_b"]), (_Cloning(V["t_input_2b"]) if cfg else None)
+        tb, ti, t2 = _Cloning(V["t_eval_b"]), _Cloning(V["t_input_b"]), (_Cloning(V["t_input_2b"]) if t2 is not None else None)
     first = [first0] + [net(x, 0) for x in xs[1:]]
     sd = self._promoted(sd, first[0][0], plan)
     mf = DV._mf_of(first[0][0]) if first[0][0].shape == shape else None
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(shape), sd, idx, stream, cfg, R, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._remedy_key())
+           self._remedy_key(), self._pair_key())
     grp = None if capturing else self._fast_groups.get(key)
     if grp is None:
         runs = [_FastRun(self, plan, shape, sd, device, cfg, mf) for _ in range(R)]
@@ -89,6 +89,7 @@ def _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, 
     x0s = [DV._conv(x, sd, mf) for x in xs]
     outs = [DV._empty(shape, sd, device, mf) for _ in range(R)]
     last, roles = runs[0].last, plan.roles
+    pair = self._pair_setting() is not None      # three dense outputs per request (launch_list._bind_outputs)
     launch = DV._stage_launch_multi_raw
     for i, a in enumerate(arrs):
         xi, xei, _ = roles[i]
@@ -109,7 +110,7 @@ def _advance_group(self, plan, xs, sd, cfg, mf, runs, arrs, first, net, stream, 
             e = first[r] if i == 0 else net(xe_t, i, x2)
             if sd is torch.float64:
                 e = self._cfg_pre(e, sd)
-            keep.append(_bind_outputs(b, e[0], e[1], e[2], sd, shape, mf))
+            keep.append(_bind_outputs(b, e[0], e[1], e[2], sd, shape, mf, pair))
         st_ref = runs[0].refs[i][0]
         if other:
             with torch.cuda.device(idx):
@@ -134,9 +135,9 @@ def run_plan_fast(self, plan, x, sd, cfg):
     # the first evaluation is on the caller's x_T whatever the plan (ref :1179, :1222): run it before choosing
     # the buffers, its output dtype decides the state dtype (see _promoted)
     if self.fresh_time_tensors:
-        tb, ti, t2 = _Cloning(tb), _Cloning(ti), (_Cloning(t2) if cfg else None)
+        tb, ti, t2 = _Cloning(tb), _Cloning(ti), (_Cloning(t2) if t2 is not None else None)
     if wrapped is not None:
-        first = wrapped.raw_outputs(x, tb[0], ti[0], t2[0] if cfg else None, x_in2=None)
+        first = wrapped.raw_outputs(x, tb[0], ti[0], t2[0] if t2 is not None else None, x_in2=None)
     else:
         first = (model_fn(x, tb[0]), None, None)
     sd = self._promoted(sd, first[0], plan)
@@ -146,7 +147,7 @@ def run_plan_fast(self, plan, x, sd, cfg):
     if plan.sde:
         mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
     key = (id(plan), tuple(x.shape), sd, idx, stream, cfg, mf, bool(self.cluster_in_graph), int(self.thr_spin_limit),
-           self._remedy_key())
+           self._remedy_key(), self._pair_key())
     fr = None if capturing else self._fast.get(key)      # a captured graph bakes its buffers in: give it its own
     if fr is None:
         fr = _FastRun(self, plan, x.shape, sd, device, cfg, mf)
@@ -167,6 +168,7 @@ def run_plan_fast(self, plan, x, sd, cfg):
         for b in bufs:
             b.opts = o
     xbuf, xfull = fr.xbuf, fr.xfull
+    pair = self._pair_setting() is not None      # three dense outputs (launch_list._bind_outputs)
     launch = DV._stage_launch_raw
     for i, b in enumerate(bufs):
         xi, xei, _ = roles[i]
@@ -181,12 +183,12 @@ def run_plan_fast(self, plan, x, sd, cfg):
         if i == 0:
             e0, e1, g = first
         elif wrapped is not None:
-            e0, e1, g = wrapped.raw_outputs(xe_t, tb[i], ti[i], t2[i] if cfg else None, x_in2=x2)
+            e0, e1, g = wrapped.raw_outputs(xe_t, tb[i], ti[i], t2[i] if t2 is not None else None, x_in2=x2)
         else:
             e0, e1, g = model_fn(xe_t, tb[i]), None, None
         if sd is torch.float64:
             e0, e1, g = self._cfg_pre((e0, e1, g), sd)
-        keep = _bind_outputs(b, e0, e1, g, sd, x.shape, mf)
+        keep = _bind_outputs(b, e0, e1, g, sd, x.shape, mf, pair)
         if other:
             with torch.cuda.device(idx):
                 rc = launch(refs[i][0], refs[i][1], stream)
@@ -204,6 +206,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     sd = self._sdtype(x)
     cfg = self._wrapped is not None and self._wrapped.effective_guidance == "classifier-free"
     self._check_remedies(sd=sd, blend=isinstance(cxt, MaskBlend))   # the one check of a run (its loops do not repeat it)
+    self._check_pair(blend=isinstance(cxt, MaskBlend))
     # denoise_to_zero evaluates the data prediction at a (1,)-shaped time (ref :1236: `torch.ones((1,)) * t_0`): on a
     # continuous schedule its alpha_t / sigma_t are then dimensioned fp32 tensors and the RESULT of a half-precision run
     # is fp32 (on a discrete schedule every run is fp32 anyway).  That last stage runs in fp32 in the general loop below.
@@ -230,7 +233,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
     V = self._time_views(plan, device, x.shape[0] if x.dim() > 0 else 1, cfg)
     if self.fresh_time_tensors:
         V = dict(V, t_eval_b=_Cloning(V["t_eval_b"]), t_input_b=_Cloning(V["t_input_b"]),
-                 t_input_2b=_Cloning(V["t_input_2b"]) if cfg else None)
+                 t_input_2b=_Cloning(V["t_input_2b"]) if V["t_input_2b"] is not None else None)
     blend = cxt if isinstance(cxt, MaskBlend) else None      # folded into the stage kernels' epilogue
     if blend is not None:
         cxt = None
@@ -252,7 +255,7 @@ def run_plan(self, plan, x, method, cxt, keep, intermediates):
         from_tmp = st.xe_src == L.SRC_TMP
         xe = tmp if from_tmp else state
         outs = self._network(xe, None, None, x_in2=tmp2 if from_tmp else state2,
-                             pre=(V["t_eval_b"][i], V["t_input_b"][i], V["t_input_2b"][i] if cfg else None))
+                             pre=(V["t_eval_b"][i], V["t_input_b"][i], V["t_input_2b"][i] if V["t_input_2b"] is not None else None))
         if i == 0:
             sd = self._promoted(sd, outs[0], plan)
         if i == 0 and method == 'multistep':

@@ -81,14 +81,16 @@ class _Plan:
 
     def time_views(self, device, batch, cfg):
         """per stage: 0-dim t_eval / t_out, t_eval and t_input expanded to (batch,) and, under classifier-free
-        guidance, t_input expanded to (2*batch,) -- views of times(), built once per (device, batch).
+        guidance, t_input expanded to (2*batch,) -- views of times(), built once per (device, batch).  `cfg`: True / False, or 3
+        for guidance over two conditions, whose network call takes three copies: `t_input_2b` is (3*batch,) then.
 
         The vectors are SHARED by every later call of the plan (the reference hands the network a fresh tensor per call,
         ref :404).  A network or callback that writes into its time argument in place (`t.mul_(1000)`) is detected through
         the tensors' version counters: the next call finds them changed, rebuilds the vectors from the host plan and sets
         `times_written` -- DPM_Solver then hands out clones (`fresh_time_tensors`).  Inside one trajectory every row is
         handed out once, so the trajectory during which the first write happens is still correct."""
-        key = (str(device), int(batch), bool(cfg))
+        copies = 3 if cfg == 3 else (2 if cfg else 1)      # of the state in one network call (True == 3 is False)
+        key = (str(device), int(batch), copies)
         hit = self._views.get(key)
         if hit is not None and hit["ver"] is not None and _versions(hit["base"]) != hit["ver"]:
             self._views.pop(key)
@@ -102,7 +104,7 @@ class _Plan:
             # torch.cat([t] * 2) under CFG) for models that need contiguous inputs.  Materialised once per (plan, batch)
             # -- two small kernels here, none per step.  `repeat` always copies: the vectors never alias times().
             te = T[0].reshape(n, 1).repeat(1, batch)
-            ti = T[1].reshape(n, 1).repeat(1, 2 * batch if cfg else batch)
+            ti = T[1].reshape(n, 1).repeat(1, copies * batch)
             if len(self._views) >= 8:                 # bounded: one entry per (device, batch, cfg)
                 self._views.pop(next(iter(self._views)))
             hit = dict(t_eval=[T[0, i] for i in range(n)], t_out=[T[2, i] for i in range(n)],
@@ -117,7 +119,7 @@ class _Plan:
                 # (dpm_stage_f64.time_f64, set by the planner).
                 T64 = self.times64(device)
                 te64 = T64[0].reshape(n, 1).repeat(1, batch)
-                ti64 = T64[1].reshape(n, 1).repeat(1, 2 * batch if cfg else batch)
+                ti64 = T64[1].reshape(n, 1).repeat(1, copies * batch)
                 for i, s64 in enumerate(self.stages64):
                     if s64.time_f64 & 1:
                         hit["t_eval"][i], hit["t_eval_b"][i] = T64[0, i], te64[i]
@@ -157,7 +159,7 @@ class _Cloning:
 def get_plan(self, precision=0, **kw):
     mt, gd, sc = self._model_codes()
     key = (tuple(sorted(kw.items())), mt, gd, sc, self._thresholding, float(self.dynamic_thresholding_ratio),
-           float(self.thresholding_max_val), self.algorithm_type, int(precision))
+           float(self.thresholding_max_val), self.algorithm_type, int(precision), self._pair_key())
     plan = self._plans.get(key)
     if plan is None:
         d = L.PlanDesc()

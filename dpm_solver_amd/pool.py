@@ -155,6 +155,7 @@ class RequestPool:
         s = self._s
         sd = s._sdtype(x)
         s._check_remedies(sd=sd)            # (a pool's requests do not pass run_plan)
+        s._check_pair("request_pool -- a pool's ticks are fused launches, and a two-condition stage runs on its own in those")
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
             raise NotImplementedError("request pool: denoise_to_zero with a half-precision state on a continuous schedule "

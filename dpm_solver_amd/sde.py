@@ -46,6 +46,7 @@ def check_solver(self, order):
         raise NotImplementedError("sample_sde: algorithm_type='dpmsolver' (the noise-prediction SDE variant) is not built; "
                                   "use algorithm_type='dpmsolver++'")
     self._check_remedies("sample_sde -- the SDE stage kernels have no {noun} (a follow-up)")
+    self._check_pair("sample_sde -- the SDE stage kernels blend two network outputs, not three (a follow-up)")
     if self._thresholding:
         raise NotImplementedError("sample_sde: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernel has no noise "
                                   "epilogue")

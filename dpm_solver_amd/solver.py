@@ -165,7 +165,7 @@ class DPM_Solver:
     def _model_codes(self):
         if self._wrapped is not None:
             w = self._wrapped
-            return L.MODEL[w.model_type], L.GUIDE[w.effective_guidance], float(w.guidance_scale)
+            return L.MODEL[w.model_type], L.GUIDE[w.effective_guidance], float(w.guidance_scale)   # (cfg_pair: s1 is the scale)
         return L.MODEL["noise"], L.GUIDE["uncond"], 1.0
 
     # the classifier-free remedies (cfg_rescale, cfg_apg, cfg_zero_star): one table, one face (dpm_solver_amd/remedies.py)
@@ -173,6 +173,41 @@ class DPM_Solver:
     _remedy_setting = _rem.setting
     _remedy_key = _rem.key
     _check_remedies = _rem.check
+
+    # guidance over two conditions (cfg_pair; DPM_GUIDE_CFG2): its setting, its cache key, what it is not built with
+    _PAIR = "guidance over two conditions (cfg_pair)"
+
+    def _pair_setting(self):
+        """(s1, s2) of the wrapper's cfg_pair, None = off"""
+        p = self._wrapped.pair if self._wrapped is not None else None
+        return None if p is None else (float(p[1]), float(p[2]))
+
+    def _pair_key(self):
+        """what the caches of plans, launch records and graphs key on besides _remedy_key(): changes with the pair setting.
+        condition2 enters by IDENTITY, like the wrapper's own conditions in the graph cache's key (capture.auto_captured) and in
+        its concatenated `_c_in`.  The wrapper holds the tensor, so no other tensor takes its id while the wrapper lives; what the
+        key cannot see is an edit IN PLACE, or a `guidance_pair` assigned by hand.  Hence the rule (cfg_pair's docstring,
+        INTEGRATION.md): a condition tensor is immutable for the life of its wrapper -- the concatenated conditions are built
+        once and a captured graph keeps replaying them.  Another condition takes another cfg_pair(...) and another DPM_Solver."""
+        p = self._wrapped.pair if self._wrapped is not None else None
+        return None if p is None else (id(p[0]), float(p[1]), float(p[2]))
+
+    def _check_pair(self, what=None, blend=False):
+        """The combinations guidance over two conditions is not built with.  `what` names a sampler or a mode without the
+        three-branch kernel; else the solver-wide rules, then the run's corrector (`blend`)."""
+        if self._pair_setting() is None:
+            return
+        if what is not None:
+            raise NotImplementedError("%s: %s" % (self._PAIR, what))
+        if self._thresholding:
+            raise NotImplementedError("%s: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernels blend two network "
+                                      "outputs, not three (a follow-up)" % self._PAIR)
+        if self._user_x0 is not None:
+            raise NotImplementedError("%s: a callable correcting_x0_fn -- the split stage's prologue kernel blends two network "
+                                      "outputs, not three (a follow-up)" % self._PAIR)
+        if blend:
+            raise NotImplementedError("%s: a MaskBlend corrector -- stage_pair_kernel has no mask-blend epilogue (a follow-up)"
+                                      % self._PAIR)
 
     def _apg_average(self, shape, device):
         """a zeroed running average for one run under adaptive projected guidance with a momentum (fp32, the state's shape);
@@ -270,8 +305,9 @@ class DPM_Solver:
         return sd
 
     def _time_views(self, plan, device, batch, cfg):
-        """plan.time_views; a network that was caught writing into the shared time vectors gets clones from now on"""
-        V = plan.time_views(device, batch, cfg)
+        """plan.time_views; a network that was caught writing into the shared time vectors gets clones from now on.  Guidance
+        over two conditions calls the network on three copies: its `t_input_2b` is the tripled time, built once like the doubled one"""
+        V = plan.time_views(device, batch, 3 if self._pair_setting() is not None else cfg)
         if plan.times_written and not self.fresh_time_tensors:
             self.fresh_time_tensors = True
         return V
@@ -290,8 +326,8 @@ class DPM_Solver:
             te, ti, t2 = pre
         else:
             te, ti = t_eval_t.expand(B), t_input_t.expand(B)
-            t2 = t_input_t.expand(2 * B) if (self._wrapped is not None and
-                                             self._wrapped.effective_guidance == "classifier-free") else None
+            eff = self._wrapped.effective_guidance if self._wrapped is not None else None
+            t2 = t_input_t.expand(2 * B) if eff == "classifier-free" else t_input_t.expand(3 * B) if eff == "classifier-free-2" else None
         if self._wrapped is not None:
             return self._wrapped.raw_outputs(x_eval, te, ti, t2, x_in2=x_in2)
         return self._model_fn(x_eval, te), None, None
@@ -329,6 +365,13 @@ class DPM_Solver:
         scalar touches the result.  The double kernel would blend in double, so the blend is taken here, in the reference's
         own expression, and handed on as both halves (e1 + s * (e0 - e1) with e0 == e1 is exact)."""
         e0, e1, g = outs
+        pair = self._pair_setting()
+        if sd is torch.float64 and pair is not None:
+            # guidance over two conditions has no double kernel: the three raw outputs are blended here, in double, and handed
+            # on as ONE unguided output (the conversions are affine in the output and the three weights sum to one, so blending
+            # before them is the same function; the stage record is unguided then: _unguided64)
+            e0, e1, g = e0.double(), e1.double(), g.double()
+            return (e1 + pair[0] * (e0 - e1)) + pair[1] * (g - e1), None, None
         if (sd is torch.float64 and e1 is not None and e0.dtype is not torch.float64 and self._wrapped is not None
                 and self._wrapped.model_type == "noise"):
             e = e1 + self._wrapped.guidance_scale * (e0 - e1)
@@ -353,6 +396,12 @@ class DPM_Solver:
         out.thr_max = float(self.thresholding_max_val)
         return out
 
+    def _unguided64(self, st, sd):
+        """a double state under guidance over two conditions: _cfg_pre hands the stage ONE blended output -- its record is unguided"""
+        if sd is torch.float64 and st.guidance == L.GUIDE["classifier-free-2"]:
+            st.guidance = L.GUIDE["uncond"]
+        return st
+
     def _prep_stage(self, st):
         """stage flags and fields that depend on this solver's correctors and on its wrapper's remedy: per active kind its
         check, its refusal of a thresholded stage, its bind"""
@@ -366,6 +415,9 @@ class DPM_Solver:
             if st.flags & L.F_THRESH:
                 raise _rem.thresholded(r)
             r.bind(st, v)
+        if st.guidance == L.GUIDE["classifier-free-2"]:
+            self._check_pair()
+            st.cg_scale = self._pair_setting()[1]               # s2 (the planner wrote 0; cfg_scale is s1 already)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
@@ -373,6 +425,7 @@ class DPM_Solver:
         stage: prologue kernel -> user function (opaque torch) -> combination kernel."""
         self._check_remedies(sd=sd)         # (sd: possibly promoted by the first evaluation; st was bound by _prep_stage)
         e0, e1, g = outs if sd is not torch.float64 else self._cfg_pre(outs, sd)
+        self._unguided64(st, sd)
         if self._user_x0 is not None and (st.flags & L.F_TO_X0):
             s1 = st.copy()
             s1.form = L.FORM_DENOISE
@@ -771,6 +824,8 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
+        self._check_pair("request_pool -- a pool's ticks are fused and table-driven launches, and a two-condition stage runs on its "
+                         "own in those (sample_requests takes such a solver; a pool is a follow-up)")
         on = dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg, zero_star=zero_star)
         _rem.check_switches(self, slots, on)
         if thresholding and not self._thresholding:
@@ -798,6 +853,7 @@ class DPM_Solver:
         synchronisation, no data-dependent control flow), shapes are frozen, and the returned tensors are static
         buffers that the next replay overwrites.  method='adaptive' is captured with its device-side controller: exactly
         `adaptive_max_iterations` (default 64) iterations are recorded, those after t_end is reached do nothing."""
+        self._check_pair()
         apg = self._remedy_setting("cfg_apg")
         if apg is not None and apg[2] != 0.0:
             self._check_remedies("capture with a momentum -- a replayed graph would carry the running average of one run into "

@@ -25,6 +25,7 @@ def check_solver(self, order, variant):
         raise NotImplementedError("sample_unipc: algorithm_type='dpmsolver' (the noise-prediction UniPC) is not built; "
                                   "use algorithm_type='dpmsolver++'")
     self._check_remedies("sample_unipc -- the UniPC stage kernels have no {noun} (a follow-up)")
+    self._check_pair("sample_unipc -- the UniPC stage kernels blend two network outputs, not three (a follow-up)")
     if self._thresholding:
         raise NotImplementedError("sample_unipc: correcting_x0_fn='dynamic_thresholding' -- the thresholding kernel has no "
                                   "UniPC form")

@@ -8,6 +8,7 @@ kernel instead of running them as separate elementwise passes.  The network itse
 call through the classifier) stays an opaque PyTorch-ROCm call on the current stream.
 """
 import copy
+import math
 import numbers
 
 import torch
@@ -25,6 +26,10 @@ class WrappedModel:
     # CFG-Zero* (Fan et al. 2025; diffusers' ClassifierFreeZeroStarGuidance): set through dpm_solver_amd.cfg_zero_star.
     # False = off: every bit as without it.
     guidance_zero_star = False
+    # guidance over two conditions (InstructPix2Pix's image and text scales, composable conditions): (condition2, s1, s2), set
+    # through dpm_solver_amd.cfg_pair.  None = off: every bit as without it.
+    guidance_pair = None
+    _c_in3 = None                            # (condition2, the three conditions concatenated)
 
     def __init__(self, model, noise_schedule, model_type, model_kwargs, guidance_type, condition,
                  unconditional_condition, guidance_scale, classifier_fn, classifier_kwargs):
@@ -45,10 +50,20 @@ class WrappedModel:
     def effective_guidance(self):
         if self.guidance_type == "classifier":
             return "classifier"
+        if self.pair is not None:
+            return "classifier-free-2"           # (also at guidance_scale == 1: the second condition still guides)
         if self.guidance_type == "classifier-free" and not (
                 self.guidance_scale == 1. or self.unconditional_condition is None):
             return "classifier-free"
         return "uncond"
+
+    @property
+    def pair(self):
+        """(condition2, s1, s2) of the guidance over two conditions this wrapper asks the stage kernels for (include/dpm_hip.h,
+        DPM_GUIDE_CFG2: eps = (n_u + s1 * (n_c - n_u)) + s2 * (n_c2 - n_u)); None = none"""
+        if self.guidance_pair is None or self.guidance_type != "classifier-free" or self.unconditional_condition is None:
+            return None
+        return self.guidance_pair
 
     @property
     def rescale_phi(self):
@@ -140,6 +155,16 @@ class WrappedModel:
             g = self._cond_grad(x, t_input)
             return self.model(x, t_input, **kw), None, g
         if self.guidance_type == "classifier-free":
+            if self.pair is not None:
+                # guidance over two conditions: ONE call on three copies of x, conditions ordered (uncond, condition,
+                # condition2); returns (e0, e1, e2) -- e2 travels where the classifier gradient does (dpm_buffers.g)
+                c3 = self._c_in3
+                if c3 is None or c3[0] is not self.pair[0]:   # the conditioning does not change between steps: concatenate once
+                    c3 = self._c_in3 = (self.pair[0], torch.cat([self.unconditional_condition, self.condition, self.pair[0]]))
+                # t_input2: the tripled time the solver's loops keep per stage (DPM_Solver._time_views), like the doubled one below
+                t_in = t_input2 if t_input2 is not None else torch.cat([t_input] * 3)
+                e1, e0, e2 = self.model(torch.cat([x] * 3), t_in, c3[1], **kw).chunk(3)
+                return e0, e1, e2
             if self.guidance_scale == 1. or self.unconditional_condition is None:
                 return self.model(x, t_input, self.condition, **kw), None, None
             # x_in2: the stage kernel that produced x already wrote it into both halves of one [2B,...] buffer
@@ -184,6 +209,19 @@ class WrappedModel:
                 return expand_dims(alpha_t, dims) * out + expand_dims(sigma_t, dims) * x
             return -expand_dims(sigma_t, dims) * out              # "score"
         eff = self.effective_guidance
+        if eff == "classifier-free-2":
+            # guidance over two conditions, the torch statement of the contract (include/dpm_hip.h, DPM_GUIDE_CFG2): half
+            # outputs are widened to fp32 first, as the stage kernel widens them, the conversions per output, then the five
+            # operations with both scales as fp32 values; nothing is rounded to half
+            e2 = g
+            if e0.dtype in (torch.float16, torch.bfloat16):
+                e0, e1, e2 = e0.float(), e1.float(), e2.float()
+                x = x.float()
+            _, s1, s2 = self.pair
+            if e0.dtype is torch.float32:
+                s1, s2 = (float(torch.tensor(float(s), dtype=torch.float32)) for s in (s1, s2))
+            n0, n1, n2 = to_noise(e0), to_noise(e1), to_noise(e2)
+            return (n1 + s1 * (n0 - n1)) + s2 * (n2 - n1)
         if eff == "classifier":                                   # ref :315-321
             _, sigma_t = self.noise_schedule.device_alpha_sigma(t_continuous)
             return to_noise(e0) - self.guidance_scale * expand_dims(sigma_t, dims) * g
@@ -232,6 +270,8 @@ def _alone(helper, model_fn):
     for r in REMEDIES:
         if r.name != helper and getattr(model_fn, r.raw):
             raise NotImplementedError("%s on top of %s: the two remedies are not built together" % (helper, r.name))
+    if getattr(model_fn, "guidance_pair", None) is not None:
+        raise NotImplementedError("%s on top of cfg_pair: the two-condition stage kernel has no remedy (a follow-up)" % helper)
     return copy.copy(model_fn)
 
 
@@ -292,6 +332,46 @@ def cfg_zero_star(model_fn):
     _classifier_free("cfg_zero_star", model_fn)
     out = _alone("cfg_zero_star", model_fn)
     out.guidance_zero_star = True
+    return out
+
+
+def cfg_pair(model_fn, condition2, scale2, nested=False):
+    """(extension) A copy of the classifier-free wrapper `model_fn` with guidance over TWO conditions: the network is evaluated
+    on three copies of the input -- unconditional, `condition` (the wrapper's), `condition2` -- and the three outputs are blended
+    inside the stage kernel (DPM_GUIDE_CFG2, stage_pair_kernel), in fp32.  With s = the wrapper's guidance_scale:
+      nested=False (composable conditions):  e_u + s (e_c - e_u) + scale2 (e_c2 - e_u)
+      nested=True (InstructPix2Pix):         e_u + scale2 (e_c2 - e_u) + s (e_c - e_c2) -- `condition` carries BOTH conditions
+                                             (image and text), `condition2` the inner one alone (the image); scale2 is the image
+                                             scale, s the text scale
+    Both are (e_u + s1 (e_c - e_u)) + s2 (e_c2 - e_u) with s1 = s and s2 = scale2 (composable) or scale2 - s (nested, formed in
+    double and rounded once).  s2 == 0 is classifier-free guidance itself: a plain copy, no third branch.  Not together with
+    cfg_rescale / cfg_apg / cfg_zero_star, in either order.
+    The three conditions are IMMUTABLE for the life of the returned wrapper: they are concatenated once, at the first
+    evaluation, the solver's caches of plans, launch records and graphs know `condition2` by identity, and a captured graph
+    replays the concatenation it was recorded with -- an edit in place would go unnoticed.  For another condition call
+    cfg_pair again and give the result to a new DPM_Solver."""
+    _classifier_free("cfg_pair", model_fn)
+    if model_fn.unconditional_condition is None:
+        raise ValueError("cfg_pair: takes a classifier-free wrapper with an unconditional_condition")
+    if not torch.is_tensor(condition2):
+        raise ValueError("cfg_pair: condition2 must be a tensor like the wrapper's condition, got %s" % type(condition2).__name__)
+    if torch.is_tensor(model_fn.condition) and condition2.shape != model_fn.condition.shape:
+        raise ValueError("cfg_pair: condition2 has shape %s, the wrapper's condition %s"
+                         % (tuple(condition2.shape), tuple(model_fn.condition.shape)))
+    if isinstance(scale2, bool) or not isinstance(scale2, numbers.Real) or not math.isfinite(float(scale2)):
+        raise ValueError("cfg_pair: scale2 must be a finite real number, got %r" % (scale2,))
+    if not isinstance(nested, bool):
+        raise ValueError("cfg_pair: nested must be a bool, got %r" % (nested,))
+    s = model_fn.guidance_scale
+    if isinstance(s, bool) or not isinstance(s, numbers.Real) or not math.isfinite(float(s)):
+        raise ValueError("cfg_pair: the wrapper's guidance_scale must be a finite real number, got %r" % (s,))
+    for r in REMEDIES:
+        if getattr(model_fn, r.raw):
+            raise NotImplementedError("cfg_pair on top of %s: the two-condition stage kernel has no remedy (a follow-up)" % r.name)
+    s1, s2 = float(s), (float(scale2) - float(s) if nested else float(scale2))
+    out = copy.copy(model_fn)
+    out._c_in3 = None                                         # (the copy concatenates its own conditions)
+    out.guidance_pair = None if s2 == 0.0 else (condition2, s1, s2)
     return out
 
 

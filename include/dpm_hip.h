@@ -100,11 +100,15 @@ extern "C" {
    217 DPM_TABLE_ZSTAR (a flag on table_mode): CFG-Zero* stages in the table -- every qualifying DPM_F_CFG_ZSTAR request owns a
    row, a group of them is ONE stage_zstar_kernel_table launch, one workgroup per sample (see "Table mode"; no entry point
    added, no struct changed, rows and records as in version 215: the kind has no record section).
+   218 DPM_GUIDE_CFG2: guidance over TWO conditions -- three network outputs per evaluation (e0, e1 and g) blended in ONE stage
+   launch, eps = (n1 + s1 * (n0 - n1)) + s2 * (n2 - n1) with s1 = cfg_scale and s2 = cg_scale (InstructPix2Pix's image and text
+   scales, composable conditions): a streaming kernel of its own, stage_pair_kernel, one instantiation per dtype pair (see
+   DPM_GUIDE_CFG2; no entry point added, no struct changed).  The planner and dpm_coef_prologue[_f64] accept the value.
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 217
+#define DPM_HIP_VERSION 218
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -137,7 +141,35 @@ enum { DPM_SOLVER_DPMSOLVER = 0, DPM_SOLVER_TAYLOR = 1,           /* solver_type
 enum { DPM_METHOD_MULTISTEP = 0, DPM_METHOD_SINGLESTEP = 1, DPM_METHOD_SINGLESTEP_FIXED = 2 }; /* ref :1171,:1214 */
 enum { DPM_SKIP_TIME_UNIFORM = 0, DPM_SKIP_LOGSNR = 1, DPM_SKIP_TIME_QUADRATIC = 2 };          /* ref :468-478    */
 enum { DPM_MODEL_NOISE = 0, DPM_MODEL_X_START = 1, DPM_MODEL_V = 2, DPM_MODEL_SCORE = 3 };     /* ref :288-298    */
-enum { DPM_GUIDE_NONE = 0, DPM_GUIDE_CFG = 1, DPM_GUIDE_CLASSIFIER = 2 };                      /* ref :313-330    */
+enum { DPM_GUIDE_NONE = 0, DPM_GUIDE_CFG = 1, DPM_GUIDE_CLASSIFIER = 2,                       /* ref :313-330    */
+       DPM_GUIDE_CFG2 = 3 /* version 218: classifier-free guidance over TWO conditions, three network outputs per evaluation.
+                             Operands, all of the eps dtype and all following eps_stride (0 or P = n / batch only):
+                               e0 = the raw output under the first condition, e1 = the unconditional raw output,
+                               g  = the raw output under the second condition.
+                             Scalars: s1 = dpm_stage.cfg_scale, s2 = dpm_stage.cg_scale (the planner writes 0 there under this
+                             guidance; the caller overwrites it, as it does with phi under DPM_F_CFG_RESCALE).
+                             Arithmetic, fp32 on the exactly widened outputs, one rounding per operation, no fused multiply-add:
+                               n_k = noise prediction of the raw output o_k (x_start / v / score conversion of the stage's model
+                                     type on xe), k = 0, 1, 2
+                               d0 = n0 - n1;  d2 = n2 - n1;  eps = (n1 + s1 * d0) + s2 * d2
+                             then DPM_F_TO_X0, the update form (LIN1 .. DENOISE, DPM_F_BASE_HIST included), DPM_F_STORE_M and the
+                             stores as under any other guidance.  Nothing is rounded to the network's dtype, not even for a 2-byte
+                             noise-prediction network, and the model values are never half-precision tensors under it: every
+                             difference of two model values is an fp32 operation.  InstructPix2Pix's e_u + s_I (e_I - e_u) +
+                             s_T (e_IT - e_I) is e0 = e_IT, g = e_I, s1 = s_T, s2 = s_I - s_T; composable conditions e_u +
+                             s (e_c - e_u) + s' (e_c' - e_u) are s1 = s, s2 = s'.  With FP32 outputs the result is DPM_GUIDE_CFG's
+                             bit for bit when s2 == 0, and when g == e1 (d2 = 0, and adding s2 * 0 changes no bit).  With a
+                             2-byte noise-prediction network neither holds: DPM_GUIDE_CFG rounds its blend to that dtype, this
+                             guidance does not.
+                             DPM_ERR_ARG: e1 or g is NULL; s1 or s2 is not finite; one of DPM_F_CFG_RESCALE / _APG / _ZSTAR
+                             (they are valid under DPM_GUIDE_CFG only); an unknown form.
+                             DPM_ERR_UNSUPPORTED (this version): DPM_F_THRESH, DPM_F_BLEND, DPM_F_NOISE, DPM_F_USER_X0;
+                             DPM_FORM_UNIPC; a non-NULL x_out2; a double state; eps_stride other than 0 or P; device-resident
+                             coefficients.  No output byte is written in any error case.  One streaming kernel
+                             (stage_pair_kernel: 2048-element tiles, 16-byte accesses where n is a multiple of 8 and every
+                             operand is 16-byte aligned, else one element per lane); such a stage runs on its own in a
+                             multi-request launch, in every mode of dpm_stage_launch_multi.  dpm_plan_create and
+                             dpm_coef_prologue[_f64] treat the value as DPM_GUIDE_CFG for cfg_scale */ };
 enum { DPM_DTYPE_F32 = 0, DPM_DTYPE_F16 = 1, DPM_DTYPE_BF16 = 2,
        DPM_DTYPE_F64 = 3 /* state AND network output in double, double arithmetic: the reference run on x.double()
                             (ref :14, :105-107); one run-time dispatched kernel, not a performance path */ };
@@ -316,7 +348,8 @@ typedef struct dpm_stage {
   float alpha_e;       /* alpha(t_eval)                                                          */
   float sigma_e;       /* sigma(t_eval)                                                          */
   float cfg_scale;     /* guidance_scale as fp32 (ref :330)                                      */
-  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi; DPM_F_CFG_APG: eta */
+  float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi; DPM_F_CFG_APG: eta;
+                          DPM_GUIDE_CFG2: s2, the scale of the second condition (the planner writes 0)            */
   float cx, c0, c1, c2; /* update coefficients, reference association (see kernels)              */
   float k[5];          /* difference-quotient scalars: 1/r0, 1/r1, ...                           */
   float thr_ratio;     /* dynamic_thresholding_ratio;  DPM_F_CFG_APG: the norm threshold r       */
@@ -396,7 +429,8 @@ typedef struct dpm_buffers {
   const void* xe;   /* state the network saw (NULL = same as x)              [n] state dtype     */
   const void* e0;   /* raw network output (conditional half under CFG)       [n] eps dtype       */
   const void* e1;   /* raw unconditional output (CFG only)                   [n] eps dtype       */
-  const void* g;    /* classifier gradient (classifier guidance only)        [n] eps dtype       */
+  const void* g;    /* classifier gradient (classifier guidance); DPM_GUIDE_CFG2: the raw
+                       output under the second condition                   [n] eps dtype       */
   const void* h1;   /* cached model value                                    [n] state dtype     */
   const void* h2;   /* cached model value                                    [n] state dtype     */
   void* x_out;      /* result of the update                                  [n] state dtype     */
