@@ -59,12 +59,15 @@ TABLE_APG = 512                           # ... another: DPM_F_CFG_APG stages ta
                                           # average is dpm_buffers.thr_hint (version 215; bit 256 is unassigned)
 TABLE_ZSTAR = 4096                        # ... another: DPM_F_CFG_ZSTAR stages take rows too, no records (version 217; bits
                                           # 1024 and 2048 are unassigned)
+TABLE_PAIR = 16384                        # ... another: DPM_GUIDE_CFG2 stages take rows and pair records too, and the third copy
+                                          # of their x_out is dpm_buffers.thr_hint (version 219; bit 8192 is unassigned)
 THR_ROW_MAX = 12288                       # elements of the largest sample a thresholded row holds (THR_CHUNK_MAX, csrc)
 TABLE_MAGIC = 0x4c425444
 SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
 SIZEOF_TABLE_NOISE = 10                           # ... and of a noise record (9 is unassigned)
 SIZEOF_TABLE_BLEND = 12                           # ... and of a blend record (11 is unassigned)
 SIZEOF_TABLE_APG = 14                             # ... and of an APG record (13 is unassigned)
+SIZEOF_TABLE_PAIR = 18                            # ... and of a pair record (15, 16 and 17 are unassigned)
 THR_HINT_WORDS = 4
 
 
@@ -307,23 +310,25 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 218:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 218 -- stale library, rebuild"
+if lib.dpm_version() < 219:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 219 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16
 TABLE_NOISE_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_NOISE))        # (TABLE_NOISE) behind the rows, one noise record per row
 TABLE_BLEND_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_BLEND))        # (TABLE_BLEND) behind those, one blend record per row
 TABLE_APG_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_APG))            # (TABLE_APG) behind those, one APG record per row
+TABLE_PAIR_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_PAIR))          # (TABLE_PAIR) behind those, one pair record per row
 
 
 def table_bytes(n_req, flags=0):
     """The bytes of the table of a table-mode call of n_req requests whose table_mode carries `flags` (TABLE_NOISE / TABLE_THRESH /
-    TABLE_BLEND / TABLE_RESCALE / TABLE_APG / TABLE_ZSTAR; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
+    TABLE_BLEND / TABLE_RESCALE / TABLE_APG / TABLE_ZSTAR / TABLE_PAIR; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
     Not rounded."""
     return (TABLE_HEADER_BYTES + n_req * (TABLE_ROW_BYTES + (TABLE_NOISE_BYTES if flags & TABLE_NOISE else 0)
                                           + (TABLE_BLEND_BYTES if flags & TABLE_BLEND else 0)
-                                          + (TABLE_APG_BYTES if flags & TABLE_APG else 0)))
+                                          + (TABLE_APG_BYTES if flags & TABLE_APG else 0)
+                                          + (TABLE_PAIR_BYTES if flags & TABLE_PAIR else 0)))
 
 
 if IS_LAB and os.environ.get("DPM_LAB_TUNE"):

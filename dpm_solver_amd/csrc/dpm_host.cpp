@@ -51,6 +51,7 @@ extern "C" size_t dpm_sizeof(int which) {
     case DPM_SIZEOF_TABLE_NOISE: return DPM_TABLE_NOISE_BYTES;
     case DPM_SIZEOF_TABLE_BLEND: return DPM_TABLE_BLEND_BYTES;
     case DPM_SIZEOF_TABLE_APG: return DPM_TABLE_APG_BYTES;
+    case DPM_SIZEOF_TABLE_PAIR: return DPM_TABLE_PAIR_BYTES;
   }
   return 0;
 }

@@ -80,6 +80,10 @@ int dpm_table_launch_zstar(const dpm_stage* st, const dpm_buffers* bs, int n_req
 // (unit H) one stage under guidance over two conditions (DPM_GUIDE_CFG2, stage_pair_kernel): three network outputs, streaming
 template <typename TS, typename TE>
 int dpm_launch_pair(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+// (unit H, DPM_TABLE_PAIR) DPM_GUIDE_CFG2 rows and their pair records (DPM_TABLE_PAIR_BYTES each: KPairTab, dpm_table_kernel.hpp;
+// behind the APG records), one super-tile per 256-lane group as the plain rows
+template <typename TS, typename TE>
+int dpm_table_launch_pair(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -50,8 +50,10 @@ struct PairUnits {
   // the per-sample guidance stages (kSampleGuidance): unit E's guidance rescale, unit F's adaptive projected guidance, unit G's
   // CFG-Zero*
   SampleFn rescale, apg, zstar;
-  // unit H's stage under guidance over two conditions (DPM_GUIDE_CFG2): a streaming kernel of its own
+  // unit H's stage under guidance over two conditions (DPM_GUIDE_CFG2): a streaming kernel of its own, and its rows of the
+  // table (DPM_TABLE_PAIR)
   SampleFn pair;
+  TableLaunchFn table_launch_pair;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
@@ -59,7 +61,7 @@ struct PairUnits {
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
    dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>, dpm_table_launch_zstar<TS, TE>,         \
    dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
-   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>},
+   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>, dpm_table_launch_pair<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -167,8 +169,9 @@ int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dp
 
 // What dpm_stage_launch asks of a stage under guidance over two conditions (DPM_GUIDE_CFG2, include/dpm_hip.h) before anything
 // else of the record is read: its two scales, then what stage_pair_kernel has no path for (b->batch >= 1, n a multiple of it).
-// A remedy flag has been reported by check_sample_guidance ("valid under classifier-free guidance only").
-int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b) {
+// A remedy flag has been reported by check_sample_guidance ("valid under classifier-free guidance only").  `copies`: the call
+// carries DPM_TABLE_PAIR, where a row stores x_out2 and a third copy (check_pair_copies decides there).
+int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b, bool copies) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (!std::isfinite(st->cfg_scale) || !std::isfinite(st->cg_scale))
     return fail(DPM_ERR_ARG, "stage_launch: DPM_GUIDE_CFG2 with s1=%g (dpm_stage.cfg_scale), s2=%g (dpm_stage.cg_scale): both must be finite",
@@ -179,7 +182,7 @@ int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b) {
   if (st->form < DPM_FORM_LIN1 || st->form > DPM_FORM_UNIPC) return fail(DPM_ERR_ARG, "unknown update form %d", st->form);
   if (st->flags & (DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC))
     return fail(DPM_ERR_ARG, "stage_launch: DPM_F_UNIPC_* / DPM_F_STORE_XC are valid on DPM_FORM_UNIPC stages only (form %d)", st->form);
-  if (b->x_out2) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)");
+  if (b->x_out2 && !copies) return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)");
   if (b->state_dtype == DPM_DTYPE_F64 || b->eps_dtype == DPM_DTYPE_F64)
     return fail(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with a double state (no double kernel)");
   if (b->eps_stride != 0 && b->eps_stride != b->n / b->batch)
@@ -189,8 +192,10 @@ int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b) {
 
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
 // base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base);
-// apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace
-int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false, bool apg_hint = false) {
+// apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace;
+// pair_copies: it is a DPM_TABLE_PAIR one, where a DPM_GUIDE_CFG2 request may carry x_out2 (checked there, check_pair_copies)
+int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false, bool apg_hint = false,
+                        bool pair_copies = false) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
@@ -200,7 +205,7 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
   if (const SampleGuidance* g = sample_guidance(st->flags))
     if (const int rc = check_sample_guidance(*g, st, b, apg_hint)) return rc;
   if (st->guidance == DPM_GUIDE_CFG2)
-    if (const int rc = check_pair_guidance(st, b)) return rc;
+    if (const int rc = check_pair_guidance(st, b, pair_copies)) return rc;
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -385,11 +390,24 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
   return DPM_OK;
 }
 
+// The copies of one DPM_GUIDE_CFG2 request of a DPM_TABLE_PAIR call: x_out2 and the third copy, dpm_buffers.thr_hint, come
+// together, and only a request that will own a pair row (`row`) has a kernel that stores them -- the lone kernel's refusal
+// otherwise, before anything is written or launched
+int check_pair_copies(const dpm_stage& st, const dpm_buffers& b, bool row) {
+  if (st.guidance != DPM_GUIDE_CFG2 || b.n == 0) return DPM_OK;
+  if ((b.x_out2 != nullptr) != (b.thr_hint != nullptr))
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: DPM_GUIDE_CFG2 in a DPM_TABLE_PAIR call needs x_out2 and the third copy "
+                         "(dpm_buffers.thr_hint) both set or both null");
+  if (b.x_out2 && !row)
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)");
+  return DPM_OK;
+}
+
 // The table of a table-mode call (include/dpm_hip.h, "Table mode"): the header, n_req rows, then n_req noise records if and only
-// if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND), then n_req APG records (DPM_TABLE_APG) --
-// record i of every section beside row i.
+// if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND), then n_req APG records (DPM_TABLE_APG), then
+// n_req pair records (DPM_TABLE_PAIR) -- record i of every section beside row i.
 struct TableSections {
-  char *rows, *noise, *blend, *apg;
+  char *rows, *noise, *blend, *apg, *pair;
 };
 TableSections table_sections(void* table, int64_t n_req, int flags) {
   TableSections t;
@@ -397,6 +415,7 @@ TableSections table_sections(void* table, int64_t n_req, int flags) {
   t.noise = t.rows + n_req * (int64_t)DPM_TABLE_ROW_BYTES;
   t.blend = t.noise + ((flags & DPM_TABLE_NOISE) ? n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
   t.apg = t.blend + ((flags & DPM_TABLE_BLEND) ? n_req * (int64_t)DPM_TABLE_BLEND_BYTES : 0);
+  t.pair = t.apg + ((flags & DPM_TABLE_APG) ? n_req * (int64_t)DPM_TABLE_APG_BYTES : 0);
   return t;
 }
 
@@ -438,6 +457,12 @@ const RowKind kRowKinds[] = {
     // CFG-Zero* requests (DPM_F_CFG_ZSTAR; dpm_table_zstar.hpp), from ONE member on, for the same reason.  Any of LIN1 / TWO /
     // MS3 / DENOISE and any guidance scale in one group; the flag has no parameter and no state, so a row is all there is.
     {DPM_TABLE_ZSTAR, zstar_row_ok, nullptr, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_zstar},
+    // requests under guidance over two conditions (DPM_GUIDE_CFG2; dpm_table_pair.hpp), from ONE member on: the alternative is a
+    // launch per request.  A streaming kind, one workgroup per super-tile.  Any of LIN1 / TWO / MS3 / DENOISE, any two scales,
+    // rows with and without the copies in one group; the record carries the third output (g) and the third copy of x_out (the
+    // request's thr_hint in such a call).
+    {DPM_TABLE_PAIR, pair_row_ok, nullptr, false, false, 1, &TableSections::pair, DPM_TABLE_PAIR_BYTES, table_fill_pair,
+     &PairUnits::table_launch_pair},
     // every other fusable request, in every call: groups of 2..HET_MAX keep the kernarg records (stage_kernel_het needs no
     // dependent load in front of its tile's own), larger ones take the table.  An SDE group of a call without DPM_TABLE_NOISE
     // is gathered here too -- het_same_group keeps it apart from the ODE groups -- and owns no rows (stage_launch_multi_het).
@@ -484,16 +509,18 @@ int launch_alone(const dpm_stage* st, const dpm_buffers* b, int flags, void* str
 // one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
   const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
-                                  DPM_TABLE_ZSTAR);
-  const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0;
+                                  DPM_TABLE_ZSTAR | DPM_TABLE_PAIR);
+  const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0, pair_rows = (flags & DPM_TABLE_PAIR) != 0;
   table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
-    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0)) return rc;
+    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0, pair_rows)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;
   for (int r = 0; noise_rows && r < n_req; ++r)
     if (const int rc = check_noise_base(st[r], bs[r], owns_row(DPM_TABLE_NOISE, st[r], bs[r], flags, fuse))) return rc;
+  for (int r = 0; pair_rows && r < n_req; ++r)
+    if (const int rc = check_pair_copies(st[r], bs[r], owns_row(DPM_TABLE_PAIR, st[r], bs[r], flags, fuse))) return rc;
   const TableSections sec = table_mode ? table_sections(table, n_req, flags) : TableSections{};
   int64_t n_rows = 0;
   uint32_t n_runs = 0;
@@ -579,11 +606,11 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
   const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
-                                     DPM_TABLE_ZSTAR);
+                                     DPM_TABLE_ZSTAR | DPM_TABLE_PAIR);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
                          "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND / DPM_TABLE_RESCALE / DPM_TABLE_APG / "
-                         "DPM_TABLE_ZSTAR)",
+                         "DPM_TABLE_ZSTAR / DPM_TABLE_PAIR)",
                          o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");

@@ -255,6 +255,23 @@ inline bool zstar_row_ok(const dpm_stage& st, const dpm_buffers& b) {
   return buffers_aligned(b, 16, 16) && aligned(b.x_out2, 16);
 }
 
+// May a request under guidance over two conditions own a table row (DPM_TABLE_PAIR; stage_pair_kernel_table,
+// dpm_table_pair.hpp)?  What dpm_stage_launch asks of the guidance (check_pair_guidance: finite scales, no thresholding / blend /
+// noise / split stage, no UniPC form or flag, 2- and 4-byte dtypes, a dense network output) and what a row asks: form LIN1 / TWO /
+// MS3 / DENOISE, a plain request, n a positive multiple of 8 (the kernel takes the 16-byte accesses only), e0, e1, g and x_out
+// set, every buffer 16-byte aligned -- x_out2 and, in such a call, the third copy (thr_hint) too.  (Whether the two copies come
+// together is the call's check, check_pair_copies, not the row's.)
+inline bool pair_row_ok(const dpm_stage& st, const dpm_buffers& b) {
+  if (st.guidance != DPM_GUIDE_CFG2 || !std::isfinite(st.cfg_scale) || !std::isfinite(st.cg_scale)) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_USER_X0 | DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC |
+                  DPM_F_CFG_RESCALE | DPM_F_CFG_APG | DPM_F_CFG_ZSTAR))
+    return false;
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3 && st.form != DPM_FORM_DENOISE) return false;
+  if (b.state_dtype == DPM_DTYPE_F64 || b.eps_dtype == DPM_DTYPE_F64) return false;
+  if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b) || !b.e0 || !b.e1 || !b.g || !b.x_out) return false;
+  return buffers_aligned(b, 16, 16) && aligned(b.g, 16) && aligned(b.x_out2, 16) && aligned(b.thr_hint, 16);
+}
+
 // the generator's parameters of one request's SDE stage: the seed from the request's own dpm_launch_opts (none: seed 0),
 // the Philox counter word = the stage index, the scale = the stage's c2
 inline KNoise noise_of(const dpm_stage& st, const dpm_buffers& b) {

@@ -20,8 +20,8 @@
 //               includes) and of the table's CFG-Zero* rows (stage_zstar_kernel_table, DPM_TABLE_ZSTAR; dpm_table_zstar.hpp) and
 //               nothing else -- units A to F compile to the code they compiled to before it existed
 //   unit H (7): the launch of a stage under guidance over two conditions (stage_pair_kernel, DPM_GUIDE_CFG2; dpm_pair_kernel.hpp,
-//               which no other unit includes) and nothing else -- units A to G compile to the code they compiled to before it
-//               existed
+//               which no other unit includes) and of the table's two-condition rows (stage_pair_kernel_table, DPM_TABLE_PAIR;
+//               dpm_table_pair.hpp) and nothing else -- units A to G compile to the code they compiled to before it existed
 // Units E, F and G are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
@@ -48,6 +48,7 @@
 #endif
 #if DPM_UNIT == 7
 #include "dpm_pair_kernel.hpp"
+#include "dpm_table_pair.hpp"
 #endif
 
 #include <tuple>
@@ -186,4 +187,13 @@ int dpm_launch_pair(const dpm_stage* st, const dpm_buffers* b, void* stream, voi
   return launch_pair_typed<TS, TE>(st, b, s);
 }
 template int dpm_launch_pair<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
+#endif
+
+#if DPM_UNIT == 7
+template <typename TS, typename TE>
+int dpm_table_launch_pair(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_pair_typed<TS, TE>(st, bs, n_req, rows, recs, s);
+}
+template int dpm_table_launch_pair<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

@@ -235,6 +235,30 @@ inline void table_fill_apg(const dpm_stage* st, const dpm_buffers* bs, int n_req
   }
 }
 
+// ---- The pair record of a DPM_TABLE_PAIR call (include/dpm_hip.h, "Table mode"; read by stage_pair_kernel_table,
+// dpm_table_pair.hpp): what a DPM_GUIDE_CFG2 row needs beyond its row.  A row has 8 pointers; a two-condition stage reads a
+// third network output and, in a slab pool, writes a third copy of the result (the network's next input is three copies of the
+// state).  Both are declared in the global address space, as KApgTab's and KBlendTab's pointers are and for the reason given at
+// DPM_GLOBAL_PTR: a plain pointer loaded from the table would make every access through it a flat one.
+struct alignas(16) KPairTab {
+  const DPM_GLOBAL_PTR void* g;  // the output under the second condition (dpm_buffers.g)
+  DPM_GLOBAL_PTR void* xo3;      // the third copy of x_out (dpm_buffers.thr_hint in such a call), or null
+};
+static_assert(sizeof(KPairTab) == DPM_TABLE_PAIR_BYTES && alignof(KPairTab) == 16,
+              "include/dpm_hip.h publishes the pair record's size: two pointers");
+
+// ---- DPM_TABLE_FILL | DPM_TABLE_PAIR: the pair records of one group of two-condition rows, beside its rows (same order).  The
+// third copy of such a call is the request's thr_hint (checked by the caller: set exactly where x_out2 is).  Host memory, no
+// HIP call.
+inline void table_fill_pair(const dpm_stage*, const dpm_buffers* bs, int n_req, void* recs) {
+  KPairTab* out = static_cast<KPairTab*>(recs);
+  for (int r = 0; r < n_req; ++r) {
+    const void* const ptrs[2] = {bs[r].g, bs[r].thr_hint};
+    static_assert(sizeof ptrs == sizeof(KPairTab), "a pair record is its two pointers");
+    std::memcpy(&out[r], ptrs, sizeof ptrs);
+  }
+}
+
 // ---- DPM_TABLE_LAUNCH: the skeleton of the streaming table launchers (plain / UniPC, noise and blend rows; the thresholded
 // rows' launch has another shape, dpm_table_thresh.hpp).  The group's size against table_group_cap, the tuning, `row_ok(r)` for
 // every member -- the kind's own argument check: `bad_row` is its error --, the prologue every member allows, the het kernels'

@@ -146,6 +146,31 @@ epilogues); `submit_unipc` on a solver whose wrapper carries the setting; `zero_
 `zero_star=True` a slab pool refuses a `cfg_zero_star` solver as before.
 Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper has the request's
 guidance scale and `cfg_zero_star` (or not), for any b, whichever rows it landed in.
+
+`request_pool(slots=S, pair=True)` is the slab pool of a `dpm_solver_amd.cfg_pair` wrapper: guidance over two conditions
+(InstructPix2Pix's image and text scales, composable conditions).  The network's input is THREE copies of every state, so the
+state slabs are [3S, ...], the time vector has 3S entries and the condition slab is [3S, *cond_shape] in the wrapper's order --
+unconditional, condition, condition2 --: the one network call's output chunks as `e1, e0, e2 = out.chunk(3)`, exactly as
+`WrappedModel.raw_outputs` chunks it.  Admission writes x_T into all three thirds.  The tick's two calls carry DPM_TABLE_PAIR:
+every row is a DPM_GUIDE_CFG2 row of the table -- ONE stage_pair_kernel_table launch, the arithmetic of the request's own
+stage_pair_kernel launch -- with a pair record behind it: g = e2 + row, and the THIRD copy of x_out in dpm_buffers.thr_hint
+(x_out2 = xout + (S + row), thr_hint = xout + (2S + row); both zero on a request's last stage).  The kernel stores the result
+three times, so no tick runs a `torch.cat([x] * 3)`; a tick stays one network call, one copy and one launch.  The DENOISE stage
+of denoise_to_zero is a row too.  Per request: `submit(..., condition=, unconditional_condition=, condition2=,
+guidance_scale=s, pair=(scale2, nested))` -- s1 = fp32(s), s2 = scale2, or scale2 - s under nested=True, formed in double and
+rounded once: exactly `cfg_pair` and `_prep_stage`, with cfg_pair's range checks and texts.  Both scales are kept per row;
+every tick writes them over the gathered records (cfg_scale, cg_scale).  The defaults are the wrapper's own values.
+`guidance_scale=` without `pair=` is ValueError (the wrapper does not keep `nested`, so the second scale's meaning would be a
+guess); `guidance_scale=1.0` is fine here: a pair wrapper always evaluates three branches.  A request whose s2 comes out 0 is
+NotImplementedError: it would be plain two-branch guidance, which for half noise networks blends in half, and a row of a [3S]
+slab cannot reproduce those bits.  At its first submit such a pool refuses a sample of fewer than 8 elements, one whose
+element count is no multiple of 8, and one whose row is no multiple of 16 bytes.  Refused with NotImplementedError:
+`pair=True` with `sde`, `thresholding`, `inpaint`, `rescale`, `apg` or `zero_star`; `submit_unipc`; `submit(sde=True)`;
+`blend=`; `pair=` outside a `pair=True` pool.  `pair=True` on a solver whose wrapper is no `cfg_pair` one, and without
+`slots`, are ValueError.  Without `pair=True` a pool refuses a `cfg_pair` solver as before.
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper is
+`cfg_pair(model_wrapper(..., guidance_scale=s, condition=c, unconditional_condition=u), c2, scale2, nested)`, for any b,
+whichever rows it landed in.
 """
 import ctypes as C
 import math
@@ -195,6 +220,9 @@ _ROW = (
     # CFG-Zero* (see "CFG-Zero*" below)
     ("zon", np.bool_, False),    # does its request bring its own choice (submit's zero_star=)?
     ("zsel", np.bool_, False),   # its choice: the CFG-Zero* projection, or plain classifier-free guidance
+    # guidance over two conditions (see "guidance over two conditions" below)
+    ("ps1", np.float32, 0),      # its two scales: cfg_scale and cg_scale of its DPM_GUIDE_CFG2 records
+    ("ps2", np.float32, 0),
     # inpainting rows (see "inpainting requests" below)
     ("bslot", np.int64, -1),     # the first row of its inpainting request: where _brec holds its blend records (-1: none)
     ("bmask", np.uint64, 0),     # the mask of its sample
@@ -209,6 +237,7 @@ _ROW_CHECKS = (
     ("_rsc", 8, math.inf, "slab pool: rescale=True with a sample of %d elements -- a rescale row of the table is " + _GROUPS),
     ("_apg", 8, math.inf, "slab pool: apg=True with a sample of %d elements -- an APG row of the table is " + _GROUPS),
     ("_zst", 8, math.inf, "slab pool: zero_star=True with a sample of %d elements -- a CFG-Zero* row of the table is " + _GROUPS),
+    ("_pr", 8, math.inf, "slab pool: pair=True with a sample of %d elements -- a two-condition row of the table is " + _GROUPS),
     ("_thr", 0, L.THR_ROW_MAX, "slab pool: thresholding=True with a sample of %%d elements -- a thresholded row of the table is "
                                "at most %d elements (one workgroup's LDS), " % L.THR_ROW_MAX + _GROUPS),
 )
@@ -231,7 +260,7 @@ def _runs(rows):
 
 
 class _Waiting:
-    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide", "apg", "zstar")
+    __slots__ = ("h", "x", "plan", "cond", "uncond", "mf", "seed", "blend", "guide", "apg", "zstar", "cond2", "pair")
 
 
 class _Blend:
@@ -249,7 +278,7 @@ class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
     def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False, apg=False,
-                 zero_star=False):
+                 zero_star=False, pair=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
@@ -260,10 +289,11 @@ class SlabPool:
         self._rsc = bool(rescale)        # guidance-rescale requests admitted: the tick's calls carry DPM_TABLE_RESCALE
         self._apg = bool(apg)            # adaptive-projected-guidance requests admitted: the tick's calls carry DPM_TABLE_APG
         self._zst = bool(zero_star)      # CFG-Zero* requests admitted: the tick's calls carry DPM_TABLE_ZSTAR
+        self._pr = bool(pair)            # a cfg_pair solver's pool, slabs of [3S, ...]: the tick's calls carry DPM_TABLE_PAIR
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
                         | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
                         | (L.TABLE_RESCALE if self._rsc else 0) | (L.TABLE_APG if self._apg else 0)
-                        | (L.TABLE_ZSTAR if self._zst else 0))
+                        | (L.TABLE_ZSTAR if self._zst else 0) | (L.TABLE_PAIR if self._pr else 0))
         self._avg = None                 # (an apg=True pool) the running averages: one fp32 slab [S, *sample_shape]
         self._cols = []                  # the per-row arrays of _ROW (self._req, self._pos, ...), each with its idle value
         for name, dtype, idle in _ROW:
@@ -347,6 +377,37 @@ class SlabPool:
                                       "request_pool(slots=..., zero_star=True) only")
         return bool(on)
 
+    def _pair_params(self, scale, pair, cond2):
+        """the request's own (s1, s2) of submit's guidance_scale= / pair=, checked as cfg_pair checks them; None: the wrapper's"""
+        if not self._pr:
+            if pair is not None:
+                raise NotImplementedError("slab pool: pair= -- two-condition stages take the table in a pool built with "
+                                          "request_pool(slots=..., pair=True) only")
+            if cond2 is not None:
+                raise ValueError("slab pool: condition2= belongs to a pool built with request_pool(slots=..., pair=True)")
+            return None
+        if pair is None:
+            if scale is not None:
+                raise ValueError("slab pool: guidance_scale= in a pair=True pool needs pair=(scale2, nested) -- the wrapper does "
+                                 "not keep `nested`, so the second scale's meaning would be a guess")
+            return None
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("slab pool: pair= takes (scale2, nested), got %r" % (pair,))
+        scale2, nested = pair
+        if isinstance(scale2, bool) or not isinstance(scale2, numbers.Real) or not math.isfinite(float(scale2)):
+            raise ValueError("cfg_pair: scale2 must be a finite real number, got %r" % (scale2,))
+        if not isinstance(nested, (bool, np.bool_)):
+            raise ValueError("cfg_pair: nested must be a bool, got %r" % (nested,))
+        sc = self._s._wrapped.guidance_scale if scale is None else scale
+        if isinstance(sc, bool) or not isinstance(sc, numbers.Real) or not math.isfinite(float(sc)):
+            raise ValueError("cfg_pair: the wrapper's guidance_scale must be a finite real number, got %r" % (sc,))
+        s1, s2 = float(sc), (float(scale2) - float(sc) if nested else float(scale2))
+        if s2 == 0.0:
+            raise NotImplementedError("slab pool: pair=%r with guidance_scale=%r -- the second scale comes out 0, which is plain "
+                                      "two-branch guidance: for half noise networks that blends in half, and a row of a [3S] "
+                                      "slab cannot reproduce those bits" % (tuple(pair), sc))
+        return s1, s2
+
     def _guidance(self, scale, phi):
         """the request's own (guidance scale, phi) of submit's guidance_scale= / guidance_rescale=, checked; None: the wrapper's"""
         if scale is None and phi is None:
@@ -397,7 +458,7 @@ class SlabPool:
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
                condition=None, unconditional_condition=None, seed=None, generator=None, blend=None, guidance_scale=None,
-               guidance_rescale=None, apg=None, zero_star=None):
+               guidance_rescale=None, apg=None, zero_star=None, condition2=None, pair=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -417,9 +478,13 @@ class SlabPool:
         guidance itself.  Default: the wrapper's.
         `zero_star=True | False` (True: a pool built with zero_star=True): the request's own choice of the CFG-Zero*
         projection -- the result of `sample()` under `cfg_zero_star(model_fn)`, or under the bare wrapper.  Default: the
-        wrapper's."""
+        wrapper's.
+        `condition2=c2, guidance_scale=s, pair=(scale2, nested)` (a pool built with pair=True): the request's own second
+        condition and its own two scales -- the result of `sample()` under `cfg_pair(model_wrapper(..., guidance_scale=s),
+        c2, scale2, nested)`.  `guidance_scale=` needs `pair=` there; 1.0 is fine.  Default: the wrapper's."""
         s = self._s
-        guide = self._guidance(guidance_scale, guidance_rescale)
+        pair = self._pair_params(guidance_scale, pair, condition2)
+        guide = self._guidance(None if self._pr else guidance_scale, guidance_rescale)
         apg = self._apg_params(apg)
         zero_star = self._zstar_choice(zero_star)
         if blend is not None:
@@ -449,7 +514,8 @@ class SlabPool:
         with torch.no_grad():
             plan = s._sample_plan(x, steps, t_0, t_T, order, skip_type, 'multistep', lower_order_final, denoise_to_zero,
                                   solver_type, sde=bool(sde))
-        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide, apg, zero_star)
+        return self._enqueue(x, plan, condition, unconditional_condition, seed if sde else None, blend, guide, apg, zero_star,
+                             condition2, pair)
 
     def submit_unipc(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', variant='bh2',
                      corrector=True, lower_order_final=True, denoise_to_zero=False, return_intermediate=False,
@@ -478,24 +544,27 @@ class SlabPool:
                                   'dpmsolver', unipc=variant)
         return self._enqueue(x, plan, condition, unconditional_condition, guide=guide)
 
-    def _conditions(self, b, cond, uncond):
+    def _conditions(self, b, cond, uncond, cond2=None):
         """the request's condition tensors, checked against the wrapper's guidance kind (None where the network takes none)"""
         w = self._s._wrapped
         if w is None or w.guidance_type != "classifier-free":
             if cond is not None or uncond is not None:
                 raise ValueError("slab pool: `condition` / `unconditional_condition` belong to a classifier-free wrapper")
-            return None, None
-        cfg = w.effective_guidance == "classifier-free"
+            return None, None, None
+        cfg = w.effective_guidance == "classifier-free" or self._pr
         cond = w.condition if cond is None else cond
         uncond = (w.unconditional_condition if uncond is None else uncond) if cfg else None
-        for name, c in (("condition", cond), ("unconditional_condition", uncond)):
-            if c is None and (name == "condition" or cfg):
+        cond2 = (w.pair[0] if cond2 is None else cond2) if self._pr else None
+        for name, c in (("condition", cond), ("unconditional_condition", uncond), ("condition2", cond2)):
+            if c is None and (name == "condition" or (cfg and name != "condition2") or self._pr):
                 raise ValueError("slab pool: the request has no %s and the wrapper has none" % name)
             if c is not None and (not torch.is_tensor(c) or c.dim() < 1 or c.shape[0] not in (1, b)):
                 raise ValueError("slab pool: %s must be a tensor of leading dimension %d or 1" % (name, b))
         if uncond is not None and (uncond.shape[1:] != cond.shape[1:] or uncond.dtype != cond.dtype):
             raise ValueError("slab pool: condition and unconditional_condition differ in shape or dtype")
-        return cond, uncond
+        if cond2 is not None and (cond2.shape[1:] != cond.shape[1:] or cond2.dtype != cond.dtype):
+            raise ValueError("slab pool: condition and condition2 differ in shape or dtype")
+        return cond, uncond, cond2
 
     def _blend_of(self, mb, x, plan, sd):
         """the request's `_Blend`: everything a tick must not compute per request, once, in the state dtype and contiguous"""
@@ -545,11 +614,11 @@ class SlabPool:
         q.keep += list(ops.values())
         return q
 
-    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None, apg=None, zstar=None):
+    def _enqueue(self, x, plan, cond, uncond, seed=None, blend=None, guide=None, apg=None, zstar=None, cond2=None, pair=None):
         like, sd = self._check_state(x)
         if plan.slots > 3:
             raise NotImplementedError("slab pool: a plan with %d cached model values (the pool holds three)" % plan.slots)
-        cond, uncond = self._conditions(int(x.shape[0]), cond, uncond)
+        cond, uncond, cond2 = self._conditions(int(x.shape[0]), cond, uncond, cond2)
         if self._like is None:
             self._allocate(like, sd, cond)
         elif cond is not None and (tuple(cond.shape[1:]), cond.dtype) != (tuple(self._cslab.shape[1:]), self._cslab.dtype):
@@ -558,7 +627,7 @@ class SlabPool:
         q = _Waiting()
         q.h, q.x, q.plan, q.cond, q.uncond, q.mf, q.seed = self._next, x, plan, cond, uncond, DV._mf_of(x), seed
         q.blend = None if blend is None else self._blend_of(blend, x, plan, sd)
-        q.guide, q.apg, q.zstar = guide, apg, zstar
+        q.guide, q.apg, q.zstar, q.cond2, q.pair = guide, apg, zstar, cond2, pair
         self._next += 1
         self._wait.append(q)
         return q.h
@@ -572,7 +641,8 @@ class SlabPool:
         self._like, self._sd = like, sd
         w = s._wrapped
         self._cfg = w is not None and w.effective_guidance == "classifier-free"
-        self._nS = nS = 2 * S if self._cfg else S
+        self._copies = 3 if self._pr else 2 if self._cfg else 1     # copies of a state the network's input holds
+        self._nS = nS = self._copies * S
         self._per = per = int(np.prod(shape, dtype=np.int64)) if shape else 1
         self._rowb = per * _esize(sd)
         self._x = [torch.zeros((nS,) + shape, dtype=sd, device=dev) for _ in range(2)]
@@ -641,6 +711,8 @@ class SlabPool:
                 self._apg_admit(q, ra)
             if q.zstar is not None:
                 self._zstar_admit(q, ra)
+            if self._pr:
+                self._pair_admit(q, ra)
             if q.blend is not None:
                 self._blend_admit(q, rows, ra)
                 blends.append((rows, q.blend))
@@ -648,16 +720,19 @@ class SlabPool:
         return blends
 
     def _load_rows(self, q, rows):
-        """the request's x_T into its rows of the current state slab (both halves under guidance), its conditions into the
-        condition slab's: one copy per run of consecutive rows"""
+        """the request's x_T into its rows of the current state slab (both halves under guidance, all three thirds under
+        guidance over two conditions), its conditions into the condition slab's: one copy per run of consecutive rows"""
         S, cur = self.S, self._x[self._cur]
-        half = S if self._cfg else 0     # the condition slab's conditional half (the unconditional one comes first)
+        half = S if self._copies > 1 else 0   # the condition slab's conditional part (the unconditional one comes first)
         x = q.x.to(self._sd)
         k = 0
         for r0, cnt in _runs(rows):
             cur[r0:r0 + cnt].copy_(x[k:k + cnt])
-            if self._cfg:
-                cur[S + r0:S + r0 + cnt].copy_(x[k:k + cnt])
+            for part in range(1, self._copies):
+                cur[part * S + r0:part * S + r0 + cnt].copy_(x[k:k + cnt])
+            if q.cond2 is not None:
+                c2 = q.cond2.to(self._cslab.device)
+                self._cslab[2 * S + r0:2 * S + r0 + cnt].copy_(c2 if c2.shape[0] == 1 else c2[k:k + cnt])
             if q.cond is not None:
                 c = q.cond.to(self._cslab.device)
                 self._cslab[half + r0:half + r0 + cnt].copy_(c if c.shape[0] == 1 else c[k:k + cnt])
@@ -667,18 +742,22 @@ class SlabPool:
             k += cnt
 
     def _network(self, x, t):
-        """ONE call on the whole slab: the raw output(s) as (e0, e1), e1 the unconditional half under guidance"""
+        """ONE call on the whole slab: the raw output(s) as (e0, e1, e2), e1 the unconditional part under guidance, e2 the
+        part under the second condition of a pair=True pool (WrappedModel.raw_outputs' order)"""
         s = self._s
         w = s._wrapped
         if w is None:
-            return s._model_fn(x, t), None
+            return s._model_fn(x, t), None, None
         if w.guidance_type != "classifier-free":
-            return w.model(x, t, **w.model_kwargs), None
+            return w.model(x, t, **w.model_kwargs), None, None
         out = w.model(x, t, self._cslab, **w.model_kwargs)
+        if self._pr:
+            e1, e0, e2 = out.chunk(3)
+            return e0, e1, e2
         if not self._cfg:
-            return out, None
+            return out, None, None
         e1, e0 = out.chunk(2)
-        return e0, e1
+        return e0, e1, None
 
     def _times_of(self, rows, idx):
         """the [S] (or [2S]) model-time vector of a tick whose active `rows` stand at the records `idx`; idle rows take the
@@ -687,8 +766,8 @@ class SlabPool:
         ta = self._recs[self._t_attr][idx]
         t[:] = ta[0] if len(ta) else 0.
         t[rows] = ta
-        if self._cfg:
-            t[self.S + rows] = ta
+        for part in range(1, self._copies):
+            t[part * self.S + rows] = ta
         return t
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -779,6 +858,21 @@ class SlabPool:
         st["flags"] = np.where(on, np.where(self._zsel[rows], st["flags"] | z, st["flags"] & ~z), st["flags"])
 
     # ------------------------------------------------------------------------------------------------------------------
+    # guidance over two conditions (a pair=True pool).  Row fields: ps1, ps2.  Checked at submit: _pair_params.  Nothing else is
+    # kept by the pool: the kind has no state; its third output and third copy are pointers of the tick (_buffer_records).
+    # ------------------------------------------------------------------------------------------------------------------
+    def _pair_admit(self, q, ra):
+        """the request's own two scales, or the wrapper's"""
+        self._ps1[ra], self._ps2[ra] = q.pair if q.pair is not None else self._s._pair_setting()
+
+    def _pair_tick(self, st, rows, rec):
+        """every row's two scales over the gathered records, as the planner (cfg_scale = s1) and _prep_stage (cg_scale = s2)
+        write them for a wrapper of the row's scales"""
+        on = rec["guidance"] == L.GUIDE["classifier-free-2"]
+        st["cfg_scale"] = np.where(on, self._ps1[rows], rec["cfg_scale"])
+        st["cg_scale"] = np.where(on, self._ps2[rows], rec["cg_scale"])
+
+    # ------------------------------------------------------------------------------------------------------------------
     # inpainting requests.  Row fields: bslot, bmask, bper (and samp).  Kept per request: _blends (built at submit: _blend_of)
     # and its records in _brec.
     # ------------------------------------------------------------------------------------------------------------------
@@ -858,7 +952,7 @@ class SlabPool:
             rec = self._recs[idx]
             last = self._pos[rows] + 1 == self._len[rows]
             xin, xout = self._x[self._cur], self._x[1 - self._cur]
-            e0, e1, ed = self._bind(*self._network(xin if self._cfg else xin[:self.S], self._tick_times(g, rows, idx)))
+            e0, e1, e2, ed = self._bind(*self._network(xin if self._copies > 1 else xin[:self.S], self._tick_times(g, rows, idx)))
             if admitted:
                 with DV._on_device(idx_dev, other):
                     self._blend_first(admitted, xin, stream)
@@ -871,7 +965,9 @@ class SlabPool:
                 self._apg_tick(st, rows, rec)
             if self._zst:
                 self._zstar_tick(st, rows, rec)
-            self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed)
+            if self._pr:
+                self._pair_tick(st, rows, rec)
+            self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed, e2)
             if self._apg:
                 self._apg_buffers(st, b, rows)
             self._call_opts(b)
@@ -887,7 +983,7 @@ class SlabPool:
                 rc = self._fill_copy_launch(g, b, R, stream)
             if rc:
                 L.check(rc)
-            del e0, e1
+            del e0, e1, e2
             self._t_next, self._t_dev = t_next, g.dev[self._tabb:self._copyb].view(torch.float32)
             self._cur = 1 - self._cur
             self._pos[rows] += 1
@@ -905,7 +1001,7 @@ class SlabPool:
         self.copies += 1
         return g.devt.view(torch.float32)
 
-    def _bind(self, e0, e1):
+    def _bind(self, e0, e1, e2=None):
         """the network's output as dense slabs of a dtype the kernels pair with the state's (launch_list._bind_outputs)"""
         sd = self._sd
         want = (self.S,) + self._like[0]
@@ -919,9 +1015,10 @@ class SlabPool:
             ed = sd
         e0 = DV._conv(e0, ed)
         e1 = DV._conv(e1, ed)
-        return e0, e1, ed
+        e2 = DV._conv(e2, ed)
+        return e0, e1, e2, ed
 
-    def _buffer_records(self, g, b, rows, rec, last, xin, xout, e0, e1, ed):
+    def _buffer_records(self, g, b, rows, rec, last, xin, xout, e0, e1, ed, e2=None):
         """the rows' dpm_buffers, zeroed and filled: every pointer is base + row * stride, a history slot the record names"""
         g.bufs_raw[:len(rows) * _BUFS.itemsize] = 0
         rb = rows.astype(np.uint64) * np.uint64(self._rowb)
@@ -931,6 +1028,11 @@ class SlabPool:
         if self._cfg:
             b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + self.S * self._rowb) + rb)
             b["e1"] = np.uint64(e1.data_ptr()) + eb
+        if self._pr:                     # the third output, and the other two thirds of the network's next input
+            b["e1"] = np.uint64(e1.data_ptr()) + eb
+            b["g"] = np.uint64(e2.data_ptr()) + eb
+            b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + self.S * self._rowb) + rb)
+            b["thr_hint"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + 2 * self.S * self._rowb) + rb)
         b["e0"] = np.uint64(e0.data_ptr()) + eb
         for name, slot, used in (("h1", rec["h1_slot"], rec["h1_slot"] >= 0), ("h2", rec["h2_slot"], rec["h2_slot"] >= 0),
                                  ("m_out", rec["m_slot"], (rec["flags"] & L.F_STORE_M) != 0)):

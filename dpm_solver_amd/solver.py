@@ -780,7 +780,7 @@ class DPM_Solver:
 
 
     def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False,
-                     apg=False, zero_star=False):
+                     apg=False, zero_star=False, pair=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -812,6 +812,12 @@ class DPM_Solver:
         table-driven launch too (DPM_TABLE_ZSTAR: one stage_zstar_kernel_table launch, one workgroup per row; no record, no
         state); samples of whole 8-element groups.  Not together with rescale / apg / sde / thresholding / inpaint (the
         CFG-Zero* kernel has none of those epilogues); without the flag a slab pool refuses a `cfg_zero_star` solver.
+        `slots=S, pair=True`: the slab pool of a `cfg_pair` wrapper (guidance over two conditions): slabs of [3S, ...] in the
+        wrapper's order (unconditional, condition, condition2), every request with its own conditions and two scales
+        (`submit(x, ..., condition2=c2, guidance_scale=s, pair=(scale2, nested))`), their stages in the table-driven launch
+        (DPM_TABLE_PAIR: one stage_pair_kernel_table launch that stores the result three times -- no `torch.cat([x] * 3)`);
+        samples of whole 8-element groups.  Not together with sde / thresholding / inpaint / rescale / apg / zero_star;
+        without the flag a pool refuses a `cfg_pair` solver.
         Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
@@ -824,8 +830,23 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
-        self._check_pair("request_pool -- a pool's ticks are fused and table-driven launches, and a two-condition stage runs on its "
-                         "own in those (sample_requests takes such a solver; a pool is a follow-up)")
+        if pair:
+            if slots is None:
+                raise ValueError("request_pool: pair=True belongs to a slab pool (slots=...)")
+            if self._pair_setting() is None:
+                raise ValueError("request_pool: pair=True needs a cfg_pair wrapper (guidance over two conditions with a second "
+                                 "scale other than 0)")
+            for name, why in (("sde", "no noise epilogue"), ("thresholding", "no thresholding"),
+                              ("inpaint", "no mask-blend epilogue"), ("rescale", "no guidance rescale"),
+                              ("apg", "no projected guidance"), ("zero_star", "no CFG-Zero* projection")):
+                if dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg, zero_star=zero_star)[name]:
+                    raise NotImplementedError("request_pool: pair=True with %s=True -- the two-condition kernel has %s (a "
+                                              "follow-up)" % (name, why))
+            self._check_pair()
+        else:
+            self._check_pair("request_pool -- a pool's ticks are fused and table-driven launches, and a two-condition stage runs "
+                             "on its own in those (sample_requests takes such a solver; request_pool(slots=..., pair=True) is its "
+                             "slab pool)")
         on = dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg, zero_star=zero_star)
         _rem.check_switches(self, slots, on)
         if thresholding and not self._thresholding:
@@ -837,7 +858,7 @@ class DPM_Solver:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
             return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg,
-                                  zero_star=zero_star)
+                                  zero_star=zero_star, pair=pair)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

@@ -104,11 +104,15 @@ extern "C" {
    launch, eps = (n1 + s1 * (n0 - n1)) + s2 * (n2 - n1) with s1 = cfg_scale and s2 = cg_scale (InstructPix2Pix's image and text
    scales, composable conditions): a streaming kernel of its own, stage_pair_kernel, one instantiation per dtype pair (see
    DPM_GUIDE_CFG2; no entry point added, no struct changed).  The planner and dpm_coef_prologue[_f64] accept the value.
+   219 DPM_TABLE_PAIR (a flag on table_mode), DPM_TABLE_PAIR_BYTES / DPM_SIZEOF_TABLE_PAIR: two-condition stages in the table --
+   every qualifying DPM_GUIDE_CFG2 request owns a row and a pair record behind the rows (the third network output, the third
+   copy of x_out), a group of them is ONE stage_pair_kernel_table launch; in such a call a DPM_GUIDE_CFG2 request may carry
+   x_out2, with the THIRD copy of x_out in dpm_buffers.thr_hint (see "Table mode"; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 218
+#define DPM_HIP_VERSION 219
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -418,10 +422,17 @@ enum { DPM_TABLE_ZSTAR = 4096 }; /* version 217: a flag OR-ed onto DPM_TABLE_FIL
                                     the lowest free bit: 16, 64, 256 and 1024 are unassigned, and so is 2048 -- table_mode 2048 |
                                     513 is pinned as DPM_ERR_ARG since version 215.  Every mode with one of the bits 16, 64, 256,
                                     1024, 2048, or a bit from 8192 on, stays DPM_ERR_ARG.) */
+enum { DPM_TABLE_PAIR = 16384 }; /* version 219: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the six
+                                    flags above: DPM_GUIDE_CFG2 stages take rows too, each with a pair record behind the rows,
+                                    and a DPM_GUIDE_CFG2 request of the call may carry x_out2 together with a third copy of x_out
+                                    in its dpm_buffers.thr_hint.  (Bit 8192 is unassigned -- table_mode 8192 | 1 is pinned as
+                                    DPM_ERR_ARG since version 217.  Every mode with one of the bits 16, 64, 256, 1024, 2048,
+                                    8192, or a bit from 32768 on, stays DPM_ERR_ARG.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 #define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
 #define DPM_TABLE_APG_BYTES 32      /* one APG record (= dpm_sizeof(DPM_SIZEOF_TABLE_APG)) */
+#define DPM_TABLE_PAIR_BYTES 16     /* one pair record (= dpm_sizeof(DPM_SIZEOF_TABLE_PAIR)) */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -473,7 +484,10 @@ typedef struct dpm_buffers {
                           DPM_F_CFG_APG with a momentum in a call that carries DPM_TABLE_APG (version 215; the flag excludes
                           DPM_F_THRESH, so no APG stage reads a hint): the RUNNING AVERAGE, n fp32 values in the state's flat
                           order, read and written in place -- private state that persists over one trajectory, as the hint
-                          is; the caller zero-fills it where a trajectory starts.  NULL with beta != 0: DPM_ERR_ARG      */
+                          is; the caller zero-fills it where a trajectory starts.  NULL with beta != 0: DPM_ERR_ARG.
+                          DPM_GUIDE_CFG2 in a call that carries DPM_TABLE_PAIR (version 219; the guidance excludes DPM_F_THRESH,
+                          so no such stage reads a hint): the THIRD copy of x_out, n values of the STATE dtype, written where
+                          x_out2 is -- both NULL or both set, else DPM_ERR_ARG                                            */
   const dpm_launch_opts* opts; /* per-call options, NULL = defaults (version 200; dpm_stage_launch_multi reads bs[0].opts) */
   const dpm_stage_f64* coef64; /* DPM_DTYPE_F64 launches: the stage's scalars in double (NULL: the dpm_stage's floats, exactly) */
 } dpm_buffers;
@@ -632,7 +646,7 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
                        group and every request that fits no group goes exactly as in mode 0.  The library copies nothing,
                        allocates nothing and synchronises nothing.
    SDE stages (without DPM_TABLE_NOISE), mixed n (fuse_shapes), thresholding (without DPM_TABLE_THRESH), mask blend (without
-   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE), DPM_F_CFG_APG (without DPM_TABLE_APG) and DPM_F_CFG_ZSTAR (without DPM_TABLE_ZSTAR) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
+   DPM_TABLE_BLEND), classifier guidance, DPM_F_STORE_XC, DPM_F_CFG_RESCALE (without DPM_TABLE_RESCALE), DPM_F_CFG_APG (without DPM_TABLE_APG), DPM_F_CFG_ZSTAR (without DPM_TABLE_ZSTAR) and DPM_GUIDE_CFG2 (without DPM_TABLE_PAIR) are outside the table kernels: in a table call such requests take exactly the path they take in mode 0.
    Every request gets the bits of its own dpm_stage_launch.
    SDE rows (version 209): DPM_TABLE_FILL | DPM_TABLE_NOISE and DPM_TABLE_LAUNCH | DPM_TABLE_NOISE (table_mode 5 / 6) make the
    same tick with SDE stages in the table (stage_kernel_table_noise).  EVERY fusable DPM_F_NOISE request -- the rules above,
@@ -763,10 +777,43 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
    DPM_F_CFG_ZSTAR request that does not qualify (a sample of 12 elements, a misaligned buffer, a separate evaluation state ...)
    goes, in the same call, as its own dpm_stage_launch, which projects too: the same bits, one more launch.  Without the flag
    every call is version 216's.  Every sample gets the bits of its request's own dpm_stage_launch.
+   Two-condition rows (version 219): DPM_TABLE_PAIR OR-ed onto either mode, alone or with any of the six flags above, makes the
+   same tick with stages under guidance over two conditions (DPM_GUIDE_CFG2) in the table (stage_pair_kernel_table: the
+   arithmetic of the request's own stage_pair_kernel launch on 16-byte accesses, in the plain table family's launch shape -- one
+   super-tile per 256-lane group, no loop, the XCD-contiguous remap --, pointers and stage scalars read from the row, the third
+   output and the third copy from its pair record).  A DPM_GUIDE_CFG2 request owns a row when dpm_stage_launch accepts the
+   guidance on it -- finite s1 and s2, no DPM_F_THRESH / DPM_F_BLEND / DPM_F_NOISE / DPM_F_USER_X0, no DPM_FORM_UNIPC and none
+   of its flags, a 2- or 4-byte dtype pair, a dense network output -- and its form is LIN1, TWO, MS3 or DPM_FORM_DENOISE, its
+   evaluation state is its state, n is a positive multiple of 8, e0, e1, g and x_out are set, and every buffer -- x_out2 and the
+   third copy included -- is 16-byte aligned.  Such requests form groups of their own that agree on dtypes, n, batch, model type,
+   guidance kind and DPM_F_TO_X0; the four forms, both scales, DPM_F_STORE_M and rows with and without the copies share a group:
+   each is the row's own.  Every group, from ONE member on, is one run of rows and ONE launch, the runs in the order the groups
+   open, among those of the other families.
+   The copies: in a call that carries DPM_TABLE_PAIR -- FILL or LAUNCH -- a DPM_GUIDE_CFG2 request may carry x_out2, the second
+   copy of x_out, and then carries the THIRD copy in dpm_buffers.thr_hint (n values of the state dtype; the guidance excludes
+   DPM_F_THRESH, so such a stage reads no hint): the network's next input is three copies of the state.  One of the two
+   without the other is DPM_ERR_ARG ("stage_launch_multi: DPM_GUIDE_CFG2 in a DPM_TABLE_PAIR call needs x_out2 and the third
+   copy (dpm_buffers.thr_hint) both set or both null").  A DPM_GUIDE_CFG2 request that carries them and owns no row
+   (misaligned, n no multiple of 8, multi_fuse off ...) is DPM_ERR_UNSUPPORTED with the text of version 218 ("stage_launch:
+   DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)"): every request is checked before anything is written or
+   launched.  A DPM_GUIDE_CFG2 request without copies that owns no row goes, in the same call, as its own dpm_stage_launch.
+   The pair records follow the rows and the noise, blend and APG records of the flags present; record i (counted over all runs)
+   is the DPM_TABLE_PAIR_BYTES bytes at
+     dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * dpm_sizeof(DPM_SIZEOF_TABLE_ROW)
+       + (DPM_TABLE_NOISE ? n_req * DPM_TABLE_NOISE_BYTES : 0) + (DPM_TABLE_BLEND ? n_req * DPM_TABLE_BLEND_BYTES : 0)
+       + (DPM_TABLE_APG ? n_req * DPM_TABLE_APG_BYTES : 0)
+       + DPM_TABLE_PAIR_BYTES * i
+   and the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + [DPM_TABLE_NOISE_BYTES] +
+   [DPM_TABLE_BLEND_BYTES] + [DPM_TABLE_APG_BYTES] + [DPM_TABLE_PAIR_BYTES]) bytes.  A record is two device pointers: g of the
+   request's dpm_buffers, then its thr_hint (NULL: no copies).  The row is a row like any other: 8 pointers (x_out2 the eighth)
+   and the 20 words of stage scalars, s1 in cfg_scale, s2 in cg_scale.  FILL leaves the pair-record slots of rows of other kinds
+   untouched.  Without the flag every call is version 218's: x_out2 on a DPM_GUIDE_CFG2 request is refused, thr_hint is not
+   read, and such a request owns no row.  Every element gets the bits of its request's own dpm_stage_launch.
    Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND,
-   DPM_TABLE_RESCALE, DPM_TABLE_APG, DPM_TABLE_ZSTAR: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46, each of those
-   plus 128, each of all these plus 512 -- the 64 modes of version 215 --, and each of those 64 plus 4096; bits 16, 64, 256,
-   1024 and 2048 are unassigned), a non-zero one without per_request_stages, or with fuse_shapes == 1:
+   DPM_TABLE_RESCALE, DPM_TABLE_APG, DPM_TABLE_ZSTAR, DPM_TABLE_PAIR: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46,
+   each of those plus 128, each of all these plus 512 -- the 64 modes of version 215 --, each of those 64 plus 4096 -- the 128
+   modes of version 217 --, and each of those 128 plus 16384; bits 16, 64, 256, 1024, 2048 and 8192 are unassigned), a non-zero
+   one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
 DPM_API int dpm_stage_launch_multi(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream);
@@ -911,7 +958,9 @@ enum { DPM_SIZEOF_STAGE = 0, DPM_SIZEOF_BUFFERS = 1, DPM_SIZEOF_PLAN_DESC = 2, D
        DPM_SIZEOF_TABLE_HEADER = 7, DPM_SIZEOF_TABLE_ROW = 8 /* version 208: the table of dpm_launch_opts.table_mode */,
        DPM_SIZEOF_TABLE_NOISE = 10 /* version 209: a noise record of a DPM_TABLE_NOISE table (9 is unassigned: 0) */,
        DPM_SIZEOF_TABLE_BLEND = 12 /* version 211: a blend record of a DPM_TABLE_BLEND table (11 is unassigned: 0) */,
-       DPM_SIZEOF_TABLE_APG = 14 /* version 215: an APG record of a DPM_TABLE_APG table (13 is unassigned: 0) */ };
+       DPM_SIZEOF_TABLE_APG = 14 /* version 215: an APG record of a DPM_TABLE_APG table (13 is unassigned: 0) */,
+       DPM_SIZEOF_TABLE_PAIR = 18 /* version 219: a pair record of a DPM_TABLE_PAIR table (15, 16 and 17 are unassigned: 0 --
+                                     the CFG-Zero* rows of version 217 have no record, and 16 is pinned as 0 since then) */ };
 DPM_API size_t dpm_sizeof(int which);
 DPM_API const char* dpm_last_error(void); /* thread-local text of the last non-zero return */
 DPM_API int dpm_device_info(int* n_cu, int* lds_bytes, char* arch, int arch_len);
