@@ -41,6 +41,7 @@ F_UNIPC_DP, F_UNIPC_P2, F_STORE_XC = 128, 256, 512
 F_CFG_RESCALE = 1024                      # guidance rescale under classifier-free guidance; dpm_stage.cg_scale carries phi (version 212)
 F_CFG_APG = 2048                          # adaptive projected guidance; cg_scale / thr_ratio / thr_max carry eta / r / beta (version 214)
 F_CFG_ZSTAR = 4096                        # CFG-Zero*: the unconditional output scaled by its per-sample fit; no field of its own (version 216)
+F_CFG2_PERP = 8192                        # Perp-Neg under DPM_GUIDE_CFG2: cfg_scale / cg_scale carry the guidance / negative scale (version 220)
 SRC_STATE, SRC_TMP = 0, 1
 # knobs of the LAB build (include/dpm_lab.h: dpm_tuning_set / dpm_tuning_get; the product library has none)
 TUNE_UNROLL, TUNE_NONTEMPORAL, TUNE_BLOCKS_PER_CU, TUNE_ASSUME_RESIDENT = 0, 1, 2, 3
@@ -48,7 +49,7 @@ TUNE_MULTI_FUSE, TUNE_MULTI_BLOCKS_PER_CU, TUNE_CLUSTER_IN_GRAPH, TUNE_CLUSTER_O
 TUNE_MULTI_XCD_REMAP = 8
 TUNE_THR_PREDICT = 9
 TUNE_THR_SPIN_LIMIT, TUNE_THR_DEBUG_FAULT, TUNE_BLOCK_THREADS = 10, 11, 12
-TUNE_FORCE_GENERIC, TUNE_THR_ELECT, TUNE_LDS_DMA, TUNE_THR_STAGGER, TUNE_BIG_TILES = 13, 14, 15, 16, 17
+TUNE_FORCE_GENERIC, TUNE_THR_ELECT, TUNE_LDS_DMA, TUNE_THR_STAGGER, TUNE_BIG_TILES, TUNE_PERP_REREAD = 13, 14, 15, 16, 17, 18
 MULTI_MAX = 32
 TABLE_FILL, TABLE_LAUNCH = 1, 2           # dpm_launch_opts.table_mode (version 208)
 TABLE_NOISE = 4                           # ... a flag on either: SDE stages take rows and noise records too (version 209)
@@ -310,8 +311,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 219:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 219 -- stale library, rebuild"
+if lib.dpm_version() < 220:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 220 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16

@@ -75,6 +75,8 @@ struct Tuning {
                             // launch shape (one workgroup per super-tile, no grid-stride loop, XCD-contiguous tiles for 2-byte
                             // states): dpm_stage_launch hands it to the multi-request launcher as a group of one; 0 = never
   int lds_dma = -1;         // lone-launch north-star kernels: read streams by LDS-DMA (1) / through registers (0); -1 = default
+  int perp_reread = -1;     // LAB: the Perp-Neg kernel's register path re-reads the third output from L2 (1) / parks its difference
+                            // in LDS (0); -1 = the shipped one (dpm_perp_kernel.hpp: PERP_PARK)
   int force_generic = 0;    // LAB: take the run-time-prologue kernels (SPEC_GENERIC / HOT 3) where a compile-time one exists (A/B)
   int thr_elect = -1;       // clustered thresholding: one elected reducer per sample (1) / every workgroup reads every slot (0)
   int thr_stagger = 0;      // LAB: start offset between thresholding clusters (ThrParams.stagger)

@@ -21,7 +21,7 @@
 // slowest unit), split by update form (bit f = form f).  Unit A also holds the fused multi-request launcher and the
 // pair's catch-all kernels, unit B the heterogeneous fused launchers, unit C (2) the table-driven ones, unit D (3) the
 // table-driven launch's mask-blend rows, unit E (4) the guidance-rescale stage, unit F (5) the adaptive-projected-guidance stage,
-// unit G (6) the CFG-Zero* stage, unit H (7) the stage under guidance over two conditions.
+// unit G (6) the CFG-Zero* stage, unit H (7) the stage under guidance over two conditions, unit I (8) the Perp-Neg stage.
 constexpr unsigned FORMS_A = (1u << DPM_FORM_TWO) | (1u << DPM_FORM_SS3T);
 constexpr unsigned FORMS_B = (1u << DPM_FORM_LIN1) | (1u << DPM_FORM_MS3) | (1u << DPM_FORM_DENOISE) | (1u << DPM_FORM_UNIPC);
 
@@ -84,6 +84,10 @@ int dpm_launch_pair(const dpm_stage* st, const dpm_buffers* b, void* stream, voi
 // behind the APG records), one super-tile per 256-lane group as the plain rows
 template <typename TS, typename TE>
 int dpm_table_launch_pair(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
+// (unit I) one Perp-Neg stage (DPM_F_CFG2_PERP under DPM_GUIDE_CFG2, stage_perp_kernel): three network outputs, one workgroup
+// per sample
+template <typename TS, typename TE>
+int dpm_launch_perp(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -54,6 +54,8 @@ struct PairUnits {
   // table (DPM_TABLE_PAIR)
   SampleFn pair;
   TableLaunchFn table_launch_pair;
+  // unit I's Perp-Neg stage (DPM_F_CFG2_PERP under DPM_GUIDE_CFG2): one workgroup per sample, three network outputs
+  SampleFn perp;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
@@ -61,7 +63,8 @@ struct PairUnits {
    dpm_table_launch_noise<TS, TE>, dpm_table_launch_thresh<TS, TE>, dpm_table_launch_blend<TS, TE>,       \
    dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>, dpm_table_launch_zstar<TS, TE>,         \
    dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
-   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>, dpm_table_launch_pair<TS, TE>},
+   dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>, dpm_table_launch_pair<TS, TE>,  \
+   dpm_launch_perp<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -190,12 +193,26 @@ int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b, bool copies) 
   return DPM_OK;
 }
 
+// What dpm_stage_launch asks of DPM_F_CFG2_PERP (include/dpm_hip.h), behind the remedy flags' checks and behind
+// check_pair_guidance: a record that is refused without the flag is refused by the same line with it.  `table`: the call is a
+// table-mode one (DPM_TABLE_PAIR rows have no per-sample pass).
+int check_perp_flag(const dpm_stage* st, const dpm_buffers* b, bool table) {
+  if (st->guidance != DPM_GUIDE_CFG2)
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG2_PERP is valid under DPM_GUIDE_CFG2 only (guidance %d)", st->guidance);
+  if (table)
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch_multi: DPM_F_CFG2_PERP in a table-mode call (the table's rows have no per-sample pass)");
+  if (b->batch > (int64_t)0x7fffffff)
+    return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_F_CFG2_PERP with a batch of %lld (one workgroup per sample)", (long long)b->batch);
+  return DPM_OK;
+}
+
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
 // base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base);
 // apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace;
-// pair_copies: it is a DPM_TABLE_PAIR one, where a DPM_GUIDE_CFG2 request may carry x_out2 (checked there, check_pair_copies)
+// pair_copies: it is a DPM_TABLE_PAIR one, where a DPM_GUIDE_CFG2 request may carry x_out2 (checked there, check_pair_copies);
+// table: it is a table-mode one, which takes no DPM_F_CFG2_PERP request
 int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false, bool apg_hint = false,
-                        bool pair_copies = false) {
+                        bool pair_copies = false, bool table = false) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (b->n < 0 || b->batch < 1 || (b->n % b->batch) != 0)
     return fail(DPM_ERR_ARG, "stage_launch: n=%lld is not a multiple of batch=%lld", (long long)b->n, (long long)b->batch);
@@ -206,6 +223,8 @@ int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok 
     if (const int rc = check_sample_guidance(*g, st, b, apg_hint)) return rc;
   if (st->guidance == DPM_GUIDE_CFG2)
     if (const int rc = check_pair_guidance(st, b, pair_copies)) return rc;
+  if (st->flags & DPM_F_CFG2_PERP)
+    if (const int rc = check_perp_flag(st, b, table)) return rc;
   if (b->n == 0) return DPM_OK;  // empty batch: nothing to do (torch allows zero-sized tensors)
   const bool needs_x = st->form != DPM_FORM_DENOISE;
   const bool unipc = st->form == DPM_FORM_UNIPC;
@@ -295,7 +314,8 @@ int dpm_stage_launch_dyn(const dpm_stage* st, const dpm_buffers* b, void* stream
   const PairUnits* p = pair_of(sd, ed);
   if (!p) return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: unsupported dtype pair state=%d eps=%d", sd, ed);
   if (g) return (p->*g->launch)(st, &bb, stream, ev_start, ev_stop);
-  if (st->guidance == DPM_GUIDE_CFG2) return p->pair(st, &bb, stream, ev_start, ev_stop);  // (before the fused-shape test)
+  if (st->guidance == DPM_GUIDE_CFG2)  // (before the fused-shape test)
+    return ((st->flags & DPM_F_CFG2_PERP) ? p->perp : p->pair)(st, &bb, stream, ev_start, ev_stop);
   // A LARGE launch takes the fused multi-request kernel's shape -- one workgroup per super-tile instead of a grid capped at 8
   // workgroups per CU walking the tiles in a loop, an XCD-contiguous tile mapping for 2-byte states, two tiles per workgroup
   // for 4-byte states -- as a "group" of one request (Tuning::big_tiles; the same arithmetic, the same bits).  Stages the fused
@@ -513,7 +533,7 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
   const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0, pair_rows = (flags & DPM_TABLE_PAIR) != 0;
   table_mode &= ~flags;
   for (int r = 0; r < n_req; ++r)
-    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0, pair_rows)) return rc;
+    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0, pair_rows, table_mode != 0)) return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;

@@ -1,5 +1,5 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled forty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5|6|7> (__graft_entry__.py).
+// translation unit: compiled forty-five times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
@@ -22,10 +22,13 @@
 //   unit H (7): the launch of a stage under guidance over two conditions (stage_pair_kernel, DPM_GUIDE_CFG2; dpm_pair_kernel.hpp,
 //               which no other unit includes) and of the table's two-condition rows (stage_pair_kernel_table, DPM_TABLE_PAIR;
 //               dpm_table_pair.hpp) and nothing else -- units A to G compile to the code they compiled to before it existed
-// Units E, F and G are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
+//   unit I (8): the launch of a Perp-Neg stage (stage_perp_kernel, DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 record;
+//               dpm_perp_kernel.hpp, which no other unit includes) and nothing else -- units A to H compile to the code they
+//               compiled to before it existed
+// Units E, F, G and I are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5|6|7>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -49,6 +52,10 @@
 #if DPM_UNIT == 7
 #include "dpm_pair_kernel.hpp"
 #include "dpm_table_pair.hpp"
+#endif
+#if DPM_UNIT == 8
+#include "dpm_sample_frame.hpp"
+#include "dpm_perp_kernel.hpp"
 #endif
 
 #include <tuple>
@@ -196,4 +203,14 @@ int dpm_table_launch_pair(const dpm_stage* st, const dpm_buffers* bs, int n_req,
   return launch_table_pair_typed<TS, TE>(st, bs, n_req, rows, recs, s);
 }
 template int dpm_table_launch_pair<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
+#endif
+
+// The launch of a Perp-Neg stage (DPM_F_CFG2_PERP under DPM_GUIDE_CFG2), checked by dpm_stage_launch.
+#if DPM_UNIT == 8
+template <typename TS, typename TE>
+int dpm_launch_perp(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), static_cast<hipEvent_t>(ev_start), static_cast<hipEvent_t>(ev_stop)};
+  return launch_perp_typed<TS, TE>(st, b, s);
+}
+template int dpm_launch_perp<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
 #endif

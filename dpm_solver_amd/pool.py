@@ -155,7 +155,10 @@ class RequestPool:
         s = self._s
         sd = s._sdtype(x)
         s._check_remedies(sd=sd)            # (a pool's requests do not pass run_plan)
-        s._check_pair("request_pool -- a pool's ticks are fused launches, and a two-condition stage runs on its own in those")
+        if s._perp():
+            s._check_pair()                 # (cfg_perp_neg: taken as it is -- each of its stages a launch of its own in the tick's call)
+        else:
+            s._check_pair("request_pool -- a pool's ticks are fused launches, and a two-condition stage runs on its own in those")
         if (s._state_dtype is None and sd not in (torch.float32, torch.float64) and plan.stages
                 and plan.stages[-1].form == L.FORM_DENOISE and s.noise_schedule.schedule != 'discrete'):
             raise NotImplementedError("request pool: denoise_to_zero with a half-precision state on a continuous schedule "
@@ -183,7 +186,7 @@ class RequestPool:
         if q.plan.sde:
             q.mf = None    # the noise contract indexes the default [B, C, H, W] order (include/dpm_hip.h): contiguous states
         q.key = (id(q.plan), tuple(q.x.shape), q.sd, idx, stream, cfg, q.mf, bool(s.cluster_in_graph), int(s.thr_spin_limit),
-                 s._remedy_key())
+                 s._remedy_key(), s._pair_key())
         free = self._free.get(q.key)
         q.fr = free.pop() if free else _FastRun(s, q.plan, q.x.shape, q.sd, q.x.device, cfg, q.mf)
         if q.fr.apg_avg is not None:
@@ -243,7 +246,7 @@ class RequestPool:
                 q.first = None
                 if q.sd is torch.float64:
                     e = s._cfg_pre(e, q.sd)
-                keep.append(_bind_outputs(b, e[0], e[1], e[2], q.sd, q.x.shape, q.mf))
+                keep.append(_bind_outputs(b, e[0], e[1], e[2], q.sd, q.x.shape, q.mf, s._pair_setting() is not None))
                 C.memmove(C.byref(sts, r * C.sizeof(L.Stage)), C.byref(fr.stages[i]), C.sizeof(L.Stage))
                 C.memmove(C.byref(bufs, r * C.sizeof(L.Buffers)), C.byref(b), C.sizeof(L.Buffers))
         # request 0's options carry the per-request flag (the library reads bs[0].opts); an SDE request's carry its seed,

@@ -190,7 +190,15 @@ class DPM_Solver:
         INTEGRATION.md): a condition tensor is immutable for the life of its wrapper -- the concatenated conditions are built
         once and a captured graph keeps replaying them.  Another condition takes another cfg_pair(...) and another DPM_Solver."""
         p = self._wrapped.pair if self._wrapped is not None else None
-        return None if p is None else (id(p[0]), float(p[1]), float(p[2]))
+        if p is None:
+            return None
+        key = (id(p[0]), float(p[1]), float(p[2]))
+        return key + ("perp_neg",) if self._perp() else key     # (without cfg_perp_neg every key is what it was)
+
+    def _perp(self):
+        """does the wrapper ask for Perp-Neg (cfg_perp_neg; DPM_F_CFG2_PERP)?  _pair_setting() is then (s, w): the guidance and
+        the negative scale, and every rule of _check_pair applies as it stands"""
+        return self._wrapped is not None and self._wrapped.perp
 
     def _check_pair(self, what=None, blend=False):
         """The combinations guidance over two conditions is not built with.  `what` names a sampler or a mode without the
@@ -371,6 +379,13 @@ class DPM_Solver:
             # on as ONE unguided output (the conversions are affine in the output and the three weights sum to one, so blending
             # before them is the same function; the stage record is unguided then: _unguided64)
             e0, e1, g = e0.double(), e1.double(), g.double()
+            if self._perp():
+                # Perp-Neg likewise: projection and blend in double on the raw outputs (include/dpm_hip.h, DPM_F_CFG2_PERP)
+                axes = list(range(1, e0.dim()))
+                d0, d2 = e0 - e1, g - e1
+                s_dd = (d0 * d0).sum(dim=axes, keepdim=True)
+                a = torch.where(s_dd > 0, (d2 * d0).sum(dim=axes, keepdim=True) / s_dd, torch.zeros_like(s_dd))
+                return e1 + pair[0] * (d0 - pair[1] * (d2 - a * d0)), None, None
             return (e1 + pair[0] * (e0 - e1)) + pair[1] * (g - e1), None, None
         if (sd is torch.float64 and e1 is not None and e0.dtype is not torch.float64 and self._wrapped is not None
                 and self._wrapped.model_type == "noise"):
@@ -400,6 +415,7 @@ class DPM_Solver:
         """a double state under guidance over two conditions: _cfg_pre hands the stage ONE blended output -- its record is unguided"""
         if sd is torch.float64 and st.guidance == L.GUIDE["classifier-free-2"]:
             st.guidance = L.GUIDE["uncond"]
+            st.flags &= ~L.F_CFG2_PERP                          # (the flag is valid under the guidance only)
         return st
 
     def _prep_stage(self, st):
@@ -418,6 +434,8 @@ class DPM_Solver:
         if st.guidance == L.GUIDE["classifier-free-2"]:
             self._check_pair()
             st.cg_scale = self._pair_setting()[1]               # s2 (the planner wrote 0; cfg_scale is s1 already)
+            if self._perp():
+                st.flags |= L.F_CFG2_PERP                           # (cg_scale: the negative scale w)
         return st
 
     def _run_stage(self, st, x, xe, outs, h1, h2, sd, t_eval_t, want_m=None, ext=None, coef64=None):
@@ -817,7 +835,8 @@ class DPM_Solver:
         (`submit(x, ..., condition2=c2, guidance_scale=s, pair=(scale2, nested))`), their stages in the table-driven launch
         (DPM_TABLE_PAIR: one stage_pair_kernel_table launch that stores the result three times -- no `torch.cat([x] * 3)`);
         samples of whole 8-element groups.  Not together with sde / thresholding / inpaint / rescale / apg / zero_star;
-        without the flag a pool refuses a `cfg_pair` solver.
+        without the flag a pool refuses a `cfg_pair` solver.  A `cfg_perp_neg` solver has no slab pool yet (a follow-up); a
+        RequestPool (no slots) takes it as it is, each of its stages a launch of its own inside the tick's call.
         Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
@@ -833,6 +852,9 @@ class DPM_Solver:
         if pair:
             if slots is None:
                 raise ValueError("request_pool: pair=True belongs to a slab pool (slots=...)")
+            if self._perp():
+                raise NotImplementedError("request_pool: pair=True with a cfg_perp_neg wrapper -- the table's two-condition rows "
+                                          "have no per-sample pass (a follow-up)")
             if self._pair_setting() is None:
                 raise ValueError("request_pool: pair=True needs a cfg_pair wrapper (guidance over two conditions with a second "
                                  "scale other than 0)")
@@ -843,6 +865,8 @@ class DPM_Solver:
                     raise NotImplementedError("request_pool: pair=True with %s=True -- the two-condition kernel has %s (a "
                                               "follow-up)" % (name, why))
             self._check_pair()
+        elif self._perp() and slots is None:
+            self._check_pair()      # a RequestPool takes a cfg_perp_neg solver as it is: such a stage runs on its own in a tick's launch
         else:
             self._check_pair("request_pool -- a pool's ticks are fused and table-driven launches, and a two-condition stage runs "
                              "on its own in those (sample_requests takes such a solver; request_pool(slots=..., pair=True) is its "

@@ -29,6 +29,10 @@ class WrappedModel:
     # guidance over two conditions (InstructPix2Pix's image and text scales, composable conditions): (condition2, s1, s2), set
     # through dpm_solver_amd.cfg_pair.  None = off: every bit as without it.
     guidance_pair = None
+    # Perp-Neg (Armandpour et al. 2023; ComfyUI's PerpNeg), set through dpm_solver_amd.cfg_perp_neg: guidance_pair is then
+    # (negative_condition, guidance scale, negative scale) and the three outputs meet in the per-sample projection
+    # (DPM_F_CFG2_PERP), not in cfg_pair's linear blend.  False = off: every bit as without it.
+    guidance_perp = False
     _c_in3 = None                            # (condition2, the three conditions concatenated)
 
     def __init__(self, model, noise_schedule, model_type, model_kwargs, guidance_type, condition,
@@ -64,6 +68,12 @@ class WrappedModel:
         if self.guidance_pair is None or self.guidance_type != "classifier-free" or self.unconditional_condition is None:
             return None
         return self.guidance_pair
+
+    @property
+    def perp(self):
+        """does this wrapper ask the stage kernels for the Perp-Neg projection of its three outputs (include/dpm_hip.h,
+        DPM_F_CFG2_PERP)?  `pair` is then (negative condition, s, w)"""
+        return bool(self.guidance_perp) and self.pair is not None
 
     @property
     def rescale_phi(self):
@@ -209,6 +219,26 @@ class WrappedModel:
                 return expand_dims(alpha_t, dims) * out + expand_dims(sigma_t, dims) * x
             return -expand_dims(sigma_t, dims) * out              # "score"
         eff = self.effective_guidance
+        if eff == "classifier-free-2" and self.perp:
+            # Perp-Neg, the torch statement of the contract (include/dpm_hip.h, DPM_F_CFG2_PERP): projection and blend on the RAW
+            # outputs, the conversion afterwards; half outputs are widened to fp32 first, as the stage kernel widens them, and
+            # nothing after that is rounded to half; the two per-sample sums in float64, their quotient rounded once to the
+            # outputs' dtype, 0 where the positive direction vanishes
+            o_c, o_u, o_n = e0, e1, g
+            if o_c.dtype in (torch.float16, torch.bfloat16):
+                o_c, o_u, o_n = o_c.float(), o_u.float(), o_n.float()
+                x = x.float()
+            _, s, w = self.pair
+            if o_c.dtype is torch.float32:
+                s, w = (float(torch.tensor(float(v), dtype=torch.float32)) for v in (s, w))
+            axes = list(range(1, dims))
+            d0, d2 = o_c - o_u, o_n - o_u
+            p64, q64 = d0.double(), d2.double()
+            s_nd = (q64 * p64).sum(dim=axes, keepdim=True)
+            s_dd = (p64 * p64).sum(dim=axes, keepdim=True)
+            a = torch.where(s_dd > 0, s_nd / s_dd, torch.zeros_like(s_dd)).to(o_c.dtype)
+            perp = d2 - a * d0
+            return to_noise(o_u + s * (d0 - w * perp))
         if eff == "classifier-free-2":
             # guidance over two conditions, the torch statement of the contract (include/dpm_hip.h, DPM_GUIDE_CFG2): half
             # outputs are widened to fp32 first, as the stage kernel widens them, the conversions per output, then the five
@@ -270,6 +300,8 @@ def _alone(helper, model_fn):
     for r in REMEDIES:
         if r.name != helper and getattr(model_fn, r.raw):
             raise NotImplementedError("%s on top of %s: the two remedies are not built together" % (helper, r.name))
+    if getattr(model_fn, "guidance_perp", False) and getattr(model_fn, "guidance_pair", None) is not None:
+        raise NotImplementedError("%s on top of cfg_perp_neg: the Perp-Neg stage kernel has no remedy (a follow-up)" % helper)
     if getattr(model_fn, "guidance_pair", None) is not None:
         raise NotImplementedError("%s on top of cfg_pair: the two-condition stage kernel has no remedy (a follow-up)" % helper)
     return copy.copy(model_fn)
@@ -368,10 +400,53 @@ def cfg_pair(model_fn, condition2, scale2, nested=False):
     for r in REMEDIES:
         if getattr(model_fn, r.raw):
             raise NotImplementedError("cfg_pair on top of %s: the two-condition stage kernel has no remedy (a follow-up)" % r.name)
+    if model_fn.guidance_perp and model_fn.guidance_pair is not None:
+        raise NotImplementedError("cfg_pair on top of cfg_perp_neg: the Perp-Neg stage kernel takes one negative condition and no "
+                                  "second blend (a follow-up)")
     s1, s2 = float(s), (float(scale2) - float(s) if nested else float(scale2))
     out = copy.copy(model_fn)
     out._c_in3 = None                                         # (the copy concatenates its own conditions)
     out.guidance_pair = None if s2 == 0.0 else (condition2, s1, s2)
+    return out
+
+
+def cfg_perp_neg(model_fn, negative_condition, neg_scale=1.0):
+    """(extension) A copy of the classifier-free wrapper `model_fn` with Perp-Neg guidance (Armandpour et al. 2023, "Re-imagine
+    the Negative Prompt Algorithm"; ComfyUI's `PerpNeg` / `PerpNegGuider`).  The wrapper's `condition` is the positive prompt,
+    its `unconditional_condition` the EMPTY prompt, `negative_condition` the negative prompt.  The network is evaluated on three
+    copies of the input -- empty, positive, negative -- and, per image, the negative direction loses its component along the
+    positive one before it is subtracted, so that a negative prompt that overlaps the positive one no longer erases the subject.
+    With s = the wrapper's guidance_scale, d_pos = o_pos - o_empty and d_neg = o_neg - o_empty on the raw outputs:
+      a = <d_neg, d_pos> / ||d_pos||^2 over the image;   guided = o_empty + s * (d_pos - neg_scale * (d_neg - a * d_pos))
+    DPM_Solver runs it inside the stage kernel (DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 stage, stage_perp_kernel), in fp32, for both
+    algorithm types.  neg_scale == 0 is classifier-free guidance itself: a plain copy, no third branch.  Not together with
+    cfg_rescale / cfg_apg / cfg_zero_star / cfg_pair, in either order.  The three conditions are IMMUTABLE for the life of the
+    returned wrapper, as under cfg_pair."""
+    _classifier_free("cfg_perp_neg", model_fn)
+    if model_fn.unconditional_condition is None:
+        raise ValueError("cfg_perp_neg: takes a classifier-free wrapper with an unconditional_condition (the empty prompt)")
+    if not torch.is_tensor(negative_condition):
+        raise ValueError("cfg_perp_neg: negative_condition must be a tensor like the wrapper's condition, got %s"
+                         % type(negative_condition).__name__)
+    if torch.is_tensor(model_fn.condition) and negative_condition.shape != model_fn.condition.shape:
+        raise ValueError("cfg_perp_neg: negative_condition has shape %s, the wrapper's condition %s"
+                         % (tuple(negative_condition.shape), tuple(model_fn.condition.shape)))
+    if isinstance(neg_scale, bool) or not isinstance(neg_scale, numbers.Real) or not math.isfinite(float(neg_scale)):
+        raise ValueError("cfg_perp_neg: neg_scale must be a finite real number, got %r" % (neg_scale,))
+    s = model_fn.guidance_scale
+    if isinstance(s, bool) or not isinstance(s, numbers.Real) or not math.isfinite(float(s)):
+        raise ValueError("cfg_perp_neg: the wrapper's guidance_scale must be a finite real number, got %r" % (s,))
+    for r in REMEDIES:
+        if getattr(model_fn, r.raw):
+            raise NotImplementedError("cfg_perp_neg on top of %s: the Perp-Neg stage kernel has no remedy (a follow-up)" % r.name)
+    if model_fn.guidance_pair is not None:
+        raise NotImplementedError("cfg_perp_neg on top of %s: the Perp-Neg stage kernel takes one negative condition and no "
+                                  "second blend (a follow-up)" % ("cfg_perp_neg" if model_fn.guidance_perp else "cfg_pair"))
+    out = copy.copy(model_fn)
+    out._c_in3 = None                                         # (the copy concatenates its own conditions)
+    w = float(neg_scale)
+    out.guidance_pair = None if w == 0.0 else (negative_condition, float(s), w)
+    out.guidance_perp = w != 0.0
     return out
 
 

@@ -108,11 +108,15 @@ extern "C" {
    every qualifying DPM_GUIDE_CFG2 request owns a row and a pair record behind the rows (the third network output, the third
    copy of x_out), a group of them is ONE stage_pair_kernel_table launch; in such a call a DPM_GUIDE_CFG2 request may carry
    x_out2, with the THIRD copy of x_out in dpm_buffers.thr_hint (see "Table mode"; no entry point added, no struct changed).
+   220 DPM_F_CFG2_PERP: Perp-Neg guidance (Armandpour et al. 2023; ComfyUI's PerpNeg) on a DPM_GUIDE_CFG2 stage in ONE stage
+   launch -- a kernel that owns a whole sample, takes the negative condition's direction perpendicular to the positive one's
+   by a per-sample projection of the three raw outputs, then runs the usual conversion, update and stores (see
+   DPM_F_CFG2_PERP; no entry point added, no struct changed).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 219
+#define DPM_HIP_VERSION 220
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -329,6 +333,40 @@ enum {
                                  per sample (stage_zstar_kernel); such a stage runs on its own in a multi-request launch, in
                                  every mode of dpm_stage_launch_multi */
 
+#define DPM_F_CFG2_PERP 8192u /* version 220, with guidance == DPM_GUIDE_CFG2 only (else DPM_ERR_ARG); never set by the planner.
+                                 (The table_mode bit 8192 is a different space and stays unassigned.)
+                                 Perp-Neg (Armandpour et al. 2023, "Re-imagine the Negative Prompt Algorithm"): the negative
+                                 condition's direction is taken perpendicular to the positive one's, per sample, before it is
+                                 subtracted.  Operands as under DPM_GUIDE_CFG2: e0 = the raw output under the positive
+                                 condition, e1 = the unconditional raw output, g = the raw output under the negative condition.
+                                 Scalars: s = dpm_stage.cfg_scale (guidance scale), w = dpm_stage.cg_scale (negative scale; the
+                                 planner writes 0 there, the caller overwrites it).  For each sample of the launch, with
+                                 P = n / batch elements, on the RAW outputs widened to fp32 (as under DPM_F_CFG_ZSTAR):
+                                   d0   = o_c - o_u ;  d2 = o_n - o_u       fp32, one rounding each
+                                   S_nd = sum (double)d2 * (double)d0       products exact in double; sums in double, any order
+                                   S_dd = sum (double)d0 * (double)d0
+                                   a    = S_dd > 0 ? (float)(S_nd / S_dd) : 0.f     one double division, one rounding; a zero or
+                                                                            NaN S_dd gives a = 0: defined behaviour
+                                   perp = d2 - a * d0                       fp32, one rounding per operation, no fused multiply-add
+                                   gd   = o_u + s * (d0 - w * perp)         likewise
+                                   eps  = noise prediction of the raw output gd (x_start / v / score conversion on xe), then
+                                          DPM_F_TO_X0, the update form (LIN1 .. DENOISE, DPM_F_BASE_HIST included),
+                                          DPM_F_STORE_M and the stores, all fp32
+                                 Nothing after the loads is rounded to the network's dtype, and the model values are never half
+                                 tensors under the flag.  Three identities follow from the arithmetic:
+                                   g == e0 (negative = positive): d2 = d0, a = 1, perp = 0 and gd = o_u + s * d0;
+                                   g == e1: d2 = 0, a = 0, perp = 0 and the same gd;
+                                   e0 == e1: d0 = 0, a = 0 and gd = o_u - s * (w * d2).
+                                 DPM_ERR_ARG: the flag without DPM_GUIDE_CFG2; s or w not finite; e1 or g NULL; an unknown form.
+                                 DPM_ERR_UNSUPPORTED (this version): everything DPM_GUIDE_CFG2 refuses -- DPM_F_THRESH,
+                                 DPM_F_BLEND, DPM_F_NOISE, DPM_F_USER_X0, DPM_FORM_UNIPC, a non-NULL x_out2, a double state,
+                                 eps_stride other than 0 or P, device-resident coefficients --; a batch above 2^31 - 1; a
+                                 table-mode call that carries the flag (DPM_TABLE_PAIR rows have no per-sample pass).  A record
+                                 that sets one of DPM_F_CFG_RESCALE / _APG / _ZSTAR is reported by those flags' checks first,
+                                 and every check of DPM_GUIDE_CFG2 speaks before this flag's own.  No output byte is written in
+                                 any error case.  One workgroup per sample (stage_perp_kernel); such a stage runs on its own in
+                                 a multi-request launch, in every mode of dpm_stage_launch_multi */
+
 /* buffer roles for the host-side loop */
 enum { DPM_SRC_STATE = 0, DPM_SRC_TMP = 1 };
 
@@ -353,7 +391,8 @@ typedef struct dpm_stage {
   float sigma_e;       /* sigma(t_eval)                                                          */
   float cfg_scale;     /* guidance_scale as fp32 (ref :330)                                      */
   float cg_scale;      /* fl(guidance_scale * sigma(t_eval))  (ref :321); DPM_F_CFG_RESCALE: phi; DPM_F_CFG_APG: eta;
-                          DPM_GUIDE_CFG2: s2, the scale of the second condition (the planner writes 0)            */
+                          DPM_GUIDE_CFG2: s2, the scale of the second condition (the planner writes 0); with
+                          DPM_F_CFG2_PERP: w, the negative scale                                                   */
   float cx, c0, c1, c2; /* update coefficients, reference association (see kernels)              */
   float k[5];          /* difference-quotient scalars: 1/r0, 1/r1, ...                           */
   float thr_ratio;     /* dynamic_thresholding_ratio;  DPM_F_CFG_APG: the norm threshold r       */

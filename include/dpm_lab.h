@@ -49,6 +49,8 @@ enum {
                                        | ticks (groups 0 = 2); 0 (default): off (profiles/r05_thresholding.md)         */
   DPM_TUNE_BIG_TILES = 17,          /* a single stage launch of at least this many 2048-element tiles is launched with the fused
                                        kernel's shape (as a group of one request); 0: never; default: the library's            */
+  DPM_TUNE_PERP_REREAD = 18,        /* Perp-Neg stage kernel, samples of at most 16384 elements: 1 = the third output is read again
+                                       from L2 in pass 2, 0 = its difference is parked in LDS; -1 (default): the product's    */
   DPM_TUNE_THR_ELECT = 14           /* clustered thresholding: 1 = one elected reducer per sample selects on the union and
                                        publishes the result (k slot reads per sample), 0 = every workgroup reads every slot
                                        (k^2); -1 (default): the library's choice                                        */
