@@ -62,6 +62,8 @@ TABLE_ZSTAR = 4096                        # ... another: DPM_F_CFG_ZSTAR stages 
                                           # 1024 and 2048 are unassigned)
 TABLE_PAIR = 16384                        # ... another: DPM_GUIDE_CFG2 stages take rows and pair records too, and the third copy
                                           # of their x_out is dpm_buffers.thr_hint (version 219; bit 8192 is unassigned)
+TABLE_PERP = 65536                        # ... another: DPM_F_CFG2_PERP stages take rows and pair records too, with the same
+                                          # copies (version 221; bit 32768 is unassigned)
 THR_ROW_MAX = 12288                       # elements of the largest sample a thresholded row holds (THR_CHUNK_MAX, csrc)
 TABLE_MAGIC = 0x4c425444
 SIZEOF_TABLE_HEADER, SIZEOF_TABLE_ROW = 7, 8      # dpm_sizeof indices of the table's header and row
@@ -311,8 +313,8 @@ for _i, _t in enumerate((Stage, Buffers, PlanDesc, RunBuffers, AdaptiveDesc, Lau
                           % (_t.__name__, C.sizeof(_t), lib.dpm_sizeof(_i)))
 
 
-if lib.dpm_version() < 220:
-    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 220 -- stale library, rebuild"
+if lib.dpm_version() < 221:
+    raise ImportError("dpm_solver_amd: libdpm_hip.so reports version %d, this binding needs >= 221 -- stale library, rebuild"
                       % lib.dpm_version())
 TABLE_HEADER_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_HEADER))      # the table of dpm_launch_opts.table_mode: header,
 TABLE_ROW_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_ROW))            # then one row per request of a group of more than 16
@@ -324,12 +326,13 @@ TABLE_PAIR_BYTES = int(lib.dpm_sizeof(SIZEOF_TABLE_PAIR))          # (TABLE_PAIR
 
 def table_bytes(n_req, flags=0):
     """The bytes of the table of a table-mode call of n_req requests whose table_mode carries `flags` (TABLE_NOISE / TABLE_THRESH /
-    TABLE_BLEND / TABLE_RESCALE / TABLE_APG / TABLE_ZSTAR / TABLE_PAIR; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one.
+    TABLE_BLEND / TABLE_RESCALE / TABLE_APG / TABLE_ZSTAR / TABLE_PAIR / TABLE_PERP; the mode bits are ignored): the header, n_req rows, and a section of n_req records for each flag that has one
+    (TABLE_PAIR and TABLE_PERP share the pair records' section: present under either, counted once).
     Not rounded."""
     return (TABLE_HEADER_BYTES + n_req * (TABLE_ROW_BYTES + (TABLE_NOISE_BYTES if flags & TABLE_NOISE else 0)
                                           + (TABLE_BLEND_BYTES if flags & TABLE_BLEND else 0)
                                           + (TABLE_APG_BYTES if flags & TABLE_APG else 0)
-                                          + (TABLE_PAIR_BYTES if flags & TABLE_PAIR else 0)))
+                                          + (TABLE_PAIR_BYTES if flags & (TABLE_PAIR | TABLE_PERP) else 0)))
 
 
 if IS_LAB and os.environ.get("DPM_LAB_TUNE"):

@@ -88,6 +88,9 @@ int dpm_table_launch_pair(const dpm_stage* st, const dpm_buffers* bs, int n_req,
 // per sample
 template <typename TS, typename TE>
 int dpm_launch_perp(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);
+// (unit J, DPM_TABLE_PERP) DPM_F_CFG2_PERP rows and their pair records (the pair records' section), one workgroup per sample
+template <typename TS, typename TE>
+int dpm_table_launch_perp(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream);
 
 // ---- dpm_f64.hip
 int dpm_launch_f64(const dpm_stage* st, const dpm_buffers* b, void* stream, void* ev_start, void* ev_stop);

@@ -54,8 +54,10 @@ struct PairUnits {
   // table (DPM_TABLE_PAIR)
   SampleFn pair;
   TableLaunchFn table_launch_pair;
-  // unit I's Perp-Neg stage (DPM_F_CFG2_PERP under DPM_GUIDE_CFG2): one workgroup per sample, three network outputs
+  // unit I's Perp-Neg stage (DPM_F_CFG2_PERP under DPM_GUIDE_CFG2): one workgroup per sample, three network outputs, and
+  // unit J's rows of the table for it (DPM_TABLE_PERP)
   SampleFn perp;
+  TableLaunchFn table_launch_perp;
 };
 #define DPM_PAIR_ROW(name, TS, TE, SD, ED)                                                                  \
   {SD, ED, dpm_launch_unit<TS, TE, FORMS_A>, dpm_launch_unit<TS, TE, FORMS_B>, dpm_launch_fused<TS, TE>,   \
@@ -64,7 +66,7 @@ struct PairUnits {
    dpm_table_launch_rescale<TS, TE>, dpm_table_launch_apg<TS, TE>, dpm_table_launch_zstar<TS, TE>,         \
    dpm_launch_sample<TS, TE, DPM_F_CFG_RESCALE>, dpm_launch_sample<TS, TE, DPM_F_CFG_APG>,                 \
    dpm_launch_sample<TS, TE, DPM_F_CFG_ZSTAR>, dpm_launch_pair<TS, TE>, dpm_table_launch_pair<TS, TE>,  \
-   dpm_launch_perp<TS, TE>},
+   dpm_launch_perp<TS, TE>, dpm_table_launch_perp<TS, TE>},
 constexpr PairUnits kPairs[] = {DPM_PAIRS(DPM_PAIR_ROW)};
 #undef DPM_PAIR_ROW
 
@@ -173,7 +175,7 @@ int check_sample_guidance(const SampleGuidance& g, const dpm_stage* st, const dp
 // What dpm_stage_launch asks of a stage under guidance over two conditions (DPM_GUIDE_CFG2, include/dpm_hip.h) before anything
 // else of the record is read: its two scales, then what stage_pair_kernel has no path for (b->batch >= 1, n a multiple of it).
 // A remedy flag has been reported by check_sample_guidance ("valid under classifier-free guidance only").  `copies`: the call
-// carries DPM_TABLE_PAIR, where a row stores x_out2 and a third copy (check_pair_copies decides there).
+// carries DPM_TABLE_PAIR or DPM_TABLE_PERP, where a row stores x_out2 and a third copy (check_pair_copies decides there).
 int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b, bool copies) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
   if (!std::isfinite(st->cfg_scale) || !std::isfinite(st->cg_scale))
@@ -195,7 +197,7 @@ int check_pair_guidance(const dpm_stage* st, const dpm_buffers* b, bool copies) 
 
 // What dpm_stage_launch asks of DPM_F_CFG2_PERP (include/dpm_hip.h), behind the remedy flags' checks and behind
 // check_pair_guidance: a record that is refused without the flag is refused by the same line with it.  `table`: the call is a
-// table-mode one (DPM_TABLE_PAIR rows have no per-sample pass).
+// table-mode one without DPM_TABLE_PERP (DPM_TABLE_PAIR rows have no per-sample pass).
 int check_perp_flag(const dpm_stage* st, const dpm_buffers* b, bool table) {
   if (st->guidance != DPM_GUIDE_CFG2)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch: DPM_F_CFG2_PERP is valid under DPM_GUIDE_CFG2 only (guidance %d)", st->guidance);
@@ -209,8 +211,8 @@ int check_perp_flag(const dpm_stage* st, const dpm_buffers* b, bool table) {
 // The argument checks of one request (st and b not null): DPM_OK, or the error (dpm_set_error) of the first check that fails.
 // base_ok: the call is a DPM_TABLE_NOISE one, whose SDE rows honour dpm_buffers.noise_sample0 (checked there, check_noise_base);
 // apg_hint: it is a DPM_TABLE_APG one, where the running average of a DPM_F_CFG_APG request is thr_hint, not workspace;
-// pair_copies: it is a DPM_TABLE_PAIR one, where a DPM_GUIDE_CFG2 request may carry x_out2 (checked there, check_pair_copies);
-// table: it is a table-mode one, which takes no DPM_F_CFG2_PERP request
+// pair_copies: it is a DPM_TABLE_PAIR or DPM_TABLE_PERP one, where a DPM_GUIDE_CFG2 request may carry x_out2 (checked there,
+// check_pair_copies); table: it is a table-mode one without DPM_TABLE_PERP, which takes no DPM_F_CFG2_PERP request
 int check_stage_buffers(const dpm_stage* st, const dpm_buffers* b, bool base_ok = false, bool apg_hint = false,
                         bool pair_copies = false, bool table = false) {
   auto fail = [](int code, const char* fmt, auto... args) { return dpm_set_error(code, fmt, args...); };
@@ -410,14 +412,15 @@ int check_noise_base(const dpm_stage& st, const dpm_buffers& b, bool row) {
   return DPM_OK;
 }
 
-// The copies of one DPM_GUIDE_CFG2 request of a DPM_TABLE_PAIR call: x_out2 and the third copy, dpm_buffers.thr_hint, come
-// together, and only a request that will own a pair row (`row`) has a kernel that stores them -- the lone kernel's refusal
-// otherwise, before anything is written or launched
-int check_pair_copies(const dpm_stage& st, const dpm_buffers& b, bool row) {
+// The copies of one DPM_GUIDE_CFG2 request of a DPM_TABLE_PAIR or DPM_TABLE_PERP call: x_out2 and the third copy,
+// dpm_buffers.thr_hint, come together, and only a request that will own a pair row or a Perp-Neg row (`row`) has a kernel that
+// stores them -- the lone kernels' refusal otherwise, before anything is written or launched.  `flag_name`: the flag the text
+// names (DPM_TABLE_PERP where the call carries that one alone).
+int check_pair_copies(const dpm_stage& st, const dpm_buffers& b, bool row, const char* flag_name) {
   if (st.guidance != DPM_GUIDE_CFG2 || b.n == 0) return DPM_OK;
   if ((b.x_out2 != nullptr) != (b.thr_hint != nullptr))
-    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: DPM_GUIDE_CFG2 in a DPM_TABLE_PAIR call needs x_out2 and the third copy "
-                         "(dpm_buffers.thr_hint) both set or both null");
+    return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: DPM_GUIDE_CFG2 in a %s call needs x_out2 and the third copy "
+                         "(dpm_buffers.thr_hint) both set or both null", flag_name);
   if (b.x_out2 && !row)
     return dpm_set_error(DPM_ERR_UNSUPPORTED, "stage_launch: DPM_GUIDE_CFG2 with x_out2 (the kernel has no second store)");
   return DPM_OK;
@@ -425,7 +428,8 @@ int check_pair_copies(const dpm_stage& st, const dpm_buffers& b, bool row) {
 
 // The table of a table-mode call (include/dpm_hip.h, "Table mode"): the header, n_req rows, then n_req noise records if and only
 // if the call carries DPM_TABLE_NOISE, then n_req blend records (DPM_TABLE_BLEND), then n_req APG records (DPM_TABLE_APG), then
-// n_req pair records (DPM_TABLE_PAIR) -- record i of every section beside row i.
+// n_req pair records (DPM_TABLE_PAIR or DPM_TABLE_PERP: one section, present under either) -- record i of every section beside
+// row i.
 struct TableSections {
   char *rows, *noise, *blend, *apg, *pair;
 };
@@ -435,7 +439,7 @@ TableSections table_sections(void* table, int64_t n_req, int flags) {
   t.noise = t.rows + n_req * (int64_t)DPM_TABLE_ROW_BYTES;
   t.blend = t.noise + ((flags & DPM_TABLE_NOISE) ? n_req * (int64_t)DPM_TABLE_NOISE_BYTES : 0);
   t.apg = t.blend + ((flags & DPM_TABLE_BLEND) ? n_req * (int64_t)DPM_TABLE_BLEND_BYTES : 0);
-  t.pair = t.apg + ((flags & DPM_TABLE_APG) ? n_req * (int64_t)DPM_TABLE_APG_BYTES : 0);
+  t.pair = t.apg + ((flags & DPM_TABLE_APG) ? n_req * (int64_t)DPM_TABLE_APG_BYTES : 0);  // (DPM_TABLE_PAIR / DPM_TABLE_PERP)
   return t;
 }
 
@@ -477,6 +481,12 @@ const RowKind kRowKinds[] = {
     // CFG-Zero* requests (DPM_F_CFG_ZSTAR; dpm_table_zstar.hpp), from ONE member on, for the same reason.  Any of LIN1 / TWO /
     // MS3 / DENOISE and any guidance scale in one group; the flag has no parameter and no state, so a row is all there is.
     {DPM_TABLE_ZSTAR, zstar_row_ok, nullptr, false, true, 1, nullptr, 0, nullptr, &PairUnits::table_launch_zstar},
+    // Perp-Neg requests (DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 record; dpm_table_perp.hpp), from ONE member on, for the same reason.
+    // Before the two-condition kind, which refuses the flag (pair_row_ok): a flagged request is never blended linearly.  Any of
+    // LIN1 / TWO / MS3 / DENOISE, any s and w, rows with and without the copies in one group; the record is a pair record, in the
+    // pair records' section.
+    {DPM_TABLE_PERP, perp_row_ok, nullptr, false, true, 1, &TableSections::pair, DPM_TABLE_PAIR_BYTES, table_fill_pair,
+     &PairUnits::table_launch_perp},
     // requests under guidance over two conditions (DPM_GUIDE_CFG2; dpm_table_pair.hpp), from ONE member on: the alternative is a
     // launch per request.  A streaming kind, one workgroup per super-tile.  Any of LIN1 / TWO / MS3 / DENOISE, any two scales,
     // rows with and without the copies in one group; the record carries the third output (g) and the third copy of x_out (the
@@ -529,18 +539,25 @@ int launch_alone(const dpm_stage* st, const dpm_buffers* b, int flags, void* str
 // one function, so their row order is the same.
 int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req, void* stream, int table_mode, void* table) {
   const int flags = table_mode & (DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
-                                  DPM_TABLE_ZSTAR | DPM_TABLE_PAIR);
-  const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0, pair_rows = (flags & DPM_TABLE_PAIR) != 0;
+                                  DPM_TABLE_ZSTAR | DPM_TABLE_PAIR | DPM_TABLE_PERP);
+  const bool noise_rows = (flags & DPM_TABLE_NOISE) != 0, perp_rows = (flags & DPM_TABLE_PERP) != 0;
+  const bool pair_rows = (flags & DPM_TABLE_PAIR) != 0 || perp_rows;  // (the calls whose DPM_GUIDE_CFG2 requests may carry copies)
   table_mode &= ~flags;
-  for (int r = 0; r < n_req; ++r)
-    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0, pair_rows, table_mode != 0)) return rc;
+  for (int r = 0; r < n_req; ++r)  // (in a call with DPM_TABLE_PERP alone only a flagged request may carry copies)
+    if (const int rc = check_stage_buffers(&st[r], &bs[r], noise_rows, (flags & DPM_TABLE_APG) != 0,
+                                           (flags & DPM_TABLE_PAIR) || (perp_rows && (st[r].flags & DPM_F_CFG2_PERP)),
+                                           table_mode != 0 && !perp_rows))
+      return rc;
   const bool fuse = tuning_for(bs[0].opts).multi_fuse != 0;
   const bool shapes = bs[0].opts->fuse_shapes == 1;
   const bool fill = table_mode == DPM_TABLE_FILL;
   for (int r = 0; noise_rows && r < n_req; ++r)
     if (const int rc = check_noise_base(st[r], bs[r], owns_row(DPM_TABLE_NOISE, st[r], bs[r], flags, fuse))) return rc;
-  for (int r = 0; pair_rows && r < n_req; ++r)
-    if (const int rc = check_pair_copies(st[r], bs[r], owns_row(DPM_TABLE_PAIR, st[r], bs[r], flags, fuse))) return rc;
+  for (int r = 0; pair_rows && r < n_req; ++r) {
+    const RowKind* const k = row_kind(st[r], bs[r], flags, fuse);
+    const bool row = k && (k->flag == DPM_TABLE_PAIR || k->flag == DPM_TABLE_PERP);
+    if (const int rc = check_pair_copies(st[r], bs[r], row, (flags & DPM_TABLE_PAIR) ? "DPM_TABLE_PAIR" : "DPM_TABLE_PERP")) return rc;
+  }
   const TableSections sec = table_mode ? table_sections(table, n_req, flags) : TableSections{};
   int64_t n_rows = 0;
   uint32_t n_runs = 0;
@@ -626,11 +643,11 @@ int stage_launch_multi_het(const dpm_stage* st, const dpm_buffers* bs, int n_req
 // the argument rules of dpm_launch_opts.table_mode (include/dpm_hip.h, "Table mode"); o = bs[0].opts
 int check_table_mode(const dpm_launch_opts* o, const dpm_stage* st, const dpm_buffers* bs) {
   const int mode = o->table_mode & ~(DPM_TABLE_NOISE | DPM_TABLE_THRESH | DPM_TABLE_BLEND | DPM_TABLE_RESCALE | DPM_TABLE_APG |
-                                     DPM_TABLE_ZSTAR | DPM_TABLE_PAIR);
+                                     DPM_TABLE_ZSTAR | DPM_TABLE_PAIR | DPM_TABLE_PERP);
   if (o->table_mode < 0 || (mode != DPM_TABLE_FILL && mode != DPM_TABLE_LAUNCH))
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode=%d (0, DPM_TABLE_FILL or DPM_TABLE_LAUNCH, with or "
                          "without DPM_TABLE_NOISE / DPM_TABLE_THRESH / DPM_TABLE_BLEND / DPM_TABLE_RESCALE / DPM_TABLE_APG / "
-                         "DPM_TABLE_ZSTAR / DPM_TABLE_PAIR)",
+                         "DPM_TABLE_ZSTAR / DPM_TABLE_PAIR / DPM_TABLE_PERP)",
                          o->table_mode);
   if (o->per_request_stages != 1)
     return dpm_set_error(DPM_ERR_ARG, "stage_launch_multi: table_mode needs per_request_stages == 1");

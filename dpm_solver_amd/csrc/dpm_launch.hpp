@@ -260,15 +260,37 @@ inline bool zstar_row_ok(const dpm_stage& st, const dpm_buffers& b) {
 // noise / split stage, no UniPC form or flag, 2- and 4-byte dtypes, a dense network output) and what a row asks: form LIN1 / TWO /
 // MS3 / DENOISE, a plain request, n a positive multiple of 8 (the kernel takes the 16-byte accesses only), e0, e1, g and x_out
 // set, every buffer 16-byte aligned -- x_out2 and, in such a call, the third copy (thr_hint) too.  (Whether the two copies come
-// together is the call's check, check_pair_copies, not the row's.)
+// together is the call's check, check_pair_copies, not the row's.)  A DPM_F_CFG2_PERP request is no such row: its blend is not
+// the linear one (in a call that carries DPM_TABLE_PERP too it owns a Perp-Neg row, perp_row_ok, or goes on its own).
 inline bool pair_row_ok(const dpm_stage& st, const dpm_buffers& b) {
   if (st.guidance != DPM_GUIDE_CFG2 || !std::isfinite(st.cfg_scale) || !std::isfinite(st.cg_scale)) return false;
+  if (st.flags & DPM_F_CFG2_PERP) return false;
   if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_USER_X0 | DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC |
                   DPM_F_CFG_RESCALE | DPM_F_CFG_APG | DPM_F_CFG_ZSTAR))
     return false;
   if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3 && st.form != DPM_FORM_DENOISE) return false;
   if (b.state_dtype == DPM_DTYPE_F64 || b.eps_dtype == DPM_DTYPE_F64) return false;
   if (b.n <= 0 || b.n % EPT != 0 || !plain_request(b) || !b.e0 || !b.e1 || !b.g || !b.x_out) return false;
+  return buffers_aligned(b, 16, 16) && aligned(b.g, 16) && aligned(b.x_out2, 16) && aligned(b.thr_hint, 16);
+}
+
+// May a Perp-Neg request own a table row (DPM_TABLE_PERP; stage_perp_kernel_table, dpm_table_perp.hpp)?  DPM_F_CFG2_PERP set,
+// what a two-condition row asks (pair_row_ok's conditions) and what a kernel that owns a sample asks: a SAMPLE (n / batch) of
+// whole 8-element groups -- 16 bytes or a multiple in either dtype: the kernel works per sample and takes the 16-byte accesses
+// only --, every buffer 16-byte aligned, x_out2 and the third copy (thr_hint) too.  For a request with batch >= 1 and n a
+// multiple of it.
+inline bool perp_row_ok(const dpm_stage& st, const dpm_buffers& b) {
+  if (!(st.flags & DPM_F_CFG2_PERP)) return false;
+  if (st.guidance != DPM_GUIDE_CFG2 || !std::isfinite(st.cfg_scale) || !std::isfinite(st.cg_scale)) return false;
+  if (st.flags & (DPM_F_THRESH | DPM_F_BLEND | DPM_F_NOISE | DPM_F_USER_X0 | DPM_F_UNIPC_DP | DPM_F_UNIPC_P2 | DPM_F_STORE_XC |
+                  DPM_F_CFG_RESCALE | DPM_F_CFG_APG | DPM_F_CFG_ZSTAR))
+    return false;
+  if (st.form != DPM_FORM_LIN1 && st.form != DPM_FORM_TWO && st.form != DPM_FORM_MS3 && st.form != DPM_FORM_DENOISE) return false;
+  if (b.state_dtype == DPM_DTYPE_F64 || b.eps_dtype == DPM_DTYPE_F64) return false;
+  if (b.n <= 0 || !plain_request(b) || !b.e0 || !b.e1 || !b.g || !b.x_out) return false;
+  const int64_t per = b.n / b.batch;
+  const int64_t bs = per * (b.state_dtype == DPM_DTYPE_F32 ? 4 : 2), be = per * (b.eps_dtype == DPM_DTYPE_F32 ? 4 : 2);
+  if (per < EPT || per % EPT != 0 || bs % 16 != 0 || be % 16 != 0) return false;
   return buffers_aligned(b, 16, 16) && aligned(b.g, 16) && aligned(b.x_out2, 16) && aligned(b.thr_hint, 16);
 }
 

@@ -1,6 +1,7 @@
 // dpm_perp_kernel.hpp -- Perp-Neg guidance (DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 stage, include/dpm_hip.h; Armandpour et al.
 // 2023, "Re-imagine the Negative Prompt Algorithm"; ComfyUI's PerpNeg): stage_perp_kernel, a stage kernel that owns a whole
-// SAMPLE and reads THREE network outputs, and its launcher.  Included by unit I of dpm_stage_unit.hip behind
+// SAMPLE and reads THREE network outputs, and its launcher (its table sibling, stage_perp_kernel_table, is dpm_table_perp.hpp's,
+// on perp_sample below, in unit J).  Included by units I and J of dpm_stage_unit.hip behind
 // dpm_sample_frame.hpp -- the workgroup, the lane-to-element map, the masked loads and stores, the reduction, the two access
 // paths -- and by nothing else, so that every other unit compiles to the code it compiled to.
 //
@@ -62,12 +63,26 @@ __device__ __forceinline__ void perp_accumulate(const float (&vc)[EPT], const fl
   }
 }
 
-// pass 2 on one iteration: the guided raw output, the conversion, eps -> x0, the update form, the stores
-template <bool VEC, typename TS, typename TE>
+// The copies of the state a table row may name (stage_perp_kernel_table, dpm_table_perp.hpp): where xo2 is not null
+// (workgroup-uniform) the state is stored to xo2 and xo3 as well, by x_out's own store -- the other two thirds of the network's
+// next [3S, ...] input.  The lone kernel has no second store: its instantiation passes no pointers and takes the empty overload.
+template <bool VEC, typename TS>
+__device__ __forceinline__ void perp_store_copies(int64_t, int64_t, const float (&)[EPT]) {}
+template <bool VEC, typename TS>
+__device__ __forceinline__ void perp_store_copies(int64_t k, int64_t per, const float (&ox)[EPT], TS* xo2, TS* xo3) {
+  if (xo2) {
+    sf_store<VEC>(xo2, k, per, ox);
+    sf_store<VEC>(xo3, k, per, ox);
+  }
+}
+
+// pass 2 on one iteration: the guided raw output, the conversion, eps -> x0, the update form, the stores.  COPIES: a compile-time
+// pack, empty (the lone kernel: the function is what it was) or the two copies' pointers (perp_store_copies).
+template <bool VEC, typename TS, typename TE, typename... COPIES>
 __device__ __forceinline__ void perp_update(const float (&vc)[EPT], const float (&vu)[EPT], const float (&d2)[EPT],
                                             const TS* __restrict__ x, const TS* __restrict__ xe, const TS* __restrict__ h1,
                                             const TS* __restrict__ h2, TS* __restrict__ xo, TS* __restrict__ mo, int64_t k,
-                                            int64_t per, float a, const KParams& p) {
+                                            int64_t per, float a, const KParams& p, COPIES... copies) {
   const bool need_xe = (p.flags & DPM_F_TO_X0) || p.model_type == DPM_MODEL_X_START || p.model_type == DPM_MODEL_V;
   const bool nx = form_needs_x<FORM_RT>(p), nh1 = form_needs_h1<FORM_RT>(p), nh2 = form_needs_h2<FORM_RT>(p);
   const bool sep = xe != x;  // a separate evaluation state (singlestep mid-stages)
@@ -90,16 +105,18 @@ __device__ __forceinline__ void perp_update(const float (&vc)[EPT], const float 
     ox[j] = combine_any<FORM_RT, float, TE>(nx ? xv : 0.f, mn, nh1 ? vh1[j] : 0.f, nh2 ? vh2[j] : 0.f, p, false);
   }
   sf_store<VEC>(xo, k, per, ox);
+  perp_store_copies<VEC, TS>(k, per, ox, copies...);
   if (p.flags & DPM_F_STORE_M) sf_store<VEC>(mo, k, per, om);
 }
 
 // one sample, both passes.  KEEP: the register path (per <= SF_KEEP_MAX), PARK: its d2 crosses the barrier in LDS.  Called by
 // every thread of the workgroup with workgroup-uniform template arguments: the barrier inside is reached by all of them.
-template <bool VEC, bool KEEP, bool PARK, typename TS, typename TE>
+// COPIES: perp_update's.
+template <bool VEC, bool KEEP, bool PARK, typename TS, typename TE, typename... COPIES>
 __device__ __forceinline__ void perp_sample(const TS* __restrict__ x, const TS* __restrict__ xe, const TE* __restrict__ e0,
                                             const TE* __restrict__ e1, const TE* __restrict__ e2, const TS* __restrict__ h1,
                                             const TS* __restrict__ h2, TS* __restrict__ xo, TS* __restrict__ mo, int64_t per,
-                                            const KParams& p, double* red, perp_f4* park) {
+                                            const KParams& p, double* red, perp_f4* park, COPIES... copies) {
   const int64_t nchunks = (per + SF_CHUNK - 1) / SF_CHUNK;
   double acc[2] = {0.0, 0.0};
   float kc[KEEP ? SF_KEEP_CHUNKS : 1][EPT], ku[KEEP ? SF_KEEP_CHUNKS : 1][EPT], vn[EPT], d2[EPT];
@@ -138,7 +155,7 @@ __device__ __forceinline__ void perp_sample(const TS* __restrict__ x, const TS* 
 #pragma unroll
           for (int j = 0; j < EPT; ++j) d2[j] = vn[j] - ku[k][j];
         }
-        perp_update<VEC, TS, TE>(kc[k], ku[k], d2, x, xe, h1, h2, xo, mo, k, per, a, p);
+        perp_update<VEC, TS, TE>(kc[k], ku[k], d2, x, xe, h1, h2, xo, mo, k, per, a, p, copies...);
       }
   } else {
     for (int64_t k = 0; k < nchunks; ++k) {
@@ -147,7 +164,7 @@ __device__ __forceinline__ void perp_sample(const TS* __restrict__ x, const TS* 
       sf_load<VEC, true>(e2, k, per, vn);
 #pragma unroll
       for (int j = 0; j < EPT; ++j) d2[j] = vn[j] - ku[0][j];
-      perp_update<VEC, TS, TE>(kc[0], ku[0], d2, x, xe, h1, h2, xo, mo, k, per, a, p);
+      perp_update<VEC, TS, TE>(kc[0], ku[0], d2, x, xe, h1, h2, xo, mo, k, per, a, p, copies...);
     }
   }
 }

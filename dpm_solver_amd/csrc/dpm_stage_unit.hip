@@ -1,5 +1,5 @@
 // dpm_stage_unit.hip -- the stage kernels of one (state dtype, network-output dtype) pair, half of its update forms per
-// translation unit: compiled forty-five times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8> (__graft_entry__.py).
+// translation unit: compiled fifty times, with -DDPM_PAIR=<row of DPM_PAIRS> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8|9> (__graft_entry__.py).
 //   unit A (0): the TWO and SS3T forms (FORMS_A), the fused multi-request launcher and the pair's catch-all kernels
 //   unit B (1): the LIN1, MS3, DENOISE and UNIPC forms (FORMS_B) and the heterogeneous fused launcher (stage_kernel_het,
 //               stage_kernel_het_noise, stage_kernel_het_unipc) with its mixed-shape sibling (stage_kernel_shapes,
@@ -23,12 +23,16 @@
 //               which no other unit includes) and of the table's two-condition rows (stage_pair_kernel_table, DPM_TABLE_PAIR;
 //               dpm_table_pair.hpp) and nothing else -- units A to G compile to the code they compiled to before it existed
 //   unit I (8): the launch of a Perp-Neg stage (stage_perp_kernel, DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 record;
-//               dpm_perp_kernel.hpp, which no other unit includes) and nothing else -- units A to H compile to the code they
-//               compiled to before it existed
-// Units E, F, G and I are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
+//               dpm_perp_kernel.hpp) and nothing else -- units A to H compile to the code they compiled to before it existed
+//   unit J (9): the launch of the table's Perp-Neg rows (stage_perp_kernel_table, DPM_TABLE_PERP; dpm_table_perp.hpp, on
+//               dpm_perp_kernel.hpp's perp_sample) and nothing else.  Not in unit I, where units E to H keep their table
+//               siblings: with the table kernel beside it in one module the compiler schedules the lone stage_perp_kernel
+//               differently (same instructions, another order and register assignment), and the lone kernel keeps the code
+//               it had (profiles/r33_slab_perp_neg.md)
+// Units E, F, G, I and J are the kernels that own a whole sample; they share dpm_sample_frame.hpp, which no other unit includes.
 // Filling a table (DPM_TABLE_FILL) is host code without a dtype and lives in no unit: dpm_kernels.hip calls it directly.
 #if !defined(DPM_PAIR) || !defined(DPM_UNIT)
-#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8>"
+#error "dpm_stage_unit.hip is compiled with -DDPM_PAIR=<row> -DDPM_UNIT=<0|1|2|3|4|5|6|7|8|9>"
 #endif
 #if DPM_UNIT == 0
 #define DPM_CATCHALL_HOME
@@ -56,6 +60,11 @@
 #if DPM_UNIT == 8
 #include "dpm_sample_frame.hpp"
 #include "dpm_perp_kernel.hpp"
+#endif
+#if DPM_UNIT == 9
+#include "dpm_sample_frame.hpp"
+#include "dpm_perp_kernel.hpp"
+#include "dpm_table_perp.hpp"
 #endif
 
 #include <tuple>
@@ -213,4 +222,13 @@ int dpm_launch_perp(const dpm_stage* st, const dpm_buffers* b, void* stream, voi
   return launch_perp_typed<TS, TE>(st, b, s);
 }
 template int dpm_launch_perp<State, Eps>(const dpm_stage*, const dpm_buffers*, void*, void*, void*);
+#endif
+
+#if DPM_UNIT == 9
+template <typename TS, typename TE>
+int dpm_table_launch_perp(const dpm_stage* st, const dpm_buffers* bs, int n_req, const void* rows, const void* recs, void* stream) {
+  const LaunchCtx s{static_cast<hipStream_t>(stream), nullptr, nullptr};
+  return launch_table_perp_typed<TS, TE>(st, bs, n_req, rows, recs, s);
+}
+template int dpm_table_launch_perp<State, Eps>(const dpm_stage*, const dpm_buffers*, int, const void*, const void*, void*);
 #endif

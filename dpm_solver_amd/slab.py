@@ -171,6 +171,31 @@ element count is no multiple of 8, and one whose row is no multiple of 16 bytes.
 Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper is
 `cfg_pair(model_wrapper(..., guidance_scale=s, condition=c, unconditional_condition=u), c2, scale2, nested)`, for any b,
 whichever rows it landed in.
+
+`request_pool(slots=S, perp_neg=True)` is the slab pool of a `dpm_solver_amd.cfg_perp_neg` wrapper: Perp-Neg guidance, the
+negative prompt's direction taken perpendicular to the positive one's, per image.  Everything about the slabs is the pair pool's:
+state slabs of [3S, ...], a time vector of 3S entries, a condition slab [3S, *cond_shape] in the wrapper's order -- empty
+prompt, positive, negative --, the one network call's output chunked as `e1, e0, e2 = out.chunk(3)`, exactly as
+`WrappedModel.raw_outputs` chunks it, x_T written into all three thirds at admission.  The tick's two calls carry
+DPM_TABLE_PERP: every row is a Perp-Neg row of the table -- ONE stage_perp_kernel_table launch per group, one workgroup per
+sample running the source of the request's own stage_perp_kernel launch -- with a pair record behind it: g = e2 + row, and the
+THIRD copy of x_out in dpm_buffers.thr_hint (x_out2 = xout + (S + row), thr_hint = xout + (2S + row); both zero on a request's
+last stage).  The kernel stores the result three times, so no tick runs a `torch.cat([x] * 3)`; a tick stays one network call,
+one copy and one launch per group.  The DENOISE stage of denoise_to_zero is a row too.  Per request: `submit(..., condition=,
+unconditional_condition=, negative_condition=, guidance_scale=s, neg_scale=w)` -- either scale without the other: they are
+independent, unlike cfg_pair's `nested` --, checked as `cfg_perp_neg` checks them, with its texts.  Both scales are kept per row;
+every tick writes them over the gathered records (cfg_scale = s, cg_scale = w); the flag stays as `_prep_stage` bound it.  The
+defaults are the wrapper's own values.  A request with w == 0 is NotImplementedError: it would be plain two-branch guidance,
+which for half noise networks blends in half, and a row of a [3S] slab cannot reproduce those bits.  At its first submit such a
+pool refuses a sample of fewer than 8 elements, one whose element count is no multiple of 8, and one whose row is no multiple
+of 16 bytes.  Refused with NotImplementedError: `perp_neg=True` with `sde`, `thresholding`, `inpaint`, `rescale`, `apg`,
+`zero_star` or `pair`; `submit_unipc`; `submit(sde=True)`; `blend=`; `negative_condition=` / `neg_scale=` outside a
+`perp_neg=True` pool; `condition2=` / `pair=` inside one.  `perp_neg=True` on a solver whose wrapper is no `cfg_perp_neg` one
+(a plain `cfg_pair` wrapper included), and without `slots`, are ValueError.  Without `perp_neg=True` a slab pool refuses a
+`cfg_perp_neg` solver as before (`pair=True` with its own text).
+Guarantee: every result is bit-identical to `sample(x, ...)` on the request alone, on a solver whose wrapper is
+`cfg_perp_neg(model_wrapper(..., guidance_scale=s, condition=c, unconditional_condition=u), n, w)`, for any b, whichever rows
+it landed in and whoever used them before.
 """
 import ctypes as C
 import math
@@ -238,6 +263,7 @@ _ROW_CHECKS = (
     ("_apg", 8, math.inf, "slab pool: apg=True with a sample of %d elements -- an APG row of the table is " + _GROUPS),
     ("_zst", 8, math.inf, "slab pool: zero_star=True with a sample of %d elements -- a CFG-Zero* row of the table is " + _GROUPS),
     ("_pr", 8, math.inf, "slab pool: pair=True with a sample of %d elements -- a two-condition row of the table is " + _GROUPS),
+    ("_pn", 8, math.inf, "slab pool: perp_neg=True with a sample of %d elements -- a Perp-Neg row of the table is " + _GROUPS),
     ("_thr", 0, L.THR_ROW_MAX, "slab pool: thresholding=True with a sample of %%d elements -- a thresholded row of the table is "
                                "at most %d elements (one workgroup's LDS), " % L.THR_ROW_MAX + _GROUPS),
 )
@@ -278,7 +304,7 @@ class SlabPool:
     """`slots` rows of one sample shape, dtype and device (fixed by the first submit); see the module docstring."""
 
     def __init__(self, solver, slots, sde=False, thresholding=False, inpaint=False, rescale=False, apg=False,
-                 zero_star=False, pair=False):
+                 zero_star=False, pair=False, perp_neg=False):
         slots = int(slots)
         if slots < 1:
             raise ValueError("request_pool: slots must be a positive number of rows, got %d" % slots)
@@ -290,10 +316,13 @@ class SlabPool:
         self._apg = bool(apg)            # adaptive-projected-guidance requests admitted: the tick's calls carry DPM_TABLE_APG
         self._zst = bool(zero_star)      # CFG-Zero* requests admitted: the tick's calls carry DPM_TABLE_ZSTAR
         self._pr = bool(pair)            # a cfg_pair solver's pool, slabs of [3S, ...]: the tick's calls carry DPM_TABLE_PAIR
+        self._pn = bool(perp_neg)        # a cfg_perp_neg solver's pool, slabs of [3S, ...]: the tick's calls carry DPM_TABLE_PERP
+        self._three = self._pr or self._pn   # three network outputs per row: the third condition in q.cond2, the scales in q.pair
         self._tflags = ((L.TABLE_NOISE if self._sde else 0) | (L.TABLE_THRESH if self._thr else 0)
                         | (L.TABLE_BLEND if self._inp else 0)       # ... the flags of every tick's two calls, and its table's size
                         | (L.TABLE_RESCALE if self._rsc else 0) | (L.TABLE_APG if self._apg else 0)
-                        | (L.TABLE_ZSTAR if self._zst else 0) | (L.TABLE_PAIR if self._pr else 0))
+                        | (L.TABLE_ZSTAR if self._zst else 0) | (L.TABLE_PAIR if self._pr else 0)
+                        | (L.TABLE_PERP if self._pn else 0))
         self._avg = None                 # (an apg=True pool) the running averages: one fp32 slab [S, *sample_shape]
         self._cols = []                  # the per-row arrays of _ROW (self._req, self._pos, ...), each with its idle value
         for name, dtype, idle in _ROW:
@@ -377,8 +406,38 @@ class SlabPool:
                                       "request_pool(slots=..., zero_star=True) only")
         return bool(on)
 
+    def _perp_params(self, scale, neg_scale, neg_cond, pair, cond2):
+        """the request's own (s, w) of submit's guidance_scale= / neg_scale=, checked as cfg_perp_neg checks them; None: the
+        wrapper's"""
+        if not self._pn:
+            if neg_scale is not None or neg_cond is not None:
+                raise NotImplementedError("slab pool: %s= -- Perp-Neg stages take the table in a pool built with "
+                                          "request_pool(slots=..., perp_neg=True) only"
+                                          % ("neg_scale" if neg_scale is not None else "negative_condition"))
+            return None
+        if pair is not None or cond2 is not None:
+            raise NotImplementedError("slab pool: %s= in a perp_neg=True pool -- the Perp-Neg kernel takes one negative "
+                                      "condition (negative_condition=, neg_scale=) and no second blend"
+                                      % ("pair" if pair is not None else "condition2"))
+        if scale is None and neg_scale is None:
+            return None
+        s0, w0 = self._s._pair_setting()
+        w = w0 if neg_scale is None else neg_scale
+        if isinstance(w, bool) or not isinstance(w, numbers.Real) or not math.isfinite(float(w)):
+            raise ValueError("cfg_perp_neg: neg_scale must be a finite real number, got %r" % (w,))
+        sc = s0 if scale is None else scale
+        if isinstance(sc, bool) or not isinstance(sc, numbers.Real) or not math.isfinite(float(sc)):
+            raise ValueError("cfg_perp_neg: the wrapper's guidance_scale must be a finite real number, got %r" % (sc,))
+        if float(w) == 0.0:
+            raise NotImplementedError("slab pool: neg_scale=%r -- a negative scale of 0 is plain two-branch guidance: for half "
+                                      "noise networks that blends in half, and a row of a [3S] slab cannot reproduce those bits"
+                                      % (w,))
+        return float(sc), float(w)
+
     def _pair_params(self, scale, pair, cond2):
         """the request's own (s1, s2) of submit's guidance_scale= / pair=, checked as cfg_pair checks them; None: the wrapper's"""
+        if self._pn:
+            return None                  # (a perp_neg=True pool: _perp_params has spoken)
         if not self._pr:
             if pair is not None:
                 raise NotImplementedError("slab pool: pair= -- two-condition stages take the table in a pool built with "
@@ -458,7 +517,8 @@ class SlabPool:
     def submit(self, x, steps=20, t_start=None, t_end=None, order=2, skip_type='time_uniform', method='multistep',
                lower_order_final=True, denoise_to_zero=False, solver_type='dpmsolver', return_intermediate=False, sde=False,
                condition=None, unconditional_condition=None, seed=None, generator=None, blend=None, guidance_scale=None,
-               guidance_rescale=None, apg=None, zero_star=None, condition2=None, pair=None):
+               guidance_rescale=None, apg=None, zero_star=None, condition2=None, pair=None, negative_condition=None,
+               neg_scale=None):
         """Admit a multistep ODE request: `x` = its x_T of [b, *sample_shape] (b rows, any rows), the rest as for `sample()`,
         validated with sample()'s errors in its order before any device work.  `condition` / `unconditional_condition`: the
         request's own, of leading dimension b or 1 (default: the wrapper's).  Refused with NotImplementedError: singlestep and
@@ -481,10 +541,16 @@ class SlabPool:
         wrapper's.
         `condition2=c2, guidance_scale=s, pair=(scale2, nested)` (a pool built with pair=True): the request's own second
         condition and its own two scales -- the result of `sample()` under `cfg_pair(model_wrapper(..., guidance_scale=s),
-        c2, scale2, nested)`.  `guidance_scale=` needs `pair=` there; 1.0 is fine.  Default: the wrapper's."""
+        c2, scale2, nested)`.  `guidance_scale=` needs `pair=` there; 1.0 is fine.  Default: the wrapper's.
+        `negative_condition=n, guidance_scale=s, neg_scale=w` (a pool built with perp_neg=True): the request's own negative
+        prompt and its own two scales, either without the other -- the result of `sample()` under
+        `cfg_perp_neg(model_wrapper(..., guidance_scale=s), n, w)`; w = 0 is refused.  Default: the wrapper's."""
         s = self._s
+        perp = self._perp_params(guidance_scale, neg_scale, negative_condition, pair, condition2)
         pair = self._pair_params(guidance_scale, pair, condition2)
-        guide = self._guidance(None if self._pr else guidance_scale, guidance_rescale)
+        if self._pn:                     # (the third condition and the two scales travel as the pair pool's do)
+            pair, condition2 = perp, negative_condition
+        guide = self._guidance(None if self._three else guidance_scale, guidance_rescale)
         apg = self._apg_params(apg)
         zero_star = self._zstar_choice(zero_star)
         if blend is not None:
@@ -551,19 +617,20 @@ class SlabPool:
             if cond is not None or uncond is not None:
                 raise ValueError("slab pool: `condition` / `unconditional_condition` belong to a classifier-free wrapper")
             return None, None, None
-        cfg = w.effective_guidance == "classifier-free" or self._pr
+        cfg = w.effective_guidance == "classifier-free" or self._three
         cond = w.condition if cond is None else cond
         uncond = (w.unconditional_condition if uncond is None else uncond) if cfg else None
-        cond2 = (w.pair[0] if cond2 is None else cond2) if self._pr else None
-        for name, c in (("condition", cond), ("unconditional_condition", uncond), ("condition2", cond2)):
-            if c is None and (name == "condition" or (cfg and name != "condition2") or self._pr):
+        cond2 = (w.pair[0] if cond2 is None else cond2) if self._three else None
+        third = "negative_condition" if self._pn else "condition2"
+        for name, c in (("condition", cond), ("unconditional_condition", uncond), (third, cond2)):
+            if c is None and (name == "condition" or (cfg and name != third) or self._three):
                 raise ValueError("slab pool: the request has no %s and the wrapper has none" % name)
             if c is not None and (not torch.is_tensor(c) or c.dim() < 1 or c.shape[0] not in (1, b)):
                 raise ValueError("slab pool: %s must be a tensor of leading dimension %d or 1" % (name, b))
         if uncond is not None and (uncond.shape[1:] != cond.shape[1:] or uncond.dtype != cond.dtype):
             raise ValueError("slab pool: condition and unconditional_condition differ in shape or dtype")
         if cond2 is not None and (cond2.shape[1:] != cond.shape[1:] or cond2.dtype != cond.dtype):
-            raise ValueError("slab pool: condition and condition2 differ in shape or dtype")
+            raise ValueError("slab pool: condition and %s differ in shape or dtype" % third)
         return cond, uncond, cond2
 
     def _blend_of(self, mb, x, plan, sd):
@@ -641,7 +708,7 @@ class SlabPool:
         self._like, self._sd = like, sd
         w = s._wrapped
         self._cfg = w is not None and w.effective_guidance == "classifier-free"
-        self._copies = 3 if self._pr else 2 if self._cfg else 1     # copies of a state the network's input holds
+        self._copies = 3 if self._three else 2 if self._cfg else 1  # copies of a state the network's input holds
         self._nS = nS = self._copies * S
         self._per = per = int(np.prod(shape, dtype=np.int64)) if shape else 1
         self._rowb = per * _esize(sd)
@@ -711,7 +778,7 @@ class SlabPool:
                 self._apg_admit(q, ra)
             if q.zstar is not None:
                 self._zstar_admit(q, ra)
-            if self._pr:
+            if self._three:
                 self._pair_admit(q, ra)
             if q.blend is not None:
                 self._blend_admit(q, rows, ra)
@@ -751,7 +818,7 @@ class SlabPool:
         if w.guidance_type != "classifier-free":
             return w.model(x, t, **w.model_kwargs), None, None
         out = w.model(x, t, self._cslab, **w.model_kwargs)
-        if self._pr:
+        if self._three:
             e1, e0, e2 = out.chunk(3)
             return e0, e1, e2
         if not self._cfg:
@@ -858,7 +925,8 @@ class SlabPool:
         st["flags"] = np.where(on, np.where(self._zsel[rows], st["flags"] | z, st["flags"] & ~z), st["flags"])
 
     # ------------------------------------------------------------------------------------------------------------------
-    # guidance over two conditions (a pair=True pool).  Row fields: ps1, ps2.  Checked at submit: _pair_params.  Nothing else is
+    # guidance over two conditions (a pair=True pool) and Perp-Neg (a perp_neg=True pool: the same slabs, rows and records; s in
+    # ps1, w in ps2, DPM_F_CFG2_PERP in the records' flags as _prep_stage bound it).  Row fields: ps1, ps2.  Checked at submit: _pair_params.  Nothing else is
     # kept by the pool: the kind has no state; its third output and third copy are pointers of the tick (_buffer_records).
     # ------------------------------------------------------------------------------------------------------------------
     def _pair_admit(self, q, ra):
@@ -965,7 +1033,7 @@ class SlabPool:
                 self._apg_tick(st, rows, rec)
             if self._zst:
                 self._zstar_tick(st, rows, rec)
-            if self._pr:
+            if self._three:
                 self._pair_tick(st, rows, rec)
             self._buffer_records(g, b, rows, rec, last, xin, xout, e0, e1, ed, e2)
             if self._apg:
@@ -1028,7 +1096,7 @@ class SlabPool:
         if self._cfg:
             b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + self.S * self._rowb) + rb)
             b["e1"] = np.uint64(e1.data_ptr()) + eb
-        if self._pr:                     # the third output, and the other two thirds of the network's next input
+        if self._three:                  # the third output, and the other two thirds of the network's next input
             b["e1"] = np.uint64(e1.data_ptr()) + eb
             b["g"] = np.uint64(e2.data_ptr()) + eb
             b["x_out2"] = np.where(last, np.uint64(0), np.uint64(xout.data_ptr() + self.S * self._rowb) + rb)

@@ -798,7 +798,7 @@ class DPM_Solver:
 
 
     def request_pool(self, mixed_shapes=False, slots=None, sde=False, thresholding=False, inpaint=False, rescale=False,
-                     apg=False, zero_star=False, pair=False):
+                     apg=False, zero_star=False, pair=False, perp_neg=False):
         """(extension) A pool of sampling requests for continuous batching: requests are submitted at any time with their
         own `sample()` arguments, every `step()` advances each active request by one stage -- the network once per request,
         then one fused launch for all of them whatever their positions -- and returns the finished ones.  Results are
@@ -835,8 +835,15 @@ class DPM_Solver:
         (`submit(x, ..., condition2=c2, guidance_scale=s, pair=(scale2, nested))`), their stages in the table-driven launch
         (DPM_TABLE_PAIR: one stage_pair_kernel_table launch that stores the result three times -- no `torch.cat([x] * 3)`);
         samples of whole 8-element groups.  Not together with sde / thresholding / inpaint / rescale / apg / zero_star;
-        without the flag a pool refuses a `cfg_pair` solver.  A `cfg_perp_neg` solver has no slab pool yet (a follow-up); a
-        RequestPool (no slots) takes it as it is, each of its stages a launch of its own inside the tick's call.
+        without the flag a pool refuses a `cfg_pair` solver.  `pair=True` refuses a `cfg_perp_neg` solver (its rows have no
+        per-sample pass): that solver's slab pool is `perp_neg=True`, below; a RequestPool (no slots) takes it as it is, each of
+        its stages a launch of its own inside the tick's call.
+        `slots=S, perp_neg=True`: the slab pool of a `cfg_perp_neg` wrapper (Perp-Neg): slabs of [3S, ...] in the wrapper's
+        order (empty prompt, positive, negative), every request with its own three conditions and two scales
+        (`submit(x, ..., negative_condition=n, guidance_scale=s, neg_scale=w)`, either scale without the other), their stages
+        in the table-driven launch (DPM_TABLE_PERP: one stage_perp_kernel_table launch, one workgroup per sample, that stores
+        the result three times -- no `torch.cat([x] * 3)`); samples of whole 8-element groups.  Not together with sde /
+        thresholding / inpaint / rescale / apg / zero_star / pair; without the flag a slab pool refuses a `cfg_perp_neg` solver.
         Every classifier-free slab pool takes a guidance scale per request: `submit(x, ..., guidance_scale=g)`."""
         if sde and slots is None:
             raise ValueError("request_pool: sde=True belongs to a slab pool (slots=...); a RequestPool takes sde per submit")
@@ -849,7 +856,22 @@ class DPM_Solver:
         if inpaint and thresholding:
             raise NotImplementedError("request_pool: inpaint=True with thresholding=True -- the thresholded table rows have "
                                       "no mask blend")
-        if pair:
+        if perp_neg:
+            if slots is None:
+                raise ValueError("request_pool: perp_neg=True belongs to a slab pool (slots=...)")
+            if not self._perp():
+                raise ValueError("request_pool: perp_neg=True needs a cfg_perp_neg wrapper (Perp-Neg guidance with a negative "
+                                 "scale other than 0)")
+            for name, why in (("sde", "no noise epilogue"), ("thresholding", "no thresholding"),
+                              ("inpaint", "no mask-blend epilogue"), ("rescale", "no guidance rescale"),
+                              ("apg", "no projected guidance"), ("zero_star", "no CFG-Zero* projection"),
+                              ("pair", "no linear second blend")):
+                if dict(sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg, zero_star=zero_star,
+                        pair=pair)[name]:
+                    raise NotImplementedError("request_pool: perp_neg=True with %s=True -- the Perp-Neg kernel has %s (a "
+                                              "follow-up)" % (name, why))
+            self._check_pair()
+        elif pair:
             if slots is None:
                 raise ValueError("request_pool: pair=True belongs to a slab pool (slots=...)")
             if self._perp():
@@ -882,7 +904,7 @@ class DPM_Solver:
                 raise ValueError("request_pool: a slab pool (slots=...) holds rows of one sample shape; mixed_shapes is the "
                                  "RequestPool's")
             return _slab.SlabPool(self, slots, sde=sde, thresholding=thresholding, inpaint=inpaint, rescale=rescale, apg=apg,
-                                  zero_star=zero_star, pair=pair)
+                                  zero_star=zero_star, pair=pair, perp_neg=perp_neg)
         return _pool.RequestPool(self, mixed_shapes=mixed_shapes)
 
     def capture(self, x, warmup=2, **sample_kwargs):

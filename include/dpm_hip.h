@@ -112,11 +112,16 @@ extern "C" {
    launch -- a kernel that owns a whole sample, takes the negative condition's direction perpendicular to the positive one's
    by a per-sample projection of the three raw outputs, then runs the usual conversion, update and stores (see
    DPM_F_CFG2_PERP; no entry point added, no struct changed).
+   221 DPM_TABLE_PERP (a flag on table_mode): Perp-Neg stages in the table -- every qualifying DPM_F_CFG2_PERP request owns a row
+   and a pair record (the record of version 219, in the same section), a group of them is ONE stage_perp_kernel_table launch, one
+   workgroup per sample, which stores the state up to three times; in such a call a flagged DPM_GUIDE_CFG2 request may carry
+   x_out2, with the THIRD copy of x_out in dpm_buffers.thr_hint (see "Table mode"; no entry point added, no struct changed, no
+   dpm_sizeof index added).
    The structs grow at their END only.  A host MUST zero-initialise every struct it passes (memset / = {0}: new trailing
    fields then read as "absent") and SHOULD check at load time that dpm_version() >= the version it was built against and
    that dpm_sizeof(DPM_SIZEOF_*) == its own sizeof() -- a host compiled against an older header passes shorter structs,
    and the library would read past their end (examples/native_host.c and dpm_solver_amd/_lib.py do both checks). */
-#define DPM_HIP_VERSION 220
+#define DPM_HIP_VERSION 221
 
 /* ---- status --------------------------------------------------------------------------- */
 enum {
@@ -361,7 +366,8 @@ enum {
                                  DPM_ERR_UNSUPPORTED (this version): everything DPM_GUIDE_CFG2 refuses -- DPM_F_THRESH,
                                  DPM_F_BLEND, DPM_F_NOISE, DPM_F_USER_X0, DPM_FORM_UNIPC, a non-NULL x_out2, a double state,
                                  eps_stride other than 0 or P, device-resident coefficients --; a batch above 2^31 - 1; a
-                                 table-mode call that carries the flag (DPM_TABLE_PAIR rows have no per-sample pass).  A record
+                                 table-mode call without DPM_TABLE_PERP (version 221; DPM_TABLE_PAIR rows have no per-sample
+                                 pass) that carries the flag.  A record
                                  that sets one of DPM_F_CFG_RESCALE / _APG / _ZSTAR is reported by those flags' checks first,
                                  and every check of DPM_GUIDE_CFG2 speaks before this flag's own.  No output byte is written in
                                  any error case.  One workgroup per sample (stage_perp_kernel); such a stage runs on its own in
@@ -467,11 +473,18 @@ enum { DPM_TABLE_PAIR = 16384 }; /* version 219: a flag OR-ed onto DPM_TABLE_FIL
                                     in its dpm_buffers.thr_hint.  (Bit 8192 is unassigned -- table_mode 8192 | 1 is pinned as
                                     DPM_ERR_ARG since version 217.  Every mode with one of the bits 16, 64, 256, 1024, 2048,
                                     8192, or a bit from 32768 on, stays DPM_ERR_ARG.) */
+enum { DPM_TABLE_PERP = 65536 }; /* version 221: a flag OR-ed onto DPM_TABLE_FILL / DPM_TABLE_LAUNCH, with or without the seven
+                                    flags above: DPM_F_CFG2_PERP stages take rows too, each with a pair record (DPM_TABLE_PAIR_BYTES,
+                                    in the pair-record section, which is present under either flag), and a flagged DPM_GUIDE_CFG2
+                                    request of the call may carry x_out2 together with a third copy of x_out in its
+                                    dpm_buffers.thr_hint.  (Bit 32768 is unassigned -- table_mode 32768 | 1 is pinned as
+                                    DPM_ERR_ARG since version 219.  Every mode with one of the bits 16, 64, 256, 1024, 2048,
+                                    8192, 32768, or a bit from 131072 on, stays DPM_ERR_ARG.) */
 #define DPM_TABLE_MAGIC 0x4c425444u /* "DTBL", the first word of a table's header */
 #define DPM_TABLE_NOISE_BYTES 32    /* one noise record (= dpm_sizeof(DPM_SIZEOF_TABLE_NOISE)) */
 #define DPM_TABLE_BLEND_BYTES 48    /* one blend record (= dpm_sizeof(DPM_SIZEOF_TABLE_BLEND)) */
 #define DPM_TABLE_APG_BYTES 32      /* one APG record (= dpm_sizeof(DPM_SIZEOF_TABLE_APG)) */
-#define DPM_TABLE_PAIR_BYTES 16     /* one pair record (= dpm_sizeof(DPM_SIZEOF_TABLE_PAIR)) */
+#define DPM_TABLE_PAIR_BYTES 16     /* one pair record (= dpm_sizeof(DPM_SIZEOF_TABLE_PAIR)); a Perp-Neg row's record too */
 
 /* ---- buffers of one launch ------------------------------------------------------------- */
 typedef struct dpm_buffers {
@@ -842,16 +855,44 @@ DPM_API int dpm_stage_launch(const dpm_stage* st, const dpm_buffers* b, void* st
        + (DPM_TABLE_NOISE ? n_req * DPM_TABLE_NOISE_BYTES : 0) + (DPM_TABLE_BLEND ? n_req * DPM_TABLE_BLEND_BYTES : 0)
        + (DPM_TABLE_APG ? n_req * DPM_TABLE_APG_BYTES : 0)
        + DPM_TABLE_PAIR_BYTES * i
-   and the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + [DPM_TABLE_NOISE_BYTES] +
+   (the section is present under DPM_TABLE_PAIR or, from version 221, DPM_TABLE_PERP) and the table is dpm_sizeof(DPM_SIZEOF_TABLE_HEADER) + n_req * (dpm_sizeof(DPM_SIZEOF_TABLE_ROW) + [DPM_TABLE_NOISE_BYTES] +
    [DPM_TABLE_BLEND_BYTES] + [DPM_TABLE_APG_BYTES] + [DPM_TABLE_PAIR_BYTES]) bytes.  A record is two device pointers: g of the
    request's dpm_buffers, then its thr_hint (NULL: no copies).  The row is a row like any other: 8 pointers (x_out2 the eighth)
    and the 20 words of stage scalars, s1 in cfg_scale, s2 in cg_scale.  FILL leaves the pair-record slots of rows of other kinds
    untouched.  Without the flag every call is version 218's: x_out2 on a DPM_GUIDE_CFG2 request is refused, thr_hint is not
    read, and such a request owns no row.  Every element gets the bits of its request's own dpm_stage_launch.
+   Perp-Neg rows (version 221): DPM_TABLE_PERP OR-ed onto either mode, alone or with any of the seven flags above, makes the
+   same tick with Perp-Neg stages (DPM_F_CFG2_PERP on a DPM_GUIDE_CFG2 record) in the table (stage_perp_kernel_table: the
+   kernel of the request's own launch, one workgroup of 512 threads per sample, with pointers and stage scalars read from the
+   sample's row, the third output and the third copy from its pair record; no cluster, no workspace, no wait on another
+   workgroup).  A flagged request owns a row when dpm_stage_launch accepts it -- finite s and w, no DPM_F_THRESH / DPM_F_BLEND /
+   DPM_F_NOISE / DPM_F_USER_X0, no DPM_FORM_UNIPC and none of its flags, a 2- or 4-byte dtype pair, a dense network output --
+   and its form is LIN1, TWO, MS3 or DPM_FORM_DENOISE, its evaluation state is its state, its SAMPLE, n / batch elements, is
+   whole 8-element groups (so a multiple of 16 bytes in either dtype: the kernel works per sample, in 16-byte accesses), e0,
+   e1, g and x_out are set, and every buffer -- x_out2 and the third copy included -- is 16-byte aligned.  Such requests form
+   groups of their own that agree on dtypes, n, batch, model type, guidance kind and DPM_F_TO_X0; the four forms, both scales,
+   DPM_F_STORE_M and rows with and without the copies share a group: each is the row's own.  Every group, from ONE member on,
+   is one run of rows and ONE launch (below 2^31 samples), the runs in the order the groups open, among those of the other
+   families.  A flagged request never owns a two-condition row: in a DPM_TABLE_PAIR | DPM_TABLE_PERP call one that does not
+   qualify here (a sample of 12 elements, a misaligned buffer ...) goes, in the same call, as its own dpm_stage_launch
+   (stage_perp_kernel), as it does in mode 0: the same bits, one more launch.
+   The record is the pair record of version 219 -- g, then thr_hint (NULL: no copies) -- in the same section at the same
+   offset: the section is present when the call carries DPM_TABLE_PAIR or DPM_TABLE_PERP or both, n_req records either way, and
+   the table's size counts [DPM_TABLE_PAIR_BYTES] once under either flag.  For a table_mode without DPM_TABLE_PERP offsets and
+   size are those of version 219.  The copies follow the rules above: in a call that carries DPM_TABLE_PERP a flagged
+   DPM_GUIDE_CFG2 request may carry x_out2 and then the THIRD copy in dpm_buffers.thr_hint; one without the other is
+   DPM_ERR_ARG with the text above (it names DPM_TABLE_PERP in place of DPM_TABLE_PAIR when the call carries only that flag);
+   copies on a request that owns neither a pair row nor a Perp-Neg row are DPM_ERR_UNSUPPORTED ("stage_launch: DPM_GUIDE_CFG2
+   with x_out2 (the kernel has no second store)"); every request is checked before anything is written or launched.  The
+   kernel stores the state to x_out and, where the row carries the copies, to both of them, each advanced to the workgroup's
+   sample.  Without the flag every call is version 220's: a DPM_F_CFG2_PERP request in a table-mode call is refused
+   ("stage_launch_multi: DPM_F_CFG2_PERP in a table-mode call (the table's rows have no per-sample pass)").  Every sample gets
+   the bits of its request's own dpm_stage_launch.
    Any other table_mode (valid: DPM_TABLE_FILL or DPM_TABLE_LAUNCH, plus any of DPM_TABLE_NOISE, DPM_TABLE_THRESH, DPM_TABLE_BLEND,
-   DPM_TABLE_RESCALE, DPM_TABLE_APG, DPM_TABLE_ZSTAR, DPM_TABLE_PAIR: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46,
+   DPM_TABLE_RESCALE, DPM_TABLE_APG, DPM_TABLE_ZSTAR, DPM_TABLE_PAIR, DPM_TABLE_PERP: 1, 2, 5, 6, 9, 10, 13, 14, 33, 34, 37, 38, 41, 42, 45, 46,
    each of those plus 128, each of all these plus 512 -- the 64 modes of version 215 --, each of those 64 plus 4096 -- the 128
-   modes of version 217 --, and each of those 128 plus 16384; bits 16, 64, 256, 1024, 2048 and 8192 are unassigned), a non-zero
+   modes of version 217 --, each of those 128 plus 16384 -- the 256 modes of version 219 --, and each of those 256 plus 65536; bits 16, 64, 256, 1024, 2048,
+   8192 and 32768 are unassigned), a non-zero
    one without per_request_stages, or with fuse_shapes == 1:
    DPM_ERR_ARG. */
 #define DPM_MULTI_MAX 32
