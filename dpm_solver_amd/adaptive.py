@@ -98,12 +98,16 @@ class _AdaptiveRun:
 
 def adaptive_device(self, x, order, t_T, t_0, h_init, atol, rtol, theta, t_err, solver_type):
     """dpm_solver_adaptive with the controller on the device (C ABI dpm_adaptive_*): no
-    device -> host synchronisation decides anything.  The host enqueues one iteration ahead of the device
-    (`adaptive_lookahead`): before iteration i it waits -- on an event, not on a tensor -- until the device has taken
-    the decisions up to iteration i - 1 - lookahead and reads the host-mapped `done` word.  Iterations enqueued after
-    the device reached t_0 are no-ops in the solver kernels (the network calls in them are the price of the
-    look-ahead: at most `lookahead` iterations).  Under stream capture exactly `adaptive_max_iterations` are
-    recorded.
+    device -> host synchronisation decides anything.  The host enqueues ahead of the device (`adaptive_lookahead`,
+    clamped to 0..24): before iteration i > lookahead it waits -- on an event, not on a tensor -- until begin
+    i - 1 - lookahead has run and reads that begin's verdict from the status ring in host-mapped memory
+    (dpm_adaptive_done_at: entry begin & 31 of 32 -- the host reads at most 25 begins behind, before a later begin
+    can overwrite the entry).  Begin k decides iteration k - 1, so with U useful iterations begin U is the first whose
+    verdict is `done`, the host sees it before iteration U + 1 + lookahead, and the run is exactly U + 1 + lookahead
+    iterations of `order` network calls each.  The iterations enqueued after the device reached t_0 are no-ops in the
+    solver kernels; the network calls in them are the price of the look-ahead: lookahead + 1 iterations (one even at a
+    look-ahead of 0: iteration U is enqueued before begin U can be read).  Under stream capture exactly
+    `adaptive_max_iterations` are recorded.
     A NaN error estimate ends the run on the device (done == 2, include/dpm_hip.h): the step is rejected, the time
     vectors keep their last finite values and the iterations already enqueued are no-ops; the host raises the host
     loop's FloatingPointError at the run's end.  Under capture nothing can be raised: the recorded iterations after the

@@ -57,9 +57,9 @@ class DPM_Solver:
     # Engine options (extensions; class-level defaults, settable per instance).
     # adaptive solver: controller on the device (no host synchronisation per iteration); False = the reference's host
     # loop (one .item() per iteration, ref :1002).  With the device controller the host enqueues `adaptive_lookahead`
-    # iterations ahead of the device's decisions: up to that many iterations enqueued after t_end was reached still call
-    # the network (their solver kernels are no-ops) -- the reported NFE and the result do not change, the number of
-    # network calls can be (lookahead + 1) * order larger than the reference's.
+    # iterations ahead of the device's decisions (clamped to 0..24): the lookahead + 1 iterations enqueued after t_end was
+    # reached still call the network (their solver kernels are no-ops) -- the reported NFE and the result do not change,
+    # the number of network calls is (lookahead + 1) * order larger than the reference's.
     adaptive_on_device = True
     adaptive_lookahead = 1
     # per-call launch options of the C ABI (dpm_launch_opts), handed to every launch of this solver:
